@@ -20,7 +20,7 @@ dealt round-robin to their host threads).
 + clubs) of 2048 users per step, users split over the ranks, one engine context per GPU by
 default; value = hold-out users/s.
 
-Roofline of the dominant kernel (fas_post_kernel, the postings scan, by default;
+Roofline (--full) of the dominant kernel (fas_post_kernel, the postings scan, by default;
 fas_scan_kernel, the record-stream scan, with --scan-kernel stream), HIP events around every
 launch on the kernel's stream:
   achieved  = the bytes the kernel reads by its access pattern (pf_scan_bytes: headers, cell
@@ -34,11 +34,18 @@ launch on the kernel's stream:
               over the same time: an *equivalent* rate, NOT an HBM fraction (the postings scan
               never reads those records, so d3_equiv_x_peak can exceed 1); roofline.frac is the
               kernel's HBM fraction.
-CPU baseline: oracle/refcpu.cpp (the reference algorithm with its unordered_map data
+CPU baseline (--full): oracle/refcpu.cpp (the reference algorithm with its unordered_map data
 structures), one core, bounded sample of the same corpus, median per query; plus an
 all-cores context figure (one oracle per core).
 
-    python bench.py [--gpus N --steps K --warmup W]
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps and
+prints the result line (metric, value, unit, ms_per_step, ...).  --full adds everything else the
+line can carry: the CPU baselines, the rocprofv3 traffic pass, the roofline, the isolated launches,
+the top-k self-check and the cfg-3 sub-record (the --no-* switches subtract from --full).
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float32 / float64):
+with the same arguments the inputs are the same seeded ones, so two builds compare output for output.
+
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python bench.py --workload cfg4 --steps 5 --warmup 1     (cfg 4 at N = 1)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
@@ -64,6 +71,25 @@ METRIC = "FAS candidates scored/sec over 1.6M users, top-k=10; 1/2/4/8 GPU + %HB
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: the last timed step's results as d/<name>.npy."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {d}: " + ", ".join(sorted(arrays)))
+
+
+def topk_arrays(rows, k):
+    """Per-query (ids, scores) lists as two dense arrays: uids float64 [Q, k] (-1 where a list is
+    shorter than k; uids are exact in float64), scores float32 [Q, k] (0 there)."""
+    uids = np.full((len(rows), k), -1.0, np.float64)
+    scores = np.zeros((len(rows), k), np.float32)
+    for i, (u, s) in enumerate(rows):
+        uids[i, :len(u)] = u
+        scores[i, :len(s)] = s
+    return {"topk_uids": uids, "topk_scores": scores}
 
 
 def cpu_model():
@@ -250,7 +276,7 @@ def pmc_pass(args, select):
     d = tempfile.mkdtemp(prefix="pf_pmc_", dir=os.environ.get("TMPDIR", "/tmp"))
     cmd = [prof, "--pmc", "FETCH_SIZE", "--kernel-include-regex", "|".join(select), "-T", "--output-format", "csv",
            "-d", d, "-o", "run", "--", sys.executable, os.path.abspath(__file__), "--gpus", "1",
-           "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-pmc",
+           "--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-pmc",
            "--workload", args.workload, "--scan-kernel", args.scan_kernel, "--users", str(args.users),
            "--contexts", str(args.contexts), "--cfg5-batch", str(args.cfg5_batch),
            "--cfg3-steps", str(args.cfg3_steps)]
@@ -378,6 +404,8 @@ def measure_cfg3(engs, mine, warm, steps, dist=None, torch=None, use_async=True,
     for e in engs:
         e.jobs_stats_reset(time_pairs=True, count=False)
 
+    last_out = [None] * C  # per context, the results of its last step (--dump-outputs)
+
     def run_steps(t):  # context t: steps warm + t, warm + t + C, ...
         n = 0
         e = engs[t]
@@ -386,13 +414,15 @@ def measure_cfg3(engs, mine, warm, steps, dist=None, torch=None, use_async=True,
             for i in range(warm + t, warm + steps, C):
                 pend.append(e.recommend_collaborative_async(mine[i], TOPK, CFG3_LIMIT))
                 if len(pend) == depth:
-                    n += sum(len(o[0]) for o in e.wait(pend.pop(0)))
+                    last_out[t] = e.wait(pend.pop(0))
+                    n += sum(len(o[0]) for o in last_out[t])
             for p in pend:
-                n += sum(len(o[0]) for o in e.wait(p))
+                last_out[t] = e.wait(p)
+                n += sum(len(o[0]) for o in last_out[t])
             return n
         for i in range(warm + t, warm + steps, C):
-            out = e.recommend_collaborative(mine[i], TOPK, CFG3_LIMIT)
-            n += sum(len(o[0]) for o in out)
+            last_out[t] = e.recommend_collaborative(mine[i], TOPK, CFG3_LIMIT)
+            n += sum(len(o[0]) for o in last_out[t])
         return n
 
     t0 = time.perf_counter()
@@ -422,6 +452,7 @@ def measure_cfg3(engs, mine, warm, steps, dist=None, torch=None, use_async=True,
     st["pair_ms"], st["pair_launches"] = timing["pair_ms"], timing["pair_launches"]
     st["disp0"], st["disp1"] = disp0, timing["disp1"]
     st["elapsed"], st["results"], st["async"] = elapsed, nres, use_async
+    st["last_out"] = last_out[(steps - 1) % C] if steps > 0 else None  # the last timed step's results
     if dist:
         t = torch.tensor([st["pairs"], st["candidates"]], dtype=torch.float64, device="cuda")
         tm = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -495,6 +526,8 @@ def run_cfg3(args, engs, pf, torch, dist, world, rank, base, pmc, open_s):
     mine = cfg3_queries(args.users, warm, steps, rank, world)
     st = measure_cfg3(engs, mine, warm, steps, dist, torch, use_async=not args.sync_calls, depth=args.async_depth)
     C = len(engs)
+    if args.dump_outputs and rank == 0 and st["last_out"] is not None:
+        dump_outputs(args.dump_outputs, topk_arrays(st["last_out"], TOPK))
     f = cfg3_fields(st, steps, pmc)
     rec = {
         "metric": METRIC, "value": f.pop("value"), "unit": f.pop("unit"), "n_gpus": world, "steps": steps,
@@ -710,14 +743,18 @@ def run_cfg5(args, world, rank, local):
         dist.barrier()
     elapsed = time.perf_counter() - ts
     timing = sum_stats(lambda e: e.jobs_stats())
-    for e in engs:
-        e.jobs_stats_reset(time_pairs=False, count=True)
-    step()  # untimed replay: pair and byte counts of one step on this rank
-    st = sum_stats(lambda e: e.jobs_stats())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"rectests_summary": np.asarray(summary, np.float64)})
+    st = {"pairs": 0, "pair_record_bytes": 0, "pair_image_bytes": 0, "pair_alg_bytes": 0}
+    if args.full:  # untimed replay: pair and byte counts of one step on this rank (the roofline's)
+        for e in engs:
+            e.jobs_stats_reset(time_pairs=False, count=True)
+        step()
+        st = sum_stats(lambda e: e.jobs_stats())
     for e in engs:
         e.jobs_stats_reset(time_pairs=False, count=False)
     selfcheck = None
-    if world == 1:  # the batched driver against the sequential one on a small sample (untimed)
+    if world == 1 and args.full:  # the batched driver against the sequential one on a small sample (untimed)
         h, c = ds.eval_recommendation_tests(eng, 64, CFG5_TOPK, 0, 1, 128)
         selfcheck = list(pf.rec_tests_summary(h, c)) == list(ds.recommendation_tests(eng, 64, CFG5_TOPK))
     if dist:
@@ -773,6 +810,8 @@ def run_cfg5(args, world, rank, local):
         "driver_calls": "asynchronous (pf_eval_recommendation_tests_async: step i + 1 planned beside step i's "
                         "last device chunk)" if use_async else "synchronous",
     }
+    if not args.full:  # a plain run has no count replay: no pair counts, no roofline
+        rec["pairs_per_step"] = rec["pair_fas_per_s"] = rec["roofline"] = None
     if rank == 0 and world == 1 and base is not None:
         rec["cpu_baseline"] = base
         rec["speedup_vs_cpu"] = value / base["value"] if base.get("value") else None
@@ -880,6 +919,16 @@ def main():
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="N > 1 collectives: nccl (RCCL over xGMI, one rank per GPU) or gloo through host memory "
                          "(ranks may share one GPU: a correctness rehearsal of the multi-GPU path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the CPU baselines, the rocprofv3 FETCH_SIZE "
+                         "pass, the roofline, the isolated launches, the top-k self-check and the cfg-3 sub-record "
+                         "(a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned as DIR/<name>.npy (cfg2 / "
+                         "cfg4 / cfg3: topk_uids float64 and topk_scores float32, [queries, 10], -1 / 0 past a "
+                         "shorter list; cfg5: rectests_summary float64); the inputs are seeded, so two builds run "
+                         "with the same arguments compare output for output (inside the tree, bench_out/ is "
+                         "ignored by git)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 FETCH_SIZE pass (traffic = null)")
     ap.add_argument("--time-every", type=int, default=1,
@@ -925,6 +974,8 @@ def main():
         args.steps = 200 if args.workload == "cfg2" else 50
     if args.contexts is None:
         args.contexts = 1
+    if not args.full:  # a plain run: nothing beside the headline figure
+        args.no_cpu_baseline = args.no_pmc = args.no_cfg3 = True
     if args.hw_queues > 0:
         os.environ["GPU_MAX_HW_QUEUES"] = str(min(16, args.hw_queues))  # before any HIP call
     if args.workload == "cfg5":
@@ -943,12 +994,13 @@ def main():
     want_kernel = "fas_scan_kernel" if args.scan_kernel == "stream" else "fas_post_kernel"
     base, base3, pmcs = None, None, {}
     if rank == 0 and world == 1:
-        if args.workload == "cfg3" or sub3:
-            steps3 = args.steps if args.workload == "cfg3" else args.cfg3_steps
-            warm3 = args.warmup if args.workload == "cfg3" else W3
-            users3 = [int(u) for qs in cfg3_queries(args.users, warm3, steps3)[warm3:] for u in qs]
         if not args.no_cpu_baseline:
-            base, base3 = cpu_baselines(desc, args.users, users3 if (args.workload == "cfg3" or sub3) else None)
+            users3 = None
+            if args.workload == "cfg3" or sub3:
+                steps3 = args.steps if args.workload == "cfg3" else args.cfg3_steps
+                warm3 = args.warmup if args.workload == "cfg3" else W3
+                users3 = [int(u) for qs in cfg3_queries(args.users, warm3, steps3)[warm3:] for u in qs]
+            base, base3 = cpu_baselines(desc, args.users, users3)
             if args.workload == "cfg3":
                 base = base3
             log(f"cpu baseline: {base}")
@@ -1074,18 +1126,23 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # the last timed step's merged top-k, every query's row decoded
+        last = final.cpu().numpy().view(np.uint64)
+        dump_outputs(args.dump_outputs, topk_arrays([pf.decode_keys(row) for row in last], k))
     # sanity: the merged top-k of the last step rescored by the pair kernel
-    last = final.cpu().numpy().view(np.uint64)
-    uids, scores = pf.decode_keys(last[0])
-    chk = eng.fas_pairs(np.full(len(uids), qstream[warm + steps - 1][0], np.int32), uids)
-    consistent = bool(len(uids) == k and np.array_equal(chk.view(np.uint32), scores.view(np.uint32)))
+    consistent = None
+    if args.full:
+        last = final.cpu().numpy().view(np.uint64)
+        uids, scores = pf.decode_keys(last[0])
+        chk = eng.fas_pairs(np.full(len(uids), qstream[warm + steps - 1][0], np.int32), uids)
+        consistent = bool(len(uids) == k and np.array_equal(chk.view(np.uint32), scores.view(np.uint32)))
 
     # One query per step on a caller's stream runs on the engine's two scan lanes (pf_ctx.h
     # ScanLane): consecutive launches overlap, so a launch's HIP events span its neighbours' tails.
     # After the timed region, the same queries once more one at a time (synchronised, untimed by
     # the step clock) give the kernel's isolated launch time beside it.
     isolated = None
-    if Q == 1 and not use_dist:
+    if Q == 1 and not use_dist and args.full:
         eng.profile_sample(1)
         eng.profile_reset()
         n_iso = min(steps, 20)
@@ -1104,8 +1161,9 @@ def main():
     value = Q * n_cand * steps / elapsed
     # bytes per launch by the kernel's access pattern, over the queries timed (this rank's shard)
     # one call per step: the byte model counts the image staging of a launch of Q queries
-    phys = np.concatenate([eng.scan_bytes(qstream[i]) for i in range(warm, warm + steps)])
-    timed_steps = list(range(0, steps, max(args.time_every, 1)))[:launches] if launches else []
+    # (--full only: the byte model builds every timed query's image on the host once more)
+    phys = np.concatenate([eng.scan_bytes(qstream[i]) for i in range(warm, warm + steps)]) if args.full else None
+    timed_steps = list(range(0, steps, max(args.time_every, 1)))[:launches] if launches and args.full else []
     phys_per_launch = (float(np.mean([phys[i * Q:(i + 1) * Q].sum() for i in timed_steps]))
                        if timed_steps else None)
     avg_launch_ms = scan_ms / launches if launches else None
@@ -1188,6 +1246,8 @@ def main():
         "topk_selfcheck": consistent,
         "host_enqueue_ms_per_step": t_submitted * 1e3 / steps,
     }
+    if not args.full:  # a plain run carries no roofline (no byte model, traffic pass or isolated launches)
+        rec["roofline"] = None
     if isolated is not None and phys_per_launch:
         # One query per step: consecutive launches overlap on the scan lanes (up to three in flight),
         # so a timed launch's HIP events span its neighbours' work and no launch runs alone.  The

@@ -7,8 +7,8 @@
 #   bench        default bench line (cfg 2, CPU baseline + PMC pass) -> bench.json
 #   prof         rocprofv3 kernel trace + stats of a 20-step cfg-2 run -> prof_default/
 #   cfgN         bench.py --workload cfgN               -> cfgN.json
-#   quick        cfg 2, 100 steps, no CPU baseline / PMC -> quick.json
-#   quick4       cfg 4, 3 steps, no CPU baseline / PMC   -> quick4.json
+#   quick        cfg 2, 100 steps, --full without the CPU baseline / PMC pass -> quick.json
+#   quick4       cfg 4, 3 steps, --full without the CPU baseline / PMC pass -> quick4.json
 #   forcedist    cfg 2 through the N > 1 step at world 1 (RCCL communicator + all-gather) -> forcedist.json
 #   quickv:V / quick4v:V  the same with the variant library vlib/V (tools/build_variant.sh)
 #   cfg5c1       cfg 5 at one context with the host stage clocks (PF_DEBUG host_prof=1) -> cfg5c1.err
@@ -24,7 +24,7 @@ TAG=$1
 shift
 cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out/$TAG && export TMPDIR=/tmp
 O=gpurun_out/$TAG
-Q="--no-cpu-baseline --no-pmc"
+Q="--full --no-cpu-baseline --no-pmc"
 for S in "$@"; do
     echo "== $S $(date +%T)"
     case $S in
@@ -37,7 +37,7 @@ for S in "$@"; do
     tests:*)
         timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "${S#tests:}" > $O/gputest_k.log 2>&1 || exit 1 ;;
     bench)
-        timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || exit 2 ;;
+        timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 2 ;;
     prof)
         timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_default -o run -- python3 bench.py --steps 20 --warmup 5 $Q > $O/prof.json 2> $O/prof.err || exit 3 ;;
     cfg3h|cfg3h:*)
@@ -51,7 +51,7 @@ for S in "$@"; do
         # kernel trace of cfg 5 at one context (host-side gaps between the device stages)
         timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace --stats -d $O/prof_cfg5 -o run -- python3 bench.py --workload cfg5 --contexts 1 --steps 5 --warmup 2 $Q > $O/prof5.json 2> $O/prof5.err || exit 3 ;;
     cfg[2345])
-        timeout -k 10 900 python3 bench.py --workload $S > $O/$S.json 2> $O/$S.err || exit 4 ;;
+        timeout -k 10 900 python3 bench.py --full --workload $S > $O/$S.json 2> $O/$S.err || exit 4 ;;
     quick)
         timeout -k 10 300 python3 bench.py --steps 100 --warmup 10 $Q > $O/quick.json 2> $O/quick.err || exit 5 ;;
     quickv:*)

@@ -17,6 +17,6 @@ timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -T --output-format csv -d $O/cali
 python3 tools/fetch_calib.py $O/calib $O/fetch_calib.out > $O/fetch_calib.json
 cp $O/fetch_calib.json profiles/fetch_calib_r2.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $O/trace -o run \
-    -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-pmc --scan-kernel $SK > $O/trace.log 2>&1
-timeout -k 10 600 python3 bench.py --scan-kernel $SK > $O/bench.json 2> $O/bench.err
+    -- python3 bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-pmc --scan-kernel $SK > $O/trace.log 2>&1
+timeout -k 10 600 python3 bench.py --full --scan-kernel $SK > $O/bench.json 2> $O/bench.err
 cat $O/bench.json

@@ -5,7 +5,7 @@ for rep in $(seq $R); do
   for spec in "$@"; do
     IFS=/ read -r h d <<< "$spec"
     [ "$d" = "-" ] && d=""
-    timeout -k 10 300 env PF_DEBUG=$d python3 bench.py --steps 20 --warmup 5 --hw-queues $h --no-cpu-baseline --no-pmc --no-cfg3 > $O/x.json 2> $O/x.err || exit 1
+    timeout -k 10 300 env PF_DEBUG=$d python3 bench.py --steps 20 --warmup 5 --hw-queues $h --full --no-cpu-baseline --no-pmc --no-cfg3 > $O/x.json 2> $O/x.err || exit 1
     (echo -n "$spec "; tail -1 $O/x.json) >> $O/all.txt
   done
 done
