@@ -4,7 +4,10 @@
 TEST INFRASTRUCTURE ONLY — runs in the build container, where /root/reference
 exists.  Steps:
   1. tools/libpokec_synth.so writes seeded synthetic corpora in the reference's
-     own on-disk formats (users_encoded.csv, adjacency.csv, ...);
+     own on-disk formats (users_encoded.csv, adjacency.csv, ...); corpus "E" (the edge
+     domain: split columns, long runs, hit lists at their caps, values past the tables,
+     clones, sparse uids) is written by tests/edge_corpus.py, with its planted queries
+     and pairs in queries.txt / pairs_extra.txt for the harness;
   2. oracle/_ref/ref_fixture (the reference compiled from its own sources by
      oracle/Makefile, linked with a harness) loads each corpus exactly like
      api_cli does and dumps parsed profiles, IDF, FAS pairs, recommender
@@ -29,7 +32,9 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import synth  # noqa: E402
+import edge_corpus  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -39,9 +44,20 @@ CORPORA = {
               npairs=60000, pair_seed=7, holdout=12, rectest=6, digest_holdout=60, digest_rectest=120),
     "B": dict(n_users=1200, seed=23, edge_cases=1, normalizers=0, median=0,
               npairs=20000, pair_seed=9, holdout=0, rectest=0, digest_holdout=0, digest_rectest=0),
+    "E": dict(builder="edge", n_users=edge_corpus.N_USERS,
+              npairs=20000, pair_seed=5, holdout=0, rectest=0, digest_holdout=0, digest_rectest=0),
 }
 # config 1 plumbing (BASELINE.json configs[0]): api_cli with load_users=10000
 API_CORPUS = dict(n_users=10000, seed=31, edge_cases=0, normalizers=1, median=1)
+
+
+def write_corpus(c, work):
+    if c.get("builder") == "edge":
+        edge_corpus.write_reference_files(work)
+        return
+    corpus = synth.Corpus(n_users=c["n_users"], seed=c["seed"], edge_cases=c["edge_cases"])
+    corpus.write_reference_files(work, normalizers=c["normalizers"], median=c["median"])
+    corpus.close()
 
 
 def run_harness(work, out, c):
@@ -100,9 +116,7 @@ def main():
         out = os.path.join(GOLDEN, name)
         os.makedirs(out, exist_ok=True)
         with tempfile.TemporaryDirectory() as work, tempfile.TemporaryDirectory() as raw:
-            corpus = synth.Corpus(n_users=c["n_users"], seed=c["seed"], edge_cases=c["edge_cases"])
-            corpus.write_reference_files(work, normalizers=c["normalizers"], median=c["median"])
-            corpus.close()
+            write_corpus(c, work)
             run_harness(work, raw, c)
             for fn in sorted(os.listdir(raw)):
                 gz_copy(os.path.join(raw, fn), os.path.join(out, fn + ".gz"))
@@ -118,10 +132,10 @@ def main():
         corpus.close()
         uids = [1, 2, 17, 4242, 9999, 10000]
         lines, stdout = transcript_for(work, uids)
-        with gzip.open(os.path.join(out, "transcript_stdin.txt.gz"), "wt", compresslevel=9) as f:
-            f.write("\n".join(lines) + "\n")
-        with gzip.open(os.path.join(out, "transcript_stdout.txt.gz"), "wt", compresslevel=9) as f:
-            f.write(stdout)
+        for fn, text in (("transcript_stdin.txt", "\n".join(lines) + "\n"), ("transcript_stdout.txt", stdout)):
+            with open(os.path.join(out, fn + ".gz"), "wb") as raw, \
+                    gzip.GzipFile(filename="", fileobj=raw, mode="wb", compresslevel=9, mtime=0) as f:  # no timestamp
+                f.write(text.encode())
     manifest["api_cli"] = dict(API_CORPUS, load_users="10000", uids=uids)
     gen_norms()
     manifest["norm_runs"] = {k: list(v) for k, v in NORM_RUNS.items()}

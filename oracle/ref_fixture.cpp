@@ -11,6 +11,8 @@
 //
 // usage: ref_fixture <workdir-with-data-and-config> <outdir> <npairs> <seed>
 //                    <holdout_samples> <rectest_samples> [<digest_holdout> <digest_rectest>]
+// Two optional files in the work directory name planted cases: queries.txt (one uid per line,
+// appended to the query set) and pairs_extra.txt ("a b" per line, appended to pairs.txt).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -164,6 +166,16 @@ int main(int argc, char** argv) {
             fprintf(f, "%d %d %08x\n", a, b, fbits(rec.profile_similarity(profiles.at(a), pb->second)));
         }
     }
+    std::vector<std::pair<int, int>> extra_pairs;  // planted pairs (both users must be loaded)
+    if (FILE* e = fopen("pairs_extra.txt", "r")) {
+        int a, b;
+        while (fscanf(e, "%d %d", &a, &b) == 2)
+            if (profiles.count(a) && profiles.count(b)) extra_pairs.emplace_back(a, b);
+        fclose(e);
+    }
+    for (auto& ab : extra_pairs)
+        fprintf(f, "%d %d %08x\n", ab.first, ab.second,
+                fbits(rec.profile_similarity(profiles.at(ab.first), profiles.at(ab.second))));
     fclose(f);
 
     // ---- query set ----
@@ -176,6 +188,12 @@ int main(int argc, char** argv) {
     queries.push_back(-5);                 // unknown user
     queries.push_back(uids.back() + 1000); // unknown user
     for (int u : uids) if (!adj.count(u)) { queries.push_back(u); break; }  // no adjacency row
+    if (FILE* e = fopen("queries.txt", "r")) {  // planted queries
+        int u;
+        while (fscanf(e, "%d", &u) == 1)
+            if (std::find(queries.begin(), queries.end(), u) == queries.end()) queries.push_back(u);
+        fclose(e);
+    }
 
     // ---- A12/A14/A15 recommenders as api_cli calls them (topk 20, limit 5000) + limits ----
     f = open("recs.txt");
@@ -259,6 +277,9 @@ int main(int argc, char** argv) {
             int a = uids[pick(rx_rng)], b = uids[pick(rx_rng)];
             fprintf(f, "%d %d %08x\n", a, b, fbits(rx.profile_similarity(profiles.at(a), profiles.at(b))));
         }
+        for (auto& ab : extra_pairs)
+            fprintf(f, "%d %d %08x\n", ab.first, ab.second,
+                    fbits(rx.profile_similarity(profiles.at(ab.first), profiles.at(ab.second))));
         fclose(f);
         f = open("idf_explicit_recs.txt");
         for (int u : queries) {

@@ -353,6 +353,10 @@ def regen_reference_dir(name, dest):
     """Regenerate golden corpus `name` (or 'api') in the reference's formats under dest."""
     m = manifest()
     c = m["api_cli"] if name == "api" else m["corpora"][name]
+    if c.get("builder") == "edge":  # corpus E: tests/edge_corpus.py
+        import edge_corpus
+        assert c["n_users"] == edge_corpus.N_USERS
+        return edge_corpus.write_reference_files(dest)
     corpus = synth.Corpus(n_users=c["n_users"], seed=c["seed"], edge_cases=c["edge_cases"])
     corpus.write_reference_files(dest, normalizers=c["normalizers"], median=c["median"])
     corpus.close()

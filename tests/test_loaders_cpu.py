@@ -45,7 +45,7 @@ def desc_arrays(ptr):
     return out
 
 
-@pytest.fixture(scope="module", params=["A", "B", "api"])
+@pytest.fixture(scope="module", params=["A", "B", "E", "api"])
 def loaded(request):
     name = request.param
     pf = tl.product()

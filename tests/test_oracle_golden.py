@@ -6,7 +6,7 @@ import pytest
 import pokec_testlib as tl
 
 
-@pytest.fixture(scope="module", params=["A", "B"])
+@pytest.fixture(scope="module", params=["A", "B", "E"])
 def gold(request):
     name = request.param
     corpus = tl.golden_corpus(name)
@@ -111,7 +111,7 @@ def test_oracle_driver_digests():
     assert np.array_equal(orc.recommendation_tests_digest(m["digest_rectest"], 10), ref)
 
 
-@pytest.mark.parametrize("name", ["A", "B"])
+@pytest.mark.parametrize("name", ["A", "B", "E"])
 def test_oracle_explicit_idf(name):
     """A7 and set_tfidf_index: with an explicit idf map that omits columns (raw-count cosine,
     recommender.cpp:141-163), omits tokens (idf 1.0) and holds an empty map, the oracle's FAS
