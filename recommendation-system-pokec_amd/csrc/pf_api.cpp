@@ -242,15 +242,6 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
     return PF_OK;
 }
 
-void emit(const Ranked& r, int i, int topk, int32_t* ou, float* os, int32_t* oc) {
-    int n = std::min<int>((int)r.size(), topk);
-    for (int k = 0; k < n; ++k) {
-        ou[(int64_t)i * topk + k] = r[k].first;
-        os[(int64_t)i * topk + k] = r[k].second;
-    }
-    oc[i] = n;
-}
-
 // K5 mode word: bit 0 dynamic block hand-out (each workgroup's first block, then the next
 // unclaimed one), for one-query launches only.  r2fb A/B: 205.3 / 205.6 us vs 206.9 / 206.9 us
 // static per cfg-2 launch; batches (one block per workgroup in L2-sharing order) stay static
@@ -397,7 +388,6 @@ int lane_begin(pf_ctx* c, hipStream_t caller, LaneUse& u) {
     }
     // the lanes run on the context's stream and the job pipeline's aux streams (created at open):
     // streams of their own would share the process's four hardware queues with them
-    // (PF_DEBUG lazy_aux=1: no aux streams yet, every lane on the context's stream)
     const hipStream_t ls[3] = {c->stream, c->jb.aux, c->jb.aux2};
     ln->st = li < 3 ? ls[li] : c->lane_st[li];
     if (!ln->st) ln->st = c->stream;
@@ -801,7 +791,7 @@ int emit_jobs(pf_ctx* c, std::vector<pf::Job>& jobs, int topk, int32_t* ou, floa
     if (topk == 0 || jobs.empty()) return PF_OK;
     const int rc = pf::run_jobs(c, jobs);
     if (rc != PF_OK) return rc;
-    for (size_t i = 0; i < jobs.size(); ++i) emit(jobs[i].out, (int)i, topk, ou, os, oc);
+    for (size_t i = 0; i < jobs.size(); ++i) pf::emit(jobs[i].out, (int)i, topk, ou, os, oc);
     return PF_OK;
 }
 
@@ -810,6 +800,15 @@ int emit_jobs(pf_ctx* c, std::vector<pf::Job>& jobs, int topk, int32_t* ou, floa
 namespace pf {
 
 const std::unordered_map<int32_t, std::vector<int32_t>>& base_adj(const pf_ctx* c) { return c->hc.adj; }
+
+void emit(const std::vector<std::pair<int32_t, float>>& r, int i, int topk, int32_t* ou, float* os, int32_t* oc) {
+    const int n = std::min<int>((int)r.size(), topk);
+    for (int k = 0; k < n; ++k) {
+        ou[(int64_t)i * topk + k] = r[k].first;
+        os[(int64_t)i * topk + k] = r[k].second;
+    }
+    oc[i] = n;
+}
 
 HostProf::HostProf() {
     on = debug_long("host_prof", 0) != 0;
@@ -885,11 +884,8 @@ int pf_open(const pf_corpus_desc* desc, int device, pf_ctx** out) {
     // at the first job call, after a torch stream pool, they ran the cfg-3 sub-record of the
     // default bench line at 0.466 vs 0.415 ms per step, r5l)
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        (pf::debug_long("lazy_aux", 0) == 0 &&
-         (hipStreamCreateWithFlags(&c->jb.aux, hipStreamNonBlocking) != hipSuccess ||
-          hipStreamCreateWithFlags(&c->jb.aux2, hipStreamNonBlocking) != hipSuccess ||
-          hipEventCreateWithFlags(&c->jb.ev_fork, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&c->jb.ev_join, hipEventDisableTiming) != hipSuccess)) ||
+        hipStreamCreateWithFlags(&c->jb.aux, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->jb.aux2, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
         c->err = "stream/event creation failed";
         return bail(PF_ENODEV);
@@ -1025,8 +1021,6 @@ void pf_close(pf_ctx* c) {
         (void)hipStreamSynchronize(c->jb.aux2);
         (void)hipStreamDestroy(c->jb.aux2);
     }
-    if (c->jb.ev_fork) (void)hipEventDestroy(c->jb.ev_fork);
-    if (c->jb.ev_join) (void)hipEventDestroy(c->jb.ev_join);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -87,5 +87,7 @@ uint64_t next_call_ticket(pf_ctx* c);
 // A batched driver call (its versioned edit set) starts or ends (pf_jobs_plan.cpp).
 void jobs_view_scope(pf_ctx* c);
 const std::unordered_map<int32_t, std::vector<int32_t>>& base_adj(const pf_ctx* c);
+// A ranked list into row i of a call's output arrays (topk entries per row; oc[i] = the count).
+void emit(const std::vector<std::pair<int32_t, float>>& r, int i, int topk, int32_t* ou, float* os, int32_t* oc);
 
 }  // namespace pf

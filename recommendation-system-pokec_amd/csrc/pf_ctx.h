@@ -115,12 +115,13 @@ struct JobsState {
     bool pimg = false;
     DBuf d_pimg;
     std::vector<int64_t> pimg_off;
-    // a chunk's K3 gathers (+ the dispatch orders) run on aux beside its K6 images on the context's
-    // stream (both latency-bound, independent), joined before the pair kernel
+    // consecutive chunks alternate (pp) between aux and the context's stream for their upload, K9,
+    // K3 gathers, dispatch orders, K6 images and pair kernel, so a chunk's gathers run beside the
+    // previous chunk's pair kernel; both aux streams are created at open
     hipStream_t aux = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // K4' (collaborative), K8, K7 (clubs) and a chunk's result copies run on aux2 after its pair
-    // kernel (Ws::ev_pairs), beside the next chunk's pair kernel (pf_jobs_plan.cpp launch_chunk)
+    // K7 (clubs), its jobs' K8 and a chunk's result copies run on aux2 after its pair kernel
+    // (Ws::ev_pairs), beside the next chunk's pair kernel; K4' (collaborative) and the other jobs'
+    // K8 too when the chunk has no clubs jobs (pf_jobs_plan.cpp enqueue_chunk)
     hipStream_t aux2 = nullptr;
     int pp = 0;  // the last chunk's ping-pong stream (1: aux, 0: the context's; pf_jobs_plan.cpp launch_chunk)
     std::unordered_set<int32_t> edited;          // uids whose adj_list row differs from the open-time row
@@ -134,9 +135,10 @@ struct JobsState {
     DevView view{};
     DBuf d_view_node, d_view_ver, d_view_off, d_view_len, d_view_nbr;
     // per-chunk workspaces, double-buffered: chunk i + 1 is planned and launched while chunk i
-    // runs (run_all in pf_jobs_plan.cpp).  Both slots queue on the context's stream: a stream per
-    // slot, so that consecutive calls overlap on the device, measured slower (r3y: the pair kernel
-    // 0.344 -> 0.385 ms beside the next call's images and gathers; cfg 3 1.93e9 -> 1.71e9).
+    // runs (run_all in pf_jobs_plan.cpp).  A slot owns no stream (its chunk takes the ping-pong
+    // stream of its turn, pp above): a stream per slot, so that consecutive calls overlap on the
+    // device, measured slower (r3y: the pair kernel 0.344 -> 0.385 ms beside the next call's images
+    // and gathers; cfg 3 1.93e9 -> 1.71e9).
     struct Ws {
         DBuf d_plan, d_ht, d_seq, d_slots, d_ids, d_fl, d_img, d_scr;  // d_plan: the plan, then the results
         DBuf d_acc;                // clubs accumulators (zero between uses)
@@ -144,18 +146,17 @@ struct JobsState {
         int64_t acc_jobs = 0;      // clubs jobs the accumulators hold
         PinBuf h_plan, h_out;
         hipEvent_t done = nullptr;  // recorded after the chunk's result copies (on aux2)
-        hipEvent_t ev_pairs = nullptr, ev_main = nullptr;  // the pair kernel queued on the context's stream / K4' + K8 there (collab_main=1)
+        hipEvent_t ev_pairs = nullptr;  // recorded after the chunk's pair kernel, on the stream that ran it
         ~Ws() {
             if (done) (void)hipEventDestroy(done);
             if (ev_pairs) (void)hipEventDestroy(ev_pairs);
-            if (ev_main) (void)hipEventDestroy(ev_main);
         }
         // what the chunk's unpack needs (host)
         bool active = false;
         std::vector<DevJob> dj;
         std::vector<int32_t> jmap, tpos;
         std::vector<size_t> full, full_off;
-        size_t o_cnt = 0, o_keys = 0, o_fail = 0;
+        size_t o_cnt = 0, o_keys = 0;  // of the counts and the keys in h_out (the fail word leads it)
         int ktop = 1;
     } ws[kJobSlots];
     // asynchronous calls (pf_recommend_*_async): each holds one workspace slot from its launch

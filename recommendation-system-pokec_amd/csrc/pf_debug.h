@@ -13,17 +13,12 @@
 //   k5_batch_blocks=N     blocks per workgroup of a batched postings scan (default 32; A/B)
 //   k5_wgs=N              workgroups of a one-query postings scan (default: one resident round; on the
 //                         scan lanes 7/8 of one with 3-5 lanes, 1/2 with 6-11, 3/16 with 12-15; A/B)
-//   lazy_aux=1            create the job pipeline's aux streams at the first job call, not at open (A/B)
 //   scan_lanes=N          single-query scans on a caller's stream: 0 or 1 launch on that stream (A/B);
 //                         default 3 (the context's stream, aux, aux2), so consecutive queries' launches
 //                         overlap; 2 leaves out aux2; 4..16 add lanes on streams of their own (for a
 //                         process with more hardware queues, GPU_MAX_HW_QUEUES)
 //   k5_dyn=0              K5: one-query launches in static block rounds, the tail claimed (A/B;
 //                         default: every block claimed per XCD group)
-//   chunk_pingpong=0      the job pipeline's chunks all gather on the aux stream and score on the
-//                         context's stream behind an event (A/B; default: alternate the two)
-//   collab_main=1         the job pipeline's K4' / K8 on the context's stream after the pair kernel
-//                         also in chunks without clubs jobs (A/B)
 //   k5_xcd=0|1            K5: contiguous block ranges per XCD in each static round (default 1; A/B)
 //   k5_tail=N             K5: candidates per claimed block past a one-query launch's static rounds
 //                         (default 0 = whole blocks; A/B)
@@ -32,7 +27,6 @@
 //                         (A/B: bit-exact, slower)
 //   k5s_static=1          K5s (variant build): static slice hand-out instead of claimed slices (A/B)
 //   k5s_batch_slices=N    K5s (variant build): slices per wave of a batched launch (default 16; A/B)
-//   chunk_plan=W1:W2:..   relative chunk sizes of large job-pipeline calls (default 1:1:1; A/B)
 //   load_threads=N        loader threads (default: min(16, hardware threads))
 //   resident_post=0       one-query all-candidates scans build and upload their K5 image per call
 //                         instead of launching from the postings images built at open (A/B)

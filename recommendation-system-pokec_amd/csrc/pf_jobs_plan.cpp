@@ -56,13 +56,6 @@ int32_t ensure_node(pf_ctx* c, int32_t uid) {
     return x;
 }
 
-template <class T>
-hipError_t up(pf_ctx* c, DBuf& b, const std::vector<T>& v) {
-    return upload(c, b, v);
-}
-
-int a16(int64_t x) { return (int)((x + 15) & ~15ll); }
-
 // candidates per pair block = the pair kernel's block (one pair per thread, pf_kernels.h)
 constexpr int64_t kPairSpan = kPairThreads;
 size_t a16z(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -71,6 +64,49 @@ int pow2_lg(int64_t n) {
     int lg = 4;
     while (((int64_t)1 << lg) < n) ++lg;
     return lg;
+}
+
+// K6's image of profile idx (QConst | table | values), for the resident pool built at open and
+// for the per-call builds: its size and table offsets, its ImgJob, its build class and scratch.
+// Meaningful for J.img_lg[idx] != 0 only (0: the tables are outside the device limits).
+const int kImgLge = lg_for(0);  // the exclusion table is empty (the pair images carry no exclusions)
+int64_t img_ntok(const pf_ctx* c, int32_t idx) {
+    return c->hc.tok_off[(size_t)(idx + 1) * c->hc.T] - c->hc.tok_off[(size_t)idx * c->hc.T];
+}
+size_t img_nkeys(const pf_ctx* c, int32_t idx) {  // 8-B entries: the table(s), then the exclusion table
+    return ((size_t)(c->hs.packed ? 1u : 3u) << c->jb.img_lg[idx]) + ((size_t)1 << kImgLge);
+}
+constexpr uint32_t kImgKeysOff = (uint32_t)sizeof(QConst);  // byte offsets from the image's start
+uint32_t img_vals_off(const pf_ctx* c, int32_t idx) { return (uint32_t)a16z(sizeof(QConst) + img_nkeys(c, idx) * 8); }
+size_t img_bytes(const pf_ctx* c, int32_t idx) {
+    return img_vals_off(c, idx) + a16z((size_t)img_ntok(c, idx) * sizeof(QVal));
+}
+int img_dlg(const pf_ctx* c, int32_t idx) { return pow2_lg(2 * (int64_t)c->jb.img_nset[idx] + 2); }
+ImgJob img_job(const pf_ctx* c, int32_t idx, uint32_t pool_off) {  // the image at byte pool_off of its pool
+    ImgJob m{};
+    m.idx = idx;
+    m.lg = c->jb.img_lg[idx];
+    m.lge = kImgLge;
+    m.dlg = img_dlg(c, idx);
+    m.rows = c->jb.img_rows[idx];
+    m.const_off = pool_off;
+    m.keys_off = pool_off + kImgKeysOff;
+    m.vals_off = pool_off + img_vals_off(c, idx);
+    return m;
+}
+// K6 builds in three launches: 0 small LDS builds (<= kImgLdsSmall, many workgroups per CU),
+// 1 large LDS builds (<= kImgLds), 2 hub users in global memory
+int img_build_class(const pf_ctx* c, int32_t idx) {
+    const int lg = c->jb.img_lg[idx];
+    const uint32_t need = lg ? qimage_lds(lg, kImgLge, img_dlg(c, idx), (uint32_t)(c->jb.img_nset[idx] + img_ntok(c, idx)),
+                                          c->hs.packed)
+                             : 0u;
+    return need == 0 ? 2 : (need <= kImgLdsSmall ? 0 : 1);
+}
+// scratch words of a class-2 build: set + u64 items + the table's u64 copy (the SoA transform)
+int64_t img_scratch_words(const pf_ctx* c, int32_t idx) {
+    return ((int64_t)1 << img_dlg(c, idx)) + 2 * ((int64_t)c->jb.img_nset[idx] + img_ntok(c, idx)) +
+           2 * (int64_t)img_nkeys(c, idx);
 }
 
 // Every user's query image (K6's layout: QConst | table | values) built once at open into one
@@ -82,21 +118,11 @@ int pow2_lg(int64_t n) {
 // resident_images=0 keeps the per-call builds.
 int build_resident_images(pf_ctx* c) {
     auto& J = c->jb;
-    const HostCorpus& hc = c->hc;
-    const bool packed = c->hs.packed;
     J.pimg = false;
-    if (debug_long("resident_images", 1) == 0 || hc.n == 0) return PF_OK;
-    const int32_t n = hc.n;
-    const int lge = lg_for(0);
-    const size_t ntab = packed ? 1u : 3u;
-    auto ntok_of = [&](int32_t idx) { return hc.tok_off[(size_t)(idx + 1) * hc.T] - hc.tok_off[(size_t)idx * hc.T]; };
+    const int32_t n = c->hc.n;
+    if (debug_long("resident_images", 1) == 0 || n == 0) return PF_OK;
     std::vector<int64_t> off((size_t)n + 1, 0);
-    par_jobs((size_t)n, [&](size_t i) {
-        const int lg = J.img_lg[i];
-        off[i + 1] = lg ? (int64_t)(a16z(sizeof(QConst) + ((ntab << lg) + ((size_t)1 << lge)) * 8) +
-                                    a16z((size_t)ntok_of((int32_t)i) * sizeof(QVal)))
-                        : 0;
-    }, 1 << 14);
+    par_jobs((size_t)n, [&](size_t i) { off[i + 1] = J.img_lg[i] ? (int64_t)img_bytes(c, (int32_t)i) : 0; }, 1 << 14);
     for (int32_t i = 0; i < n; ++i) off[i + 1] += off[i];
     const size_t total = (size_t)off[n];
     size_t freeb = 0, totb = 0;
@@ -118,20 +144,9 @@ int build_resident_images(pf_ctx* c) {
         std::vector<uint8_t> cls;
         cls.reserve((size_t)(i1 - i0));
         for (int32_t idx = i0; idx < i1; ++idx) {
-            const int lg = J.img_lg[idx];
-            if (!lg) continue;
-            ImgJob m{};
-            m.idx = idx;
-            m.lg = lg;
-            m.lge = lge;
-            m.dlg = pow2_lg(2 * (int64_t)J.img_nset[idx] + 2);
-            m.rows = J.img_rows[idx];
-            m.const_off = (uint32_t)(off[idx] - off[i0]);
-            m.keys_off = (uint32_t)(m.const_off + sizeof(QConst));
-            m.vals_off = (uint32_t)(m.const_off + a16z(sizeof(QConst) + ((ntab << lg) + ((size_t)1 << lge)) * 8));
-            const uint32_t need = qimage_lds(lg, lge, m.dlg, (uint32_t)(J.img_nset[idx] + ntok_of(idx)), packed);
-            cls.push_back(need == 0 ? 2 : (need <= kImgLdsSmall ? 0 : 1));
-            ij.push_back(m);
+            if (!J.img_lg[idx]) continue;
+            cls.push_back((uint8_t)img_build_class(c, idx));
+            ij.push_back(img_job(c, idx, (uint32_t)(off[idx] - off[i0])));
         }
         std::vector<ImgJob> ord;
         ord.reserve(ij.size());
@@ -142,9 +157,7 @@ int build_resident_images(pf_ctx* c) {
                 if (cls[x] == k) {
                     ImgJob m = ij[x];
                     m.scr_off = scr;
-                    if (k == 2)  // set + u64 items + the table's u64 copy (the SoA transform)
-                        scr += ((int64_t)1 << m.dlg) + 2 * ((int64_t)J.img_nset[m.idx] + ntok_of(m.idx)) +
-                               2 * (((int64_t)(c->hs.packed ? 1 : 3) << m.lg) + ((int64_t)1 << m.lge));
+                    if (k == 2) scr += img_scratch_words(c, m.idx);
                     ord.push_back(m);
                     ++nc[k];
                 }
@@ -340,23 +353,23 @@ int jobs_open(pf_ctx* c) {
     std::vector<int32_t> slot_of(hs.slot_of_idx.begin(), hs.slot_of_idx.end());
     sc.lap("image sizes");
     hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = up(c, J.d_tmpl, tv);
-    if (e == hipSuccess) e = up(c, J.d_sigreg, sreg);
-    if (e == hipSuccess) e = up(c, J.d_comp_vals, comp_vals);
-    if (e == hipSuccess) e = up(c, J.d_comp_rows, comp_rows);
-    if (e == hipSuccess) e = up(c, J.d_age_vals, age_vals);
-    if (e == hipSuccess) e = up(c, J.d_age_rows, age_rows);
-    if (e == hipSuccess) e = up(c, J.d_idf_doff, dense_off);
-    if (e == hipSuccess) e = up(c, J.d_idf_dlen, dense_len);
-    if (e == hipSuccess) e = up(c, J.d_idf_dense, dense);
-    if (e == hipSuccess) e = up(c, J.d_slot_of, slot_of);
-    if (e == hipSuccess) e = up(c, J.d_goff, g_off);
-    if (e == hipSuccess) e = up(c, J.d_glen, J.g_len);
-    if (e == hipSuccess) e = up(c, J.d_gnbr, g_nbr);
-    if (e == hipSuccess) e = up(c, J.d_guid, J.g_uid);
-    if (e == hipSuccess) e = up(c, J.d_club_off, hc.club_off);
-    if (e == hipSuccess) e = up(c, J.d_club_dense, club_dense);
-    if (e == hipSuccess) e = up(c, J.d_club_id, club_id);
+    if (e == hipSuccess) e = upload(c, J.d_tmpl, tv);
+    if (e == hipSuccess) e = upload(c, J.d_sigreg, sreg);
+    if (e == hipSuccess) e = upload(c, J.d_comp_vals, comp_vals);
+    if (e == hipSuccess) e = upload(c, J.d_comp_rows, comp_rows);
+    if (e == hipSuccess) e = upload(c, J.d_age_vals, age_vals);
+    if (e == hipSuccess) e = upload(c, J.d_age_rows, age_rows);
+    if (e == hipSuccess) e = upload(c, J.d_idf_doff, dense_off);
+    if (e == hipSuccess) e = upload(c, J.d_idf_dlen, dense_len);
+    if (e == hipSuccess) e = upload(c, J.d_idf_dense, dense);
+    if (e == hipSuccess) e = upload(c, J.d_slot_of, slot_of);
+    if (e == hipSuccess) e = upload(c, J.d_goff, g_off);
+    if (e == hipSuccess) e = upload(c, J.d_glen, J.g_len);
+    if (e == hipSuccess) e = upload(c, J.d_gnbr, g_nbr);
+    if (e == hipSuccess) e = upload(c, J.d_guid, J.g_uid);
+    if (e == hipSuccess) e = upload(c, J.d_club_off, hc.club_off);
+    if (e == hipSuccess) e = upload(c, J.d_club_dense, club_dense);
+    if (e == hipSuccess) e = upload(c, J.d_club_id, club_id);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host vectors die here
     if (e != hipSuccess) return c->hip_fail(e, "job pipeline upload");
     sc.lap("upload");
@@ -660,22 +673,43 @@ void plan_job(pf_ctx* c, const Job& Jb, JP& p, bool raw) {
     }
 }
 
-// Launches jobs[b, e) (planned in P) on the device with workspaces W: every stage and the
-// result copies are queued on the context's stream and W.done is recorded after them;
-// finish_chunk waits for it and fills jobs[i].out (or raw lists in raw_out).
-int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b, size_t e, JobsState::Ws& W) {
-    auto& J = c->jb;
-    W.active = false;
-    const HostCorpus& hc = c->hc;
-    const bool packed = c->hs.packed;
-    HpLap hl;
-    // ---- layout
+// ---------------------------------------------------------------- one chunk: plan, pack, queue
+// The pair blocks as runs (PairGen, expanded on the device by K9 expand_pairs_kernel): a run is
+// ceil(cap / kPairSpan) candidate chunks x nf (image, row) entries of the pool, chunk-major, so
+// the host writes ~one run per job and image class instead of ~140k 16-B blocks per cfg-5 chunk
+// (their layout was ~2.3 ms of host time per chunk, r4m host clocks).  layout_jobs builds the runs
+// per job (images as indices into img_idx), plan_images splits them by the images' class.
+// What one chunk's steps hand on to the next ones (host only):
+struct ChunkPlan {
+    // from layout_jobs
     std::vector<DevJob> dj;
-    std::vector<int32_t> pool32;
+    std::vector<int32_t> pool32, jmap;  // jmap: dj index -> job index
     std::vector<int64_t> pool64;
-    std::vector<int32_t> jmap;  // dj index -> job index
-    int64_t E = 0, HT = 0, SEQ = 0;
-    std::vector<int32_t> img_idx;
+    std::vector<int32_t> img_idx;  // image -> profile idx (plan_images orders them by build class)
+    std::vector<PairGen> rgen;     // the runs per job (`first` unset)
+    std::vector<int2> gpool;       // their (image, row) entries
+    // dj indices by stage: K4', K7, K8 (the first n_topk_main on K4''s stream, then the clubs jobs'),
+    // and the collaborative jobs whose top-k K4' fuses
+    std::vector<int32_t> jix_collab, jix_clubs, jix_topk, jix_fused;
+    int64_t E = 0, HT = 0, SEQ = 0;  // elements, gather hash-table words, gather segment words
+    int ktop = 1, max_cap_collab = 0, n_topk_main = 0;
+    // from plan_images
+    std::vector<ImgJob> ij;        // K6's builds (none when the images are resident)
+    std::vector<QImageRef> refs;
+    size_t ipool = 0;              // bytes of the images K6 builds
+    int64_t scr = 0;               // and their scratch words
+    int n_small = 0, n_lds = 0;    // images [0, n_small) small LDS builds, [n_small, n_lds) large ones
+    std::vector<PairGen> gens;     // the runs by pair class, `first` = the run's first block
+    std::vector<int2> gp2;         // their (image, row) entries
+    uint32_t lds_c[3] = {0u, 0u, 0u};  // per pair class: LDS of a block
+    int nb_c[3] = {0, 0, 0};           // and its blocks
+    int64_t nblk = 0;              // pair blocks of the chunk
+};
+
+// Step 1: jobs[b, e) (planned in P) as DevJobs, their two pools and their pair-block runs.
+int layout_jobs(pf_ctx* c, const std::vector<Job>& jobs, const std::vector<JP>& P, size_t b, size_t e, ChunkPlan& cp) {
+    auto& J = c->jb;
+    const HostCorpus& hc = c->hc;
     if (J.img_stamp.size() != (size_t)hc.n || ++J.img_gen == 0) {  // a stamp per profile idx
         J.img_stamp.assign((size_t)hc.n, 0u);
         J.img_pos.assign((size_t)hc.n, 0);
@@ -684,36 +718,26 @@ int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b
     const uint32_t gen = J.img_gen;
     auto img = [&](int32_t idx) {
         if (J.img_stamp[idx] == gen) return J.img_pos[idx];
-        const int32_t k = (int32_t)img_idx.size();
+        const int32_t k = (int32_t)cp.img_idx.size();
         J.img_stamp[idx] = gen;
         J.img_pos[idx] = k;
-        img_idx.push_back(idx);
+        cp.img_idx.push_back(idx);
         return k;
     };
-    // The pair blocks as runs (PairGen, expanded on the device by K9 expand_pairs_kernel): a run is
-    // ceil(cap / kPairSpan) candidate chunks x nf (image, row) entries of the pool, chunk-major, so
-    // the host writes ~one run per job and image class instead of ~140k 16-B blocks per cfg-5 chunk
-    // (their layout was ~2.3 ms of host time per chunk, r4m host clocks).  Runs are built per job
-    // here (images as img() indices), then split by the images' LDS class below.
-    struct RawGen {
-        int32_t nch, cap, cand, out, stride, fl, nf;
-    };
-    std::vector<RawGen> rgen;
-    std::vector<int2> gpool;  // (image, row) entries of the runs
     auto add_gen = [&](int64_t cap, int64_t cand, int64_t out, int64_t stride, const int2* ents, int nf) {
         if (cap <= 0 || nf <= 0) return;
-        rgen.push_back(RawGen{(int32_t)((cap + kPairSpan - 1) / kPairSpan), (int32_t)cap, (int32_t)cand, (int32_t)out,
-                              (int32_t)stride, (int32_t)gpool.size(), nf});
-        gpool.insert(gpool.end(), ents, ents + nf);
+        cp.rgen.push_back(PairGen{nf, (int32_t)((cap + kPairSpan - 1) / kPairSpan), (int32_t)cap, (int32_t)cand,
+                                  (int32_t)cp.gpool.size(), (int32_t)stride, (int32_t)out, 0});
+        cp.gpool.insert(cp.gpool.end(), ents, ents + nf);
     };
     auto add_blocks = [&](int32_t im, int64_t begin, int64_t count, int64_t out) {
-        const int2 e = make_int2(im, 0);
-        add_gen(count, begin, out, 0, &e, 1);
+        const int2 ent = make_int2(im, 0);
+        add_gen(count, begin, out, 0, &ent, 1);
     };
-    std::vector<int32_t> jix_collab, jix_clubs, jix_topk, jix_fused, jix_ctopk;
-    int max_cap_collab = 0, ktop = 1;
-    const int lge = lg_for(0);
-    auto ntok_of = [&](int32_t idx) { return hc.tok_off[(size_t)(idx + 1) * hc.T] - hc.tok_off[(size_t)idx * hc.T]; };
+    std::vector<int32_t>& pool32 = cp.pool32;
+    std::vector<int64_t>& pool64 = cp.pool64;
+    int64_t& E = cp.E;
+    std::vector<int32_t> jix_ctopk;  // the clubs jobs' K8 runs after K7 on the second aux stream
     {
         size_t ng = 0, words = 0;  // the runs and pool words this chunk appends (one allocation)
         for (size_t i = b; i < e; ++i) {
@@ -722,12 +746,12 @@ int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b
             ng += 2 + p.fd.size();
             words += p.own.size() + p.F.size() + 2 * p.fd.size();
         }
-        rgen.reserve(ng);
-        gpool.reserve(ng + 2 * (e - b));
+        cp.rgen.reserve(ng);
+        cp.gpool.reserve(ng + 2 * (e - b));
         pool32.reserve(words + 1);
     }
     for (size_t i = b; i < e; ++i) {
-        JP& p = P[i];
+        const JP& p = P[i];
         if (p.kind < 0) continue;
         DevJob d{};
         d.kind = p.kind;
@@ -742,10 +766,10 @@ int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b
         pool32.insert(pool32.end(), p.F.begin(), p.F.end());
         d.nf = (int32_t)p.F.size();
         d.ht_lg = p.ht_lg;
-        d.ht_off = HT;
-        HT += p.ht_words;
-        d.seg_off = SEQ;
-        SEQ += (int64_t)p.F.size() + 1;
+        d.ht_off = cp.HT;
+        cp.HT += p.ht_words;
+        d.seg_off = cp.SEQ;
+        cp.SEQ += (int64_t)p.F.size() + 1;
         d.cap = (int32_t)p.cap;
         d.topk = jobs[i].topk;
         d.nfd = (int32_t)p.fd.size();
@@ -753,7 +777,7 @@ int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b
         pool32.insert(pool32.end(), p.fd.begin(), p.fd.end());
         d.fpos_off = (int64_t)pool32.size();
         pool32.insert(pool32.end(), p.fpos.begin(), p.fpos.end());
-        const int32_t jn = (int32_t)dj.size();
+        const int32_t jn = (int32_t)cp.dj.size();
         if (p.kind == kDjClubs) {
             d.sim_off = E;
             E += d.nfd;
@@ -765,10 +789,9 @@ int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b
             d.out_off = E;
             d.cand_off = E;
             E += J.js.n_club_ids;
-            const int32_t iu = img(p.u);
-            add_blocks(iu, d.sim_off, d.nfd, d.sim_off);
+            add_blocks(img(p.u), d.sim_off, d.nfd, d.sim_off);
             for (size_t r = 0; r < p.fd.size(); ++r) add_blocks(img(p.fd[r]), pool64[d.sreg_off + r], p.flen[r], pool64[d.sreg_off + r]);
-            jix_clubs.push_back(jn);
+            cp.jix_clubs.push_back(jn);
         } else {
             d.cand_off = E;
             d.out_off = E;
@@ -778,8 +801,7 @@ int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b
                 E += d.nfd;
                 d.m_off = E;
                 E += (int64_t)d.nfd * p.cap;
-                const int32_t iu = img(p.u);
-                add_blocks(iu, d.sim_off, d.nfd, d.sim_off);
+                add_blocks(img(p.u), d.sim_off, d.nfd, d.sim_off);
                 // candidate-chunk major: the friends' blocks of one candidate chunk are
                 // consecutive, so they run together and share the chunk's records in cache;
                 // a block scores span() candidates against one staged friend image
@@ -787,347 +809,365 @@ int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b
                 std::vector<int2> fe(d.nfd);
                 for (int r = 0; r < d.nfd; ++r) fe[r] = make_int2(img(p.fd[r]), r);
                 add_gen(p.cap, d.cand_off, d.m_off, p.cap, fe.data(), d.nfd);
-                jix_collab.push_back(jn);
-                max_cap_collab = std::max<int>(max_cap_collab, (int)p.cap);
+                cp.jix_collab.push_back(jn);
+                cp.max_cap_collab = std::max<int>(cp.max_cap_collab, (int)p.cap);
             } else if (p.kind == kDjInterest || p.kind == kDjAll) {
                 add_blocks(img(p.u), d.cand_off, p.cap, d.cand_off);
             }
         }
         if (p.kind != kDjRawGraph && p.kind != kDjRawCollab && jobs[i].topk <= kDevTopK) {
-            // a collaborative job with candidates gets its top-k inside K4' (collab_kernel); the
-            // clubs jobs' K8 runs after K7 on the second aux stream (jix_ctopk, appended below)
-            (p.kind == kDjCollab && p.cap > 0 ? jix_fused : (p.kind == kDjClubs ? jix_ctopk : jix_topk)).push_back(jn);
-            ktop = std::max(ktop, jobs[i].topk);
+            // a collaborative job with candidates gets its top-k inside K4' (collab_kernel)
+            (p.kind == kDjCollab && p.cap > 0 ? cp.jix_fused : (p.kind == kDjClubs ? jix_ctopk : cp.jix_topk)).push_back(jn);
+            cp.ktop = std::max(cp.ktop, jobs[i].topk);
         }
-        dj.push_back(d);
-        jmap.push_back((int32_t)i);
+        cp.dj.push_back(d);
+        cp.jmap.push_back((int32_t)i);
     }
-    if (dj.empty()) return PF_OK;
-    const int n_topk_main = (int)jix_topk.size();  // K8 on the context's stream; the clubs jobs' after them
-    jix_topk.insert(jix_topk.end(), jix_ctopk.begin(), jix_ctopk.end());
-    if (W.done == nullptr) {
-        HIPCHK(c, hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&W.ev_pairs, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&W.ev_main, hipEventDisableTiming));
-    }
-    const hipStream_t s = c->stream;
+    cp.n_topk_main = (int)cp.jix_topk.size();
+    cp.jix_topk.insert(cp.jix_topk.end(), jix_ctopk.begin(), jix_ctopk.end());
     if (E >= INT32_MAX) return c->fail(PF_EUNSUPP, "job batch too large for one pair launch");
-    // ---- images (pf_api.cpp plan_images layout).  Resident (J.pimg, built at open): every
-    // user's image already sits in J.d_pimg and the batch only references them.  Otherwise K6
-    // builds the batch's images, the ones it builds in LDS first.
-    const bool resident = J.pimg;
-    const uint32_t ntab = packed ? 1u : 3u;
-    auto dlg_of = [&](int32_t idx) { return pow2_lg(2 * (int64_t)J.img_nset[idx] + 2); };
-    // K6 builds the images in three launches: small LDS builds (<= kImgLdsSmall, many workgroups
-    // per CU), large LDS builds (<= kImgLds), hub users in global memory
-    int n_lds = 0, n_small = 0;
+    return PF_OK;
+}
+
+// Step 2: the chunk's images and its pair launches.  Resident images (J.pimg, built at open): every
+// user's image already sits in J.d_pimg and the chunk only references them.  Otherwise K6 builds
+// the chunk's images, ordered by build class (img_build_class).
+int plan_images(pf_ctx* c, ChunkPlan& cp) {
+    auto& J = c->jb;
+    const bool resident = J.pimg, packed = c->hs.packed;
+    const size_t n = cp.img_idx.size();
     if (!resident) {
-        std::vector<int32_t> order(img_idx.size()), pos(img_idx.size());
-        std::vector<uint8_t> cls(img_idx.size());  // 0 small, 1 large, 2 global
-        for (size_t k = 0; k < img_idx.size(); ++k) {
-            const int32_t idx = img_idx[k];
-            const uint32_t need = J.img_lg[idx] ? qimage_lds(J.img_lg[idx], lge, dlg_of(idx),
-                                                             (uint32_t)(J.img_nset[idx] + ntok_of(idx)), packed)
-                                                : 0u;
-            cls[k] = need == 0 ? 2 : (need <= kImgLdsSmall ? 0 : 1);
-            n_lds += cls[k] < 2;
-            n_small += cls[k] == 0;
-        }
-        int a = 0, b2 = n_small, g2 = n_lds;
-        for (size_t k = 0; k < img_idx.size(); ++k) pos[k] = cls[k] == 0 ? a++ : (cls[k] == 1 ? b2++ : g2++);
-        for (size_t k = 0; k < img_idx.size(); ++k) order[pos[k]] = img_idx[k];
-        img_idx.swap(order);
-        for (int2& ge : gpool) ge.x = pos[ge.x];
+        std::vector<int32_t> order(n), pos(n);
+        std::vector<uint8_t> cls(n);
+        int nc[3] = {0, 0, 0};
+        for (size_t k = 0; k < n; ++k) ++nc[cls[k] = (uint8_t)img_build_class(c, cp.img_idx[k])];
+        cp.n_small = nc[0];
+        cp.n_lds = nc[0] + nc[1];
+        int at[3] = {0, cp.n_small, cp.n_lds};
+        for (size_t k = 0; k < n; ++k) pos[k] = at[cls[k]]++;
+        for (size_t k = 0; k < n; ++k) order[pos[k]] = cp.img_idx[k];
+        cp.img_idx.swap(order);
+        for (int2& ge : cp.gpool) ge.x = pos[ge.x];
     }
-    std::vector<ImgJob> ij(resident ? 0 : img_idx.size());
-    std::vector<QImageRef> refs(img_idx.size());
-    size_t ipool = 0;
-    int64_t scr = 0;
-    for (size_t k = 0; k < img_idx.size(); ++k) {
-        const int32_t idx = img_idx[k];
-        const int lg = J.img_lg[idx];
-        if (lg == 0) return c->fail(PF_EUNSUPP, "query hash table too large");
-        const int64_t ntok = ntok_of(idx);
-        const size_t nkeys = ((size_t)ntab << lg) + ((size_t)1 << lge);
-        QImageRef& r = refs[k];
-        r.keys_off = (uint32_t)sizeof(QConst);
-        r.vals_off = (uint32_t)a16z(sizeof(QConst) + nkeys * 8);
+    cp.ij.resize(resident ? 0 : n);
+    cp.refs.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+        const int32_t idx = cp.img_idx[k];
+        if (J.img_lg[idx] == 0) return c->fail(PF_EUNSUPP, "query hash table too large");
+        QImageRef& r = cp.refs[k];
+        r.keys_off = kImgKeysOff;
+        r.vals_off = img_vals_off(c, idx);
         if (resident) {
             r.const_off = (uint32_t)(J.pimg_off[idx] >> 4);
         } else {
-            ImgJob& m = ij[k];
-            m.idx = idx;
-            m.lg = lg;
-            m.lge = lge;
-            m.dlg = dlg_of(idx);
-            m.rows = J.img_rows[idx];
-            m.const_off = (uint32_t)ipool;
-            m.keys_off = (uint32_t)(ipool + r.keys_off);
-            m.vals_off = (uint32_t)(ipool + r.vals_off);
-            r.const_off = (uint32_t)(ipool >> 4);
-            ipool = a16z(m.vals_off + (size_t)ntok * sizeof(QVal));
-            if (ipool >= (size_t)UINT32_MAX) return c->fail(PF_EUNSUPP, "query images of one batch exceed 4 GB");
-            m.scr_off = scr;
-            if ((int)k >= n_lds)  // set + u64 items + the table's u64 copy (the SoA transform)
-                scr += ((int64_t)1 << m.dlg) + 2 * ((int64_t)J.img_nset[idx] + ntok) + 2 * (int64_t)nkeys;
+            ImgJob& m = cp.ij[k];
+            m = img_job(c, idx, (uint32_t)cp.ipool);
+            r.const_off = (uint32_t)(cp.ipool >> 4);
+            cp.ipool += img_bytes(c, idx);
+            if (cp.ipool >= (size_t)UINT32_MAX) return c->fail(PF_EUNSUPP, "query images of one batch exceed 4 GB");
+            m.scr_off = cp.scr;
+            if ((int)k >= cp.n_lds) cp.scr += img_scratch_words(c, idx);
         }
-        const size_t kv = nkeys * 8 + (size_t)ntok * sizeof(QVal);
+        const size_t kv = img_nkeys(c, idx) * 8 + (size_t)img_ntok(c, idx) * sizeof(QVal);
         r.lds_bytes = kv <= kStageLimitJobs ? (uint32_t)kv : 0u;
     }
     // The pair blocks in three launches by their image: LDS-staged images whose block fits two
     // workgroups per CU, larger LDS-staged ones, global-memory tables.  One launch sized for the
     // batch's largest image ran every block of 6 % of the cfg-3 steps at one workgroup per CU
     // (484 vs 338 us, r3ad), and one global-table image switched every block to global probes.
-    uint32_t lds_c[3] = {0u, 0u, 0u};
-    int nb_c[3] = {0, 0, 0};
-    std::vector<PairGen> gens;  // by class, `first` = the run's first block
-    std::vector<int2> gp2;      // their (image, row) entries
-    int64_t nblk = 0;           // pair blocks of the chunk
     {
         constexpr uint32_t kTwoPerCu = 80u * 1024u;  // 160 KB of LDS per CU
-        std::vector<uint8_t> icls(refs.size());
-        for (size_t k = 0; k < refs.size(); ++k) {
-            const uint32_t need = (uint32_t)sizeof(QConst) + refs[k].lds_bytes +
+        std::vector<uint8_t> icls(n);
+        for (size_t k = 0; k < n; ++k) {
+            const uint32_t need = (uint32_t)sizeof(QConst) + cp.refs[k].lds_bytes +
                                   kHitSlots * (packed ? 4u : 8u) * kPairThreads + 4u * kPairThreads + 2048u;
-            icls[k] = refs[k].lds_bytes == 0 ? 2 : (need <= kTwoPerCu ? 0 : 1);
-            lds_c[icls[k]] = std::max(lds_c[icls[k]], need);
+            icls[k] = cp.refs[k].lds_bytes == 0 ? 2 : (need <= kTwoPerCu ? 0 : 1);
+            cp.lds_c[icls[k]] = std::max(cp.lds_c[icls[k]], need);
         }
         // each run split by class (its entries of one class keep their order); the classes'
         // blocks are consecutive, class 0 first
-        gens.reserve(rgen.size() + 8);
-        gp2.reserve(gpool.size());
+        cp.gens.reserve(cp.rgen.size() + 8);
+        cp.gp2.reserve(cp.gpool.size());
         for (int k = 0; k < 3; ++k) {
             int64_t cnt = 0;
-            for (const RawGen& g : rgen) {
-                const int32_t fl = (int32_t)gp2.size();
+            for (const PairGen& g : cp.rgen) {
+                const int32_t fl = (int32_t)cp.gp2.size();
                 for (int f = 0; f < g.nf; ++f)
-                    if (icls[gpool[g.fl + f].x] == k) gp2.push_back(gpool[g.fl + f]);
-                const int32_t nf = (int32_t)gp2.size() - fl;
+                    if (icls[cp.gpool[g.fl + f].x] == k) cp.gp2.push_back(cp.gpool[g.fl + f]);
+                const int32_t nf = (int32_t)cp.gp2.size() - fl;
                 if (nf == 0) continue;
-                gens.push_back(PairGen{nf, g.nch, g.cap, g.cand, fl, g.stride, g.out, (int32_t)(nblk + cnt)});
+                cp.gens.push_back(PairGen{nf, g.nch, g.cap, g.cand, fl, g.stride, g.out, (int32_t)(cp.nblk + cnt)});
                 cnt += (int64_t)g.nch * nf;
             }
-            if (nblk + cnt >= INT32_MAX) return c->fail(PF_EUNSUPP, "job batch too large for one pair launch");
-            nb_c[k] = (int)cnt;
-            nblk += cnt;
+            if (cp.nblk + cnt >= INT32_MAX) return c->fail(PF_EUNSUPP, "job batch too large for one pair launch");
+            cp.nb_c[k] = (int)cnt;
+            cp.nblk += cnt;
         }
     }
-    hl.lap(kHpImages);
-    // ---- staging: [DevJob | pool32 | pool64 | ImgJob | QImageRef | PairBlock | jix x3], then the
-    // chunk's result region [fail word (16 B, uploaded as zero) | ncand | top-k keys], so one
-    // upload and one download carry everything (no memset, one result copy)
-    if (pool32.empty()) pool32.push_back(0);
-    if (pool64.empty()) pool64.push_back(0);
-    const size_t o_dj = 0;
-    const size_t o_p32 = a16z(o_dj + dj.size() * sizeof(DevJob));
-    const size_t o_p64 = a16z(o_p32 + pool32.size() * 4);
-    const size_t o_ij = a16z(o_p64 + pool64.size() * 8);
-    const size_t o_refs = a16z(o_ij + ij.size() * sizeof(ImgJob));
-    const size_t o_blk = a16z(o_refs + refs.size() * sizeof(QImageRef));
-    const size_t o_gp = a16z(o_blk + std::max<size_t>(gens.size(), 1) * sizeof(PairGen));
-    const size_t o_jc = a16z(o_gp + std::max<size_t>(gp2.size(), 1) * sizeof(int2));
-    const size_t o_jk = a16z(o_jc + jix_collab.size() * 4);
-    const size_t o_jt = a16z(o_jk + jix_clubs.size() * 4);
-    const size_t o_tk = a16z(o_jt + jix_topk.size() * 4);  // K4' top-k tickets (zero), one per collaborative job
-    const size_t o_res = a16z(o_tk + jix_collab.size() * 4);
-    const size_t o_rcnt = o_res + 16, o_rkeys = o_rcnt + a16z(dj.size() * 4);
-    const size_t res_b = o_rkeys - o_res + dj.size() * (size_t)ktop * 8;
-    const size_t total = o_res + 16;  // uploaded: the plan and the zero fail word
-    HIPCHK(c, W.h_plan.ensure(total));
-    uint8_t* h = W.h_plan.as<uint8_t>();
-    auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) std::memcpy(h + o, src, bytes); };
-    put(o_dj, dj.data(), dj.size() * sizeof(DevJob));
-    put(o_p32, pool32.data(), pool32.size() * 4);
-    put(o_p64, pool64.data(), pool64.size() * 8);
-    put(o_ij, ij.data(), ij.size() * sizeof(ImgJob));
-    put(o_refs, refs.data(), refs.size() * sizeof(QImageRef));
-    put(o_blk, gens.data(), gens.size() * sizeof(PairGen));
-    put(o_gp, gp2.data(), gp2.size() * sizeof(int2));
-    put(o_jc, jix_collab.data(), jix_collab.size() * 4);
-    put(o_jk, jix_clubs.data(), jix_clubs.size() * 4);
-    put(o_jt, jix_topk.data(), jix_topk.size() * 4);
-    if (!jix_collab.empty()) std::memset(h + o_tk, 0, jix_collab.size() * 4);
-    std::memset(h + o_res, 0, 16);
-    const size_t o_ord = a16z(o_res + res_b);  // the pair blocks' dispatch order (device-written)
-    const size_t o_bd = a16z(o_ord + std::max<size_t>((size_t)nblk, 1) * 4);  // the pair blocks (device-written, K9)
-    HIPCHK(c, W.d_plan.reserve(o_bd + std::max<size_t>((size_t)nblk, 1) * sizeof(PairBlock)));
-    if (J.aux == nullptr) {
-        HIPCHK(c, hipStreamCreateWithFlags(&J.aux, hipStreamNonBlocking));
-        HIPCHK(c, hipStreamCreateWithFlags(&J.aux2, hipStreamNonBlocking));
-        HIPCHK(c, hipEventCreateWithFlags(&J.ev_fork, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&J.ev_join, hipEventDisableTiming));
+    return PF_OK;
+}
+
+// The plan buffer: 16-byte-aligned sections, each at one offset of the slot's pinned host buffer
+// (h; nullptr: a sizing pass) and of its device buffer.
+template <class T>
+struct Sec {
+    size_t off = 0;
+    T* at(void* base) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + off); }
+};
+struct PlanArena {
+    uint8_t* h;
+    size_t end = 0;
+    template <class T>
+    Sec<T> space(size_t count) {  // not initialised: the device writes it
+        const Sec<T> s{end};
+        end = a16z(end + count * sizeof(T));
+        return s;
     }
-    // the plan goes up on the aux stream, where this chunk's gathers follow it at once: they run
-    // beside the previous chunk's pair kernel (their slot's buffers were released when that slot's
-    // previous chunk was unpacked); r3ab: cfg 3 +3 % over forking them from the context's stream
-    // Ping-pong (default): consecutive chunks alternate between the aux stream and the context's
-    // stream for their upload, gathers, images and pair kernel, so a chunk's pair kernel follows
-    // its own gathers in stream order (no cross-stream wait in front of it: ~20 us per chunk in the
-    // r7l trace) and may start beside the previous chunk's pair kernel.  A chunk's workspace slot is
-    // reused only after its W.done (the caller waits it), so the two streams never share a slot's
-    // buffers in flight.  (PF_DEBUG chunk_pingpong=0: the gathers on the aux stream, the images
-    // and the pair kernel on the context's stream behind an event, as before)
-    static const bool pingpong = debug_long("chunk_pingpong", 1) != 0;
-    if (pingpong) J.pp ^= 1;
-    const hipStream_t up = (!pingpong || J.pp) ? J.aux : s;  // upload, K9, K3, dispatch orders
-    const hipStream_t sp = pingpong ? up : s;                // images, pair kernel, K4' / K8 with clubs
-    HIPCHK(c, hipMemcpyAsync(W.d_plan.p, h, total, hipMemcpyHostToDevice, up));
-    if (!pingpong) HIPCHK(c, hipEventRecord(J.ev_fork, up));
-    uint8_t* d = W.d_plan.as<uint8_t>();
-    const DevJob* d_dj = reinterpret_cast<const DevJob*>(d + o_dj);
-    const int32_t* d_p32 = reinterpret_cast<const int32_t*>(d + o_p32);
-    const int64_t* d_p64 = reinterpret_cast<const int64_t*>(d + o_p64);
-    const ImgJob* d_ij = reinterpret_cast<const ImgJob*>(d + o_ij);
-    const QImageRef* d_refs = reinterpret_cast<const QImageRef*>(d + o_refs);
-    const PairGen* d_gen = reinterpret_cast<const PairGen*>(d + o_blk);
-    const int2* d_gpool = reinterpret_cast<const int2*>(d + o_gp);
-    PairBlock* d_blk = reinterpret_cast<PairBlock*>(d + o_bd);
-    const int32_t* d_jc = reinterpret_cast<const int32_t*>(d + o_jc);
-    const int32_t* d_jk = reinterpret_cast<const int32_t*>(d + o_jk);
-    const int32_t* d_jt = reinterpret_cast<const int32_t*>(d + o_jt);
-    unsigned int* d_tk = reinterpret_cast<unsigned int*>(d + o_tk);
-    int32_t* d_fail = reinterpret_cast<int32_t*>(d + o_res);
-    int32_t* d_ord = reinterpret_cast<int32_t*>(d + o_ord);
-    int32_t* d_ncand = reinterpret_cast<int32_t*>(d + o_rcnt);
-    uint64_t* d_keys = reinterpret_cast<uint64_t*>(d + o_rkeys);
-    hl.lap(kHpPack);
-    // ---- workspaces
-    const size_t nE = (size_t)std::max<int64_t>(E, 1);
+    template <class T>
+    Sec<T> put(const std::vector<T>& v, size_t min_count = 0) {  // v's bytes, room for min_count at least
+        if (h && !v.empty()) std::memcpy(h + end, v.data(), v.size() * sizeof(T));
+        return space<T>(std::max(v.size(), min_count));
+    }
+    template <class T>
+    Sec<T> zeros(size_t count) {
+        if (h && count) std::memset(h + end, 0, count * sizeof(T));
+        return space<T>(count);
+    }
+};
+
+// [DevJob | pool32 | pool64 | ImgJob | QImageRef | PairGen | entries | jix x3 | K4' tickets], then
+// the chunk's result region [fail word (16 B, uploaded as zero) | ncand | top-k keys], so one upload
+// and one download carry everything (no memset, one result copy); then what only the device
+// touches: the pair blocks' dispatch order and the pair blocks (K9).
+struct PlanLayout {
+    Sec<DevJob> dj;
+    Sec<int32_t> p32, jc, jk, jt, fail, ncand, ord;
+    Sec<int64_t> p64;
+    Sec<ImgJob> ij;
+    Sec<QImageRef> refs;
+    Sec<PairGen> gen;
+    Sec<int2> gpool;
+    Sec<unsigned int> tk;  // K4' top-k tickets (zero), one per collaborative job
+    Sec<uint64_t> keys;
+    Sec<PairBlock> blk;
+    size_t res_bytes = 0;  // [fail | ncand | keys]
+};
+
+// Step 3: the plan packed into W.h_plan and sent to W.d_plan on stream `up`.
+int pack_plan(pf_ctx* c, ChunkPlan& cp, JobsState::Ws& W, hipStream_t up, PlanLayout& L) {
+    if (cp.pool32.empty()) cp.pool32.push_back(0);
+    if (cp.pool64.empty()) cp.pool64.push_back(0);
+    const size_t nj = cp.dj.size(), nblk = std::max<size_t>((size_t)cp.nblk, 1);
+    size_t uploaded = 0;  // the plan and the zero fail word
+    auto lay = [&](uint8_t* h) {
+        PlanArena a{h};
+        L.dj = a.put(cp.dj);
+        L.p32 = a.put(cp.pool32);
+        L.p64 = a.put(cp.pool64);
+        L.ij = a.put(cp.ij);
+        L.refs = a.put(cp.refs);
+        L.gen = a.put(cp.gens, 1);
+        L.gpool = a.put(cp.gp2, 1);
+        L.jc = a.put(cp.jix_collab);
+        L.jk = a.put(cp.jix_clubs);
+        L.jt = a.put(cp.jix_topk);
+        L.tk = a.zeros<unsigned int>(cp.jix_collab.size());
+        L.fail = a.zeros<int32_t>(4);
+        uploaded = a.end;
+        L.ncand = a.space<int32_t>(nj);
+        L.keys = a.space<uint64_t>(nj * (size_t)cp.ktop);
+        L.res_bytes = L.keys.off - L.fail.off + nj * (size_t)cp.ktop * 8;
+        L.ord = a.space<int32_t>(nblk);
+        L.blk = a.space<PairBlock>(nblk);
+        return a.end;
+    };
+    lay(nullptr);
+    HIPCHK(c, W.h_plan.ensure(uploaded));
+    HIPCHK(c, W.d_plan.reserve(lay(W.h_plan.as<uint8_t>())));
+    HIPCHK(c, hipMemcpyAsync(W.d_plan.p, W.h_plan.p, uploaded, hipMemcpyHostToDevice, up));
+    return PF_OK;
+}
+
+// A chunk's streams by role.  Consecutive chunks alternate (J.pp) between the aux stream and the
+// context's stream for their upload, gathers, images and pair kernel, so a chunk's pair kernel
+// follows its own gathers in stream order (no cross-stream wait in front of it: ~20 us per chunk
+// in the r7l trace) and may start beside the previous chunk's pair kernel.  A chunk's workspace
+// slot is reused only after its W.done (the caller waits it), so the two streams never share a
+// slot's buffers in flight.
+// K7 (clubs) and its jobs' K8 go to the second aux stream once the pairs are scored (K7 ran
+// 0.8-1.4 ms per cfg-5 chunk between two pair kernels with the device mostly idle, r4k), and so
+// do K4' (collaborative, fused top-k) and the interest jobs' K8 when the chunk has no clubs jobs:
+// the ping-pong stream then goes straight on to its next chunk's pair kernel (cfg-3 trace r7e:
+// K4' + K8 took ~40 us of every ~400-us step between two pair kernels; cfg3 +9 %, r7g).  With
+// clubs jobs K4' stays on the pair kernel's stream beside K7 (behind K7 on one stream, cfg 5 ran
+// 148k-162k vs 166k-171k users/s, r7h).
+struct ChunkStreams {
+    hipStream_t up;    // upload, K9, K3, dispatch orders
+    hipStream_t sp;    // images, pair kernel (the same stream: they follow the gathers in order)
+    hipStream_t sc;    // K4', the interest jobs' K8
+    hipStream_t aux2;  // K7, the clubs jobs' K8, the result copies, W.done
+};
+
+// Step 4: the workspaces, then every device stage in stream order.
+int enqueue_chunk(pf_ctx* c, const ChunkPlan& cp, const PlanLayout& L, JobsState::Ws& W, const ChunkStreams& st,
+                  HpLap& hl) {
+    auto& J = c->jb;
+    const bool resident = J.pimg;
+    const size_t nE = (size_t)std::max<int64_t>(cp.E, 1);
     HIPCHK(c, W.d_slots.reserve(nE * 4));
     HIPCHK(c, W.d_ids.reserve(nE * 4));
     HIPCHK(c, W.d_fl.reserve(nE * 4));
-    HIPCHK(c, W.d_ht.reserve((size_t)std::max<int64_t>(HT, 1) * 4));
-    HIPCHK(c, W.d_seq.reserve((size_t)std::max<int64_t>(SEQ, 1) * 4));
+    HIPCHK(c, W.d_ht.reserve((size_t)std::max<int64_t>(cp.HT, 1) * 4));
+    HIPCHK(c, W.d_seq.reserve((size_t)std::max<int64_t>(cp.SEQ, 1) * 4));
     if (!resident) {
-        HIPCHK(c, W.d_img.reserve(std::max<size_t>(ipool, 16)));
-        HIPCHK(c, W.d_scr.reserve((size_t)std::max<int64_t>(scr, 1) * 4));
+        HIPCHK(c, W.d_img.reserve(std::max<size_t>(cp.ipool, 16)));
+        HIPCHK(c, W.d_scr.reserve((size_t)std::max<int64_t>(cp.scr, 1) * 4));
     }
-    const uint8_t* ipl = resident ? J.d_pimg.as<uint8_t>() : W.d_img.as<uint8_t>();  // the batch's image pool
-    const int collab_gx = (max_cap_collab + 63) / 64;  // K4' blocks per job (pf_jobs.hip kCollabCands)
-    if (!jix_collab.empty())
-        HIPCHK(c, W.d_parts.reserve(jix_collab.size() * (size_t)std::max(collab_gx, 1) * (size_t)ktop * 8));
+    const uint8_t* ipl = resident ? J.d_pimg.as<uint8_t>() : W.d_img.as<uint8_t>();  // the chunk's image pool
+    const int collab_gx = (cp.max_cap_collab + 63) / 64;  // K4' blocks per job (pf_jobs.hip kCollabCands)
+    if (!cp.jix_collab.empty())
+        HIPCHK(c, W.d_parts.reserve(cp.jix_collab.size() * (size_t)std::max(collab_gx, 1) * (size_t)cp.ktop * 8));
     hl.lap(kHpPlan);  // workspaces
-    if (!jix_clubs.empty()) {
-        const int64_t want = (int64_t)jix_clubs.size();
+    if (!cp.jix_clubs.empty()) {
+        const int64_t want = (int64_t)cp.jix_clubs.size();
         if (want > W.acc_jobs) {
             const size_t words = (size_t)want * (size_t)std::max(J.js.n_club_ids, 1);
             HIPCHK(c, W.d_acc.ensure(words * 8));
-            HIPCHK(c, hipMemsetAsync(W.d_acc.p, 0, W.d_acc.cap, sp));
+            HIPCHK(c, hipMemsetAsync(W.d_acc.p, 0, W.d_acc.cap, st.sp));
             W.acc_jobs = want;
         }
     }
-    // ---- the stages, in stream order; the gathers and dispatch orders run on the aux stream and
-    // join before the pair kernel, beside the images
-    if (!pingpong) HIPCHK(c, hipStreamWaitEvent(s, J.ev_fork, 0));  // the plan (images, fail word) is up
-    HIPCHK(c, launch_expand_pairs(d_gen, (int)gens.size(), d_gpool, (int)nblk, d_blk, up));  // K9: the blocks
-    HIPCHK(c, launch_gather(J.js, J.view, d_dj, (int)dj.size(), d_p32, d_p64, W.d_ht.as<int32_t>(),
-                            W.d_seq.as<int32_t>(), W.d_slots.as<int32_t>(), W.d_ids.as<int32_t>(),
-                            d_ncand, up));
-    for (int k = 0, o = 0; k < 3; o += nb_c[k++])  // each launch's dispatch order (relative to its blocks)
-        HIPCHK(c, launch_order_pairs(d_blk + o, nb_c[k], W.d_slots.as<int32_t>(), hc.n, d_ord + o, up));
-    if (!pingpong) HIPCHK(c, hipEventRecord(J.ev_join, up));
+    void* d = W.d_plan.p;
+    const DevJob* d_dj = L.dj.at(d);
+    const int32_t* d_p32 = L.p32.at(d);
+    int32_t* slots = W.d_slots.as<int32_t>();
+    int32_t* ids = W.d_ids.as<int32_t>();
+    float* fl = W.d_fl.as<float>();
+    PairBlock* d_blk = L.blk.at(d);
+    int32_t* d_ord = L.ord.at(d);
+    int32_t* d_ncand = L.ncand.at(d);
+    uint64_t* d_keys = L.keys.at(d);
+    HIPCHK(c, launch_expand_pairs(L.gen.at(d), (int)cp.gens.size(), L.gpool.at(d), (int)cp.nblk, d_blk, st.up));  // K9
+    HIPCHK(c, launch_gather(J.js, J.view, d_dj, (int)cp.dj.size(), d_p32, L.p64.at(d), W.d_ht.as<int32_t>(),
+                            W.d_seq.as<int32_t>(), slots, ids, d_ncand, st.up));
+    for (int k = 0, o = 0; k < 3; o += cp.nb_c[k++])  // each launch's dispatch order (relative to its blocks)
+        HIPCHK(c, launch_order_pairs(d_blk + o, cp.nb_c[k], slots, c->hc.n, d_ord + o, st.up));
     if (!resident)
-        HIPCHK(c, launch_qimages(c->ds, J.js, d_ij, n_small, n_lds - n_small, (int)ij.size() - n_lds,
-                                 W.d_img.as<uint8_t>(), W.d_scr.as<uint32_t>(), d_fail, sp));
-    if (!pingpong) HIPCHK(c, hipStreamWaitEvent(s, J.ev_join, 0));
-    const bool any_pairs = nblk > 0;
+        HIPCHK(c, launch_qimages(c->ds, J.js, L.ij.at(d), cp.n_small, cp.n_lds - cp.n_small, (int)cp.ij.size() - cp.n_lds,
+                                 W.d_img.as<uint8_t>(), W.d_scr.as<uint32_t>(), L.fail.at(d), st.sp));
+    const bool any_pairs = cp.nblk > 0;
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
     if ((J.stats_on || J.stats_count) && any_pairs) {
         if (J.stat_used == J.stat_ev.size()) {
-            hipEvent_t a, b2;
-            HIPCHK(c, timing_event(&a));
-            HIPCHK(c, timing_event(&b2));
-            J.stat_ev.emplace_back(a, b2);
+            hipEvent_t e0, e1;
+            HIPCHK(c, timing_event(&e0));
+            HIPCHK(c, timing_event(&e1));
+            J.stat_ev.emplace_back(e0, e1);
         }
         pe0 = J.stat_ev[J.stat_used].first;
         pe1 = J.stat_ev[J.stat_used].second;
         ++J.stat_used;
-        HIPCHK(c, hipEventRecord(pe0, sp));
+        HIPCHK(c, hipEventRecord(pe0, st.sp));
     }
-    for (int k = 0, o = 0; k < 3; o += nb_c[k++]) {  // the pair-scoring stage (timed)
-        HIPCHK(c, launch_pairs(c->ds, ipl, d_refs, lds_c[k], k == 2, d_blk + o, nb_c[k], d_ord + o,
-                               W.d_slots.as<int32_t>(), W.d_fl.as<float>(), sp));
-        J.n_dispatch += nb_c[k] > 0;
+    for (int k = 0, o = 0; k < 3; o += cp.nb_c[k++]) {  // the pair-scoring stage (timed)
+        HIPCHK(c, launch_pairs(c->ds, ipl, L.refs.at(d), cp.lds_c[k], k == 2, d_blk + o, cp.nb_c[k], d_ord + o, slots, fl,
+                               st.sp));
+        J.n_dispatch += cp.nb_c[k] > 0;
     }
     if (pe1) {
-        HIPCHK(c, hipEventRecord(pe1, sp));
+        HIPCHK(c, hipEventRecord(pe1, st.sp));
         ++J.st_launches;
     }
     if (J.stats_count && any_pairs) {
         unsigned long long* acc = J.d_stats.as<unsigned long long>();
-        HIPCHK(c, launch_pair_stats(c->ds, d_blk, (int)nblk, W.d_slots.as<int32_t>(), acc, sp));
-        for (const PairGen& g : gens)  // the staged image per pair block (QConst + tables)
-            for (int f = 0; f < g.nf; ++f) {
-                const int32_t k = gp2[g.fl + f].x;
-                J.st_img_bytes += (int64_t)g.nch * ((int64_t)refs[k].vals_off + ntok_of(img_idx[k]) * (int64_t)sizeof(QVal));
-            }
+        HIPCHK(c, launch_pair_stats(c->ds, d_blk, (int)cp.nblk, slots, acc, st.sp));
+        for (const PairGen& g : cp.gens)  // the staged image per pair block (QConst + tables)
+            for (int f = 0; f < g.nf; ++f)
+                J.st_img_bytes += (int64_t)g.nch * (int64_t)img_bytes(c, cp.img_idx[cp.gp2[g.fl + f].x]);
     }
     hl.lap(kHpCollab);  // images, gathers, pairs launched
-    // K7 (clubs) and its jobs' K8 go to the second aux stream once the pairs are scored (K7 ran
-    // 0.8-1.4 ms per cfg-5 chunk between two pair kernels with the device mostly idle, r4k), and so
-    // do K4' (collaborative, fused top-k) and the interest jobs' K8 when the chunk has no clubs jobs:
-    // the context's stream then goes straight on to the next chunk's pair kernel (cfg-3 trace r7e:
-    // K4' + K8 took ~40 us of every ~400-us step between two pair kernels; cfg3 +9 %, r7g).  With
-    // clubs jobs K4' stays on the context's stream beside K7 (behind K7 on one stream, cfg 5 ran
-    // 148k-162k vs 166k-171k users/s, r7h).  The chunk's result copies follow on the aux stream and
-    // W.done is recorded last there.  Jobs write disjoint regions of the slot's buffers.
-    // (PF_DEBUG collab_main=1: K4' and K8 on the context's stream always, the A/B)
-    const hipStream_t s2 = J.aux2;
-    static const bool collab_main = debug_long("collab_main", 0) != 0;
-    const hipStream_t sc = (collab_main || !jix_clubs.empty()) ? sp : s2;
-    HIPCHK(c, hipEventRecord(W.ev_pairs, sp));
-    HIPCHK(c, hipStreamWaitEvent(s2, W.ev_pairs, 0));
-    HIPCHK(c, launch_collab(d_dj, d_jc, (int)jix_collab.size(), max_cap_collab, d_p32, W.d_fl.as<float>(),
-                            W.d_slots.as<int32_t>(), W.d_fl.as<float>(), W.d_ids.as<int32_t>(), W.d_parts.as<uint64_t>(),
-                            d_tk, d_keys, ktop, sc));
-    HIPCHK(c, launch_job_topk(d_dj, d_jt, n_topk_main, W.d_fl.as<float>(), W.d_ids.as<int32_t>(),
-                              W.d_slots.as<int32_t>(), d_ncand, d_keys, ktop, sc));
-    if (collab_main) HIPCHK(c, hipEventRecord(W.ev_main, sp));
-    HIPCHK(c, launch_clubs(J.js, J.view, d_dj, d_jk, (int)jix_clubs.size(), d_p32, d_p64, W.d_fl.as<float>(),
-                           W.d_acc.as<double>(), W.d_fl.as<float>(), W.d_ids.as<int32_t>(),
-                           d_ncand, (int64_t)J.js.n_club_ids, s2));
-    HIPCHK(c, launch_job_topk(d_dj, d_jt + n_topk_main, (int)jix_topk.size() - n_topk_main, W.d_fl.as<float>(),
-                              W.d_ids.as<int32_t>(), W.d_slots.as<int32_t>(), d_ncand, d_keys, ktop, s2));
-    if (collab_main) HIPCHK(c, hipStreamWaitEvent(s2, W.ev_main, 0));
-    // ---- results: keys (top-k jobs), counts, the fail flag; full lists for the others
+    HIPCHK(c, hipEventRecord(W.ev_pairs, st.sp));
+    HIPCHK(c, hipStreamWaitEvent(st.aux2, W.ev_pairs, 0));
+    HIPCHK(c, launch_collab(d_dj, L.jc.at(d), (int)cp.jix_collab.size(), cp.max_cap_collab, d_p32, fl, slots, fl, ids,
+                            W.d_parts.as<uint64_t>(), L.tk.at(d), d_keys, cp.ktop, st.sc));
+    HIPCHK(c, launch_job_topk(d_dj, L.jt.at(d), cp.n_topk_main, fl, ids, slots, d_ncand, d_keys, cp.ktop, st.sc));
+    HIPCHK(c, launch_clubs(J.js, J.view, d_dj, L.jk.at(d), (int)cp.jix_clubs.size(), d_p32, L.p64.at(d), fl,
+                           W.d_acc.as<double>(), fl, ids, d_ncand, (int64_t)J.js.n_club_ids, st.aux2));
+    HIPCHK(c, launch_job_topk(d_dj, L.jt.at(d) + cp.n_topk_main, (int)cp.jix_topk.size() - cp.n_topk_main, fl, ids, slots,
+                              d_ncand, d_keys, cp.ktop, st.aux2));
+    return PF_OK;
+}
+
+// entries of a job's whole result list (a clubs job's holds every club id)
+size_t full_len(const JobsState& J, const DevJob& x) {
+    return (size_t)std::max(x.cap, x.kind == kDjClubs ? J.js.n_club_ids : 0);
+}
+
+// Step 5: the result copies on aux2 behind the last stages, W.done after them, and what
+// finish_chunk needs moved into W: keys (top-k jobs), counts, the fail flag; full lists for the others.
+int queue_results(pf_ctx* c, ChunkPlan& cp, const PlanLayout& L, JobsState::Ws& W, hipStream_t aux2) {
+    auto& J = c->jb;
+    const std::vector<DevJob>& dj = cp.dj;
     std::vector<int32_t> tpos(dj.size(), -1);
-    for (size_t t = 0; t < jix_topk.size(); ++t) tpos[jix_topk[t]] = (int32_t)t;
-    for (size_t t = 0; t < jix_fused.size(); ++t) tpos[jix_fused[t]] = (int32_t)(jix_topk.size() + t);
-    std::vector<size_t> full;  // dj indices copied whole
-    size_t ob = res_b;  // [fail | ncand | keys] as on the device, then the full lists
-    std::vector<size_t> full_off;
+    for (size_t t = 0; t < cp.jix_topk.size(); ++t) tpos[cp.jix_topk[t]] = (int32_t)t;
+    for (size_t t = 0; t < cp.jix_fused.size(); ++t) tpos[cp.jix_fused[t]] = (int32_t)(cp.jix_topk.size() + t);
+    std::vector<size_t> full, full_off;  // dj indices copied whole, and where
+    size_t ob = L.res_bytes;  // [fail | ncand | keys] as on the device, then the full lists
     for (size_t x = 0; x < dj.size(); ++x) {
         if (tpos[x] >= 0) continue;
         full.push_back(x);
         full_off.push_back(ob);
-        ob += a16z((size_t)std::max(dj[x].cap, dj[x].kind == kDjClubs ? J.js.n_club_ids : 0) * 12);
+        ob += a16z(full_len(J, dj[x]) * 12);
     }
     HIPCHK(c, W.h_out.ensure(ob));
     uint8_t* ho = W.h_out.as<uint8_t>();
-    const size_t o_fail = 0, o_cnt = o_rcnt - o_res, o_keys = o_rkeys - o_res;
-    HIPCHK(c, hipMemcpyAsync(ho, d + o_res, res_b, hipMemcpyDeviceToHost, s2));
+    HIPCHK(c, hipMemcpyAsync(ho, L.fail.at(W.d_plan.p), L.res_bytes, hipMemcpyDeviceToHost, aux2));
     for (size_t q = 0; q < full.size(); ++q) {
         const DevJob& x = dj[full[q]];
-        const size_t cnt = (size_t)std::max(x.cap, x.kind == kDjClubs ? J.js.n_club_ids : 0);
+        const size_t cnt = full_len(J, x);
         uint8_t* dst = ho + full_off[q];
-        HIPCHK(c, hipMemcpyAsync(dst, W.d_fl.as<float>() + x.out_off, cnt * 4, hipMemcpyDeviceToHost, s2));
-        HIPCHK(c, hipMemcpyAsync(dst + cnt * 4, W.d_ids.as<int32_t>() + x.out_off, cnt * 4, hipMemcpyDeviceToHost, s2));
-        HIPCHK(c, hipMemcpyAsync(dst + cnt * 8, W.d_slots.as<int32_t>() + x.out_off, cnt * 4, hipMemcpyDeviceToHost,
-                                 s2));
+        HIPCHK(c, hipMemcpyAsync(dst, W.d_fl.as<float>() + x.out_off, cnt * 4, hipMemcpyDeviceToHost, aux2));
+        HIPCHK(c, hipMemcpyAsync(dst + cnt * 4, W.d_ids.as<int32_t>() + x.out_off, cnt * 4, hipMemcpyDeviceToHost, aux2));
+        HIPCHK(c, hipMemcpyAsync(dst + cnt * 8, W.d_slots.as<int32_t>() + x.out_off, cnt * 4, hipMemcpyDeviceToHost, aux2));
     }
-    HIPCHK(c, hipEventRecord(W.done, s2));
-    hl.lap(kHpStage2);  // launches issued
+    HIPCHK(c, hipEventRecord(W.done, aux2));
     W.active = true;
-    W.o_cnt = o_cnt;
-    W.o_keys = o_keys;
-    W.o_fail = o_fail;
-    W.ktop = ktop;
-    W.dj.swap(dj);
-    W.jmap.swap(jmap);
+    W.o_cnt = L.ncand.off - L.fail.off;
+    W.o_keys = L.keys.off - L.fail.off;
+    W.ktop = cp.ktop;
+    W.dj.swap(cp.dj);
+    W.jmap.swap(cp.jmap);
     W.tpos.swap(tpos);
     W.full.swap(full);
     W.full_off.swap(full_off);
     return PF_OK;
+}
+
+// Launches jobs[b, e) (planned in P) on the device with workspaces W: every stage and the result
+// copies are queued (ChunkStreams) and W.done is recorded after them; finish_chunk waits for it
+// and fills jobs[i].out (or raw lists in raw_out).
+int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b, size_t e, JobsState::Ws& W) {
+    auto& J = c->jb;
+    W.active = false;
+    HpLap hl;
+    ChunkPlan cp;
+    if (const int rc = layout_jobs(c, jobs, P, b, e, cp); rc != PF_OK || cp.dj.empty()) return rc;
+    if (W.done == nullptr) {
+        HIPCHK(c, hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&W.ev_pairs, hipEventDisableTiming));
+    }
+    if (const int rc = plan_images(c, cp); rc != PF_OK) return rc;
+    hl.lap(kHpImages);
+    const hipStream_t up = (J.pp ^= 1) ? J.aux : c->stream;
+    const ChunkStreams st{up, up, cp.jix_clubs.empty() ? J.aux2 : up, J.aux2};
+    PlanLayout L;
+    if (const int rc = pack_plan(c, cp, W, st.up, L); rc != PF_OK) return rc;
+    hl.lap(kHpPack);
+    // laps kHpPlan (workspaces) and kHpCollab (images, gathers, pairs launched)
+    if (const int rc = enqueue_chunk(c, cp, L, W, st, hl); rc != PF_OK) return rc;
+    const int rc = queue_results(c, cp, L, W, st.aux2);
+    hl.lap(kHpStage2);  // launches issued
+    return rc;
 }
 
 int finish_chunk(pf_ctx* c, std::vector<Job>& jobs, JobsState::Ws& W, std::vector<std::vector<int32_t>>* raw_out) {
@@ -1139,25 +1179,20 @@ int finish_chunk(pf_ctx* c, std::vector<Job>& jobs, JobsState::Ws& W, std::vecto
     hl.lap(kHpGpu);
     const uint8_t* ho = W.h_out.as<uint8_t>();
     const std::vector<DevJob>& dj = W.dj;
-    const std::vector<int32_t>& jmap = W.jmap;
-    const std::vector<int32_t>& tpos = W.tpos;
-    const std::vector<size_t>& full = W.full;
-    const std::vector<size_t>& full_off = W.full_off;
-    const size_t o_cnt = W.o_cnt, o_keys = W.o_keys, o_fail = W.o_fail;
     const int ktop = W.ktop;
-    if (*reinterpret_cast<const int32_t*>(ho + o_fail))
+    if (*reinterpret_cast<const int32_t*>(ho))  // the fail word leads the result region
         return c->fail(PF_EINTERNAL, "device query table build did not converge");
-    const int32_t* cnt = reinterpret_cast<const int32_t*>(ho + o_cnt);
+    const int32_t* cnt = reinterpret_cast<const int32_t*>(ho + W.o_cnt);
     if (J.stats_on || J.stats_count) {
         J.st_jobs += (int64_t)dj.size();
         for (size_t x = 0; x < dj.size(); ++x)
             if (dj[x].kind == kDjInterest || dj[x].kind == kDjCollab || dj[x].kind == kDjAll) J.st_cands += cnt[x];
     }
-    const uint64_t* keys = reinterpret_cast<const uint64_t*>(ho + o_keys);
+    const uint64_t* keys = reinterpret_cast<const uint64_t*>(ho + W.o_keys);
     for (size_t x = 0; x < dj.size(); ++x) {
-        Job& jb = jobs[jmap[x]];
+        Job& jb = jobs[W.jmap[x]];
         jb.out.clear();
-        if (tpos[x] >= 0) {
+        if (W.tpos[x] >= 0) {
             const uint64_t* kx = keys + (size_t)x * ktop;
             for (int q = 0; q < jb.topk && q < ktop; ++q) {
                 if (kx[q] == ~0ull) break;
@@ -1165,20 +1200,19 @@ int finish_chunk(pf_ctx* c, std::vector<Job>& jobs, JobsState::Ws& W, std::vecto
             }
         }
     }
-    for (size_t q = 0; q < full.size(); ++q) {
-        const size_t x = full[q];
+    for (size_t q = 0; q < W.full.size(); ++q) {
+        const size_t x = W.full[q];
         const DevJob& dx = dj[x];
-        const size_t cntx = (size_t)std::max(dx.cap, dx.kind == kDjClubs ? J.js.n_club_ids : 0);
-        const uint8_t* src = ho + full_off[q];
+        const size_t cntx = full_len(J, dx);
+        const uint8_t* src = ho + W.full_off[q];
         const float* sc = reinterpret_cast<const float*>(src);
         const int32_t* id = reinterpret_cast<const int32_t*>(src + cntx * 4);
         const int32_t* sl = reinterpret_cast<const int32_t*>(src + cntx * 8);
         if (dx.kind == kDjRawGraph || dx.kind == kDjRawCollab) {
-            auto& v = (*raw_out)[jmap[x]];
-            v.assign(id, id + cnt[x]);
+            (*raw_out)[W.jmap[x]].assign(id, id + cnt[x]);
             continue;
         }
-        Job& jb = jobs[jmap[x]];
+        Job& jb = jobs[W.jmap[x]];
         Ranked r;
         if (dx.kind == kDjClubs) {
             for (int32_t k = 0; k < cnt[x]; ++k) r.emplace_back(id[k], sc[k]);
@@ -1193,27 +1227,22 @@ int finish_chunk(pf_ctx* c, std::vector<Job>& jobs, JobsState::Ws& W, std::vecto
     return PF_OK;
 }
 
+// After an error with chunks in flight: everything the pipeline queued has left the device.
+void sync_streams(pf_ctx* c) {
+    (void)hipStreamSynchronize(c->stream);
+    if (c->jb.aux2) (void)hipStreamSynchronize(c->jb.aux2);
+    if (c->jb.aux) (void)hipStreamSynchronize(c->jb.aux);
+}
+
 // Unpack the oldest pending asynchronous call into its caller's buffers (pf_wait).
 int finish_pending(pf_ctx* c) {
     auto& J = c->jb;
     JobsState::Pending& p = J.pending.front();
     int rc = finish_chunk(c, p.jobs, J.ws[p.slot], nullptr);
     if (rc == PF_OK)
-        for (size_t i = 0; i < p.jobs.size(); ++i) {
-            const auto& r = p.jobs[i].out;
-            const int n = std::min<int>((int)r.size(), p.topk);
-            for (int k = 0; k < n; ++k) {
-                p.ou[(int64_t)i * p.topk + k] = r[k].first;
-                p.os[(int64_t)i * p.topk + k] = r[k].second;
-            }
-            p.oc[i] = n;
-        }
+        for (size_t i = 0; i < p.jobs.size(); ++i) emit(p.jobs[i].out, (int)i, p.topk, p.ou, p.os, p.oc);
     J.pending.pop_front();
-    if (rc != PF_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        if (J.aux2) (void)hipStreamSynchronize(J.aux2);
-        if (J.aux) (void)hipStreamSynchronize(J.aux);
-    }
+    if (rc != PF_OK) sync_streams(c);
     return rc;
 }
 
@@ -1288,35 +1317,15 @@ int run_all(pf_ctx* c, std::vector<Job>& jobs, bool raw, std::vector<std::vector
     // is planned and launched while chunk i runs on the device, then chunk i is unpacked.
     // Only large calls are cut: splitting a 64-user cfg-3 step into four chunks made it slower
     // (1.09 -> 1.50 ms: four times the launches, each too small to fill the GPU; r2n).
-    // Chunk sizes by weight (PF_DEBUG chunk_plan=w1:w2:..., A/B): the first chunk's planning and
-    // the last chunk's unpacking are the host work no device stage hides
-    static const std::vector<int> weights = [] {
-        std::vector<int> w;
-        const char* v = debug_str("chunk_plan");
-        std::string str = v ? v : "1:1:1";
-        for (size_t p = 0; p < str.size();) {
-            size_t q = str.find(':', p);
-            if (q == std::string::npos) q = str.size();
-            w.push_back(std::max(1, std::atoi(str.substr(p, q - p).c_str())));
-            p = q + 1;
-        }
-        return w;
-    }();
-    int wsum = 0;
-    for (int w : weights) wsum += w;
-    size_t ck = 0;  // chunks cut so far
+    // Large calls go in three equal chunks: the first chunk's planning and the last chunk's
+    // unpacking are the host work no device stage hides
     auto chunk_end = [&](size_t b) {
-        if (n < kPipeJobs) return n;
-        const size_t w = (size_t)weights[std::min(ck, weights.size() - 1)];
-        const size_t len = std::max<size_t>(kPipeJobs / 4, (n * w + wsum - 1) / wsum);
-        return std::min(n, b + len);
+        return n < kPipeJobs ? n : std::min(n, b + std::max<size_t>(kPipeJobs / 4, (n + 2) / 3));
     };
     int slot = J.carry.on ? (J.carry.slot ^ 1) : 0;  // the carried call holds the other workspace
     JobsState::Ws* pending = nullptr;
     auto drain = [&](int code) {  // an error with a chunk in flight: let it finish first
-        (void)hipStreamSynchronize(c->stream);
-        if (J.aux2) (void)hipStreamSynchronize(J.aux2);
-        if (J.aux) (void)hipStreamSynchronize(J.aux);
+        sync_streams(c);
         for (auto& w : J.ws) w.active = false;
         if (J.carry.on) {  // its results are dropped; pf_eval_wait reports the error
             J.carry_done = J.carry.ticket;
@@ -1328,7 +1337,6 @@ int run_all(pf_ctx* c, std::vector<Job>& jobs, bool raw, std::vector<std::vector
     size_t b = 0;
     while (b < n) {
         const size_t lim = chunk_end(b);
-        ++ck;
         // 1-hop planning is a few microseconds per job: threads only for large chunks (spawning
         // them costs more than planning a 64-user step).  Per chunk: planning every job of a call
         // up front measured no faster (cfg 5 113.4k vs 110.4k users/s, r4n)
@@ -1441,14 +1449,7 @@ int run_jobs_async(pf_ctx* c, std::vector<Job>&& jobs, int32_t topk, int32_t* ou
         rc = jobs_drain(c);
         if (rc == PF_OK) rc = run_all(c, jobs, false, nullptr);
         if (rc != PF_OK) return rc;
-        for (size_t i = 0; i < n; ++i) {
-            const int m = std::min<int>((int)jobs[i].out.size(), topk);
-            for (int k = 0; k < m; ++k) {
-                ou[(int64_t)i * topk + k] = jobs[i].out[k].first;
-                os[(int64_t)i * topk + k] = jobs[i].out[k].second;
-            }
-            oc[i] = m;
-        }
+        for (size_t i = 0; i < n; ++i) emit(jobs[i].out, (int)i, topk, ou, os, oc);
         return PF_OK;
     }
     int slot = 0;  // a slot neither a pending call nor the carried call holds
@@ -1467,9 +1468,7 @@ int run_jobs_async(pf_ctx* c, std::vector<Job>&& jobs, int32_t topk, int32_t* ou
     pd.oc = oc;
     rc = launch_chunk(c, pd.jobs, P, 0, n, J.ws[slot]);
     if (rc != PF_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        if (J.aux2) (void)hipStreamSynchronize(J.aux2);
-        if (J.aux) (void)hipStreamSynchronize(J.aux);
+        sync_streams(c);
         J.ws[slot].active = false;
         return rc;
     }

@@ -329,6 +329,49 @@ def test_big_collab_and_clubs_vs_oracle(big):
         assert list(g[0]) == list(r[0]) and np.array_equal(g[1].view(np.uint32), r[1].view(np.uint32)), u
 
 
+def test_collab_run_spans_three_image_classes():
+    """One collaborative job whose friends' images fall into all three classes of the pair kernel
+    (pf_jobs_plan.cpp plan_images), so the job's candidate run is split three ways: bit-exact
+    against the oracle, and exactly three pair launches (one per non-empty class).
+
+    The classes, for the packed store (one table of 2^lg entries, lg = lg_for(distinct clubs +
+    distinct friends + tokens) = the smallest lg >= 4 with 2 * 2^lg >= 5 n, jobs_open; exclusion
+    table 2^4): kv = (2^lg + 16) * 8 + 16 * tokens bytes of tables and values, staged in LDS when
+    kv <= 49152; a staged image's block needs sizeof(QConst) 4512 + kv + hit lists 24 * 4 * 512 +
+    4 * 512 + 2048 = kv + 57760 bytes and is class 0 when that is <= 80 KB (kv <= 24160), else
+    class 1; an image that is not staged is class 2.  So lg = 12 (820 <= n <= 1638, kv = 32896 +
+    16 * tokens, tokens <= 1016) is class 1: 1,200 friends; lg <= 10 is class 0 up to 990 tokens;
+    22,000 friends (the hub fixture's) give lg = 16, far past the stage limit."""
+    base = tl.synth.Corpus(n_users=20000, seed=77, edge_cases=1)
+    c = tl.corpus_from_desc(base.desc_ptr())
+    u, plain, mid, heavy = 1000, 15000, 3000, 4242
+    c = tl.with_rows(c, user=mid, friends=np.arange(1, 1201, dtype=np.uint32))
+    c = tl.with_rows(c, user=heavy, friends=np.arange(1, 22001, dtype=np.uint32), adj={u: [plain, mid, heavy]})
+    idx = c.index()
+
+    def kv_bytes(uid):  # None: not staged (class 2)
+        i, T = idx[uid], c.n_cols
+        ntok = int(c.tok_off[(i + 1) * T] - c.tok_off[i * T])
+        n = (len(np.unique(c.clubs[c.club_off[i]:c.club_off[i + 1]])) +
+             len(np.unique(c.friends[c.friend_off[i]:c.friend_off[i + 1]])) + ntok)
+        lg = 4
+        while 2 * (1 << lg) < 5 * n:
+            lg += 1
+        kv = ((1 << lg) + 16) * 8 + 16 * ntok
+        return kv if kv <= 49152 else None
+    assert kv_bytes(u) <= 24160 and kv_bytes(plain) <= 24160
+    assert 24160 < kv_bytes(mid) <= 49152
+    assert kv_bytes(heavy) is None
+    eng, orc = tl.engine(c), tl.Oracle(c)
+    assert eng.layout().packed_tokens == 1
+    d0 = eng.jobs_stats()["pair_dispatches"]
+    g, = eng.recommend_collaborative([u], 10, 1000)
+    assert eng.jobs_stats()["pair_dispatches"] - d0 == 3
+    r, = orc.collab([u], 10, 1000)
+    assert len(r[0]) == 10
+    assert list(g[0]) == list(r[0]) and np.array_equal(g[1].view(np.uint32), r[1].view(np.uint32))
+
+
 @pytest.mark.parametrize("kernel", list(SCAN_KERNELS))
 def test_big_top64_vs_oracle(big, kernel):
     c, eng, orc = big
