@@ -251,7 +251,8 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
 // Measured slower than the query-major grid: cfg 4 216.9 vs 203.4 ms per 1024-query launch, r4c)
 uint32_t post_mode(int nq) {
     static const bool tr = pf::debug_long("k5_transposed", 0) != 0;
-    static const bool st = pf::debug_long("k5_static", 0) != 0;  // A/B: static hand-out for one query
+    // A/B: static hand-out for one query, no claimed tail (takes k5_dyn=0 as well: bit 3 overrides it)
+    static const bool st = pf::debug_long("k5_static", 0) != 0;
     // each XCD's workgroups take a contiguous range of every static round's blocks (neighbouring
     // blocks share the cache lines at their list segments' ends); the query-major batch grid too
     // (a query's workgroups are a multiple of 8 there, so bx mod 8 is still the XCD); k5_xcd=0 A/B
@@ -292,8 +293,8 @@ int batch_blocks_per_wg() {
 uint32_t post_image_lds(const pf::QPostHead* h) {
     return pf::post_lds(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend));
 }
-int post_image_per_cu(const pf::QPostHead* h) {
-    return pf::post_blocks_per_cu(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend));
+int post_image_per_cu(const pf::QPostHead* h, int nq) {  // in a launch of nq queries
+    return pf::post_blocks_per_cu(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), post_mode(nq));
 }
 
 int scan_lanes();
@@ -428,7 +429,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
     for (int q = 0; q < nq; ++q) {
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q]->data() + sizeof(pf::QConst));
         vl[q] = pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend);
-        pcu[q] = post_image_per_cu(h);
+        pcu[q] = post_image_per_cu(h, nq);
         order[q] = q;
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pcu[a] > pcu[b]; });
@@ -531,7 +532,7 @@ bool resident_ok(const pf_ctx* c, int32_t i) {
 int scan_post_resident(pf_ctx* c, int32_t i, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
     auto& R = c->rp;
     const uint32_t vl = R.var_lds[i];
-    const int per_cu = pf::post_blocks_per_cu(vl);
+    const int per_cu = pf::post_blocks_per_cu(vl, post_mode(1));
     const int nwb = c->wb_end - c->wb_begin;
     LaneUse lu;
     int rc = lane_begin(c, s, lu);
@@ -1311,7 +1312,7 @@ int pf_scan_bytes(pf_ctx* c, const int32_t* q, int32_t nq, int64_t* out) {
     }
     // workgroups that stage a query's image, as scan_post launches the fitting queries
     const int nwb = c->wb_end - c->wb_begin;
-    const int wgs = nfit == 1 ? one_query_wgs(c->num_cus * pf::post_blocks_per_cu(pf::post_var_lds(max_tok, max_lists)), true)
+    const int wgs = nfit == 1 ? one_query_wgs(c->num_cus * pf::post_blocks_per_cu(pf::post_var_lds(max_tok, max_lists), post_mode(1)), true)
                               : (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg();
     par_jobs((size_t)nq, [&](size_t i) {
         out[i] = kind[i] == 0 ? 0 : (kind[i] == 2 ? k1 : post_query_bytes(c, imgs[i], wgs));

@@ -9,7 +9,8 @@
 //   tile_steps=N          tile-store chunk limit in 16-B steps, splits records over lanes (48)
 //   k5_block=N            postings-scan block size in candidates (kBlockCands, 512; tests)
 //   k5_transposed=1       batched postings scans on the query-fastest grid (A/B; measured slower)
-//   k5_static=1           one-query postings scans with the static block hand-out (A/B)
+//   k5_static=1           one-query postings scans with the static block hand-out and no claimed tail
+//                         (A/B; with k5_dyn=0: alone, every block is still claimed per XCD group)
 //   k5_batch_blocks=N     blocks per workgroup of a batched postings scan (default 32; A/B)
 //   k5_wgs=N              workgroups of a one-query postings scan (default: one resident round; on the
 //                         scan lanes 7/8 of one with 3-5 lanes, 1/2 with 6-11, 3/16 with 12-15; A/B)

@@ -46,7 +46,8 @@ hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t*
                        int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
                        const int32_t* out_rows, uint32_t mode, uint32_t tail_bs, hipEvent_t e0, hipEvent_t e1,
                        hipStream_t s, const uint8_t* qconst = nullptr);
-int post_blocks_per_cu(uint32_t var_lds);
+// workgroups per CU of the instantiation launch_post takes for `mode` (bit 3: the one-query claimed one)
+int post_blocks_per_cu(uint32_t var_lds, uint32_t mode);
 // plain merge of key lists (cross-shard merge after the all-gather)
 hipError_t launch_merge(const uint64_t* in, int nparts, int64_t part_stride, int64_t query_stride, int nq, int k,
                         uint64_t* out, hipStream_t s);

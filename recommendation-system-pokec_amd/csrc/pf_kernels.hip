@@ -26,6 +26,7 @@
 
 #include "pf_device.h"
 #include "pf_kernels.h"
+#include "pf_plan.h"
 
 namespace pf {
 
@@ -1229,40 +1230,7 @@ __device__ __forceinline__ double tok_product(const PTok* pt, int j, uint32_t tf
     return v.wq * ((double)tf * v.idf);
 }
 
-// The next round from (column ci, token jcur): tokens [ja, jb), columns [ca, ce) touched (ce - 1
-// is left unfinished when ci_next == ce - 1).  Greedy: whole columns while the round holds <= 64
-// tokens and <= kRoundCap entries; a column that does not fit an empty round is split (at least
-// one token, whose entries in the block are <= kBlockCands hits).
-struct Round {
-    int ja, jb, ca, ce;
-};
-template <int CAP = kRoundCap>
-__device__ __forceinline__ Round next_round(const QCol* scol, const uint32_t* gpre, int n_act, int& ci, int& jcur) {
-    Round r;
-    r.ja = jcur;
-    r.jb = jcur;
-    r.ca = ci;
-    const uint32_t g0 = gpre[r.ja];
-    while (ci < n_act) {
-        const int j1 = scol[ci].j1;
-        if (j1 - r.ja <= kRoundToks && gpre[j1] - g0 <= (uint32_t)CAP) {
-            r.jb = j1;
-            ++ci;
-            continue;
-        }
-        if (r.jb == r.ja) {
-            int jb = r.ja + 1;
-            const int lim = min(j1, r.ja + kRoundToks);
-            while (jb < lim && gpre[jb + 1] - g0 <= (uint32_t)CAP) ++jb;
-            r.jb = jb;
-            if (jb == j1) ++ci;
-        }
-        break;
-    }
-    jcur = r.jb;
-    r.ce = (ci < n_act && scol[ci].j0 < r.jb) ? ci + 1 : ci;
-    return r;
-}
+// (Round, the serial next_round and the lane-parallel plan_round: pf_plan.h)
 
 #ifdef PF_K5_TIMERS
 // profiling build only (make K5T=1): per-phase clock64() sums over every wave, printed by
@@ -1275,6 +1243,13 @@ __device__ __forceinline__ Round next_round(const QCol* scol, const uint32_t* gp
 #ifndef PF_K5_MINB
 #define PF_K5_MINB 4  // workgroups per CU the register budget is sized for (LDS allows 4 for most queries)
 #endif
+// XD: the one-query launch with every block claimed per XCD group (mode bit 3; launch_post picks
+// the instantiation).  The mode booleans below are constants there, so the transposed grid, the
+// static hand-out, the finer claimed tail and their scalars fold away; <false> serves the batches
+// and the one-query launches without bit 3 (k5_dyn=0: static rounds, with the tail claimed from
+// the query's counter unless k5_static=1, in k5_tail's finer blocks) and never claims per group.
+// (k5_static=1 alone leaves bit 3 set: such a launch is still <true>'s, the flag without effect)
+template <bool XD>
 __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(PostStore ps, const uint8_t* __restrict__ pool,
                                                               const uint32_t* __restrict__ img_off, int32_t blk_begin,
                                                               int32_t blk_end, int32_t k, uint64_t* __restrict__ parts,
@@ -1285,8 +1260,8 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     // mode bit 1 (batches): the grid is transposed, blockIdx.x = the query and blockIdx.y = the block
     // group, so the workgroups resident at once are many queries on the same candidate blocks and
     // the lists they share (popular tokens, clubs) are read from HBM once and then served by L2
-    const bool tr = (mode & 2u) != 0u;
-    const int qy = tr ? (int)blockIdx.x : (int)blockIdx.y;
+    const bool tr = !XD && (mode & 2u) != 0u;
+    const int qy = XD ? 0 : tr ? (int)blockIdx.x : (int)blockIdx.y;
     const int bx = tr ? (int)blockIdx.y : (int)blockIdx.x;
     const int nbx = tr ? (int)gridDim.y : (int)gridDim.x;
     const uint8_t* img = pool + img_off[qy];
@@ -1359,12 +1334,12 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     // dynamic mode (one query): whole static rounds of nbx blocks, then the rest of the range by
     // claim, in blocks of tail_bs candidates: the ~117 blocks past three static rounds of a cfg-2
     // launch would run on ~11 % of the workgroups; cut four times finer they spread over ~470
-    const int tail = (mode & 1u) ? blk_begin + max(1, (blk_end - blk_begin) / nbx) * nbx : blk_end;
+    const int tail = XD ? blk_end : (mode & 1u) ? blk_begin + max(1, (blk_end - blk_begin) / nbx) * nbx : blk_end;
     const uint32_t B = (uint32_t)ps.bsize;
     const uint32_t cend = min((uint32_t)blk_end * B, (uint32_t)ps.n);  // the range's end
     // (mode bit 3 counts every block in whole B-candidate blocks: finer tail blocks apply to the
     // static-rounds mode only)
-    const uint32_t tbs = (tail_bs > 0u && tail_bs < B && !(mode & 8u)) ? tail_bs : B;
+    const uint32_t tbs = (!XD && tail_bs > 0u && tail_bs < B && !(mode & 8u)) ? tail_bs : B;
     const uint32_t cst = min((uint32_t)tail * B, cend);                 // the claimed part's start
     int blk_last = tail + (int)((cend - cst + tbs - 1) / tbs);
     const bool short_excl = H.n_excl <= kPostThreads;
@@ -1380,7 +1355,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     // ones by age and ran their static blocks ~25 % slower every round (r6j block log): claimed
     // blocks let the faster workgroups take more.  The next block is claimed at the start of a
     // block's last text round, so the claim's round trip hides behind that round.
-    const bool xdyn = (mode & 8u) != 0u;
+    const bool xdyn = XD;
     const int xng = min(8, nbx), xg = bx % xng;
     const int x_lo = blk_begin + (int)((int64_t)(blk_end - blk_begin) * xg / xng);
     const int x_hi = blk_begin + (int)((int64_t)(blk_end - blk_begin) * (xg + 1) / xng);
@@ -1389,8 +1364,9 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     if (xdyn) blk_last = x_hi;
     for (int blk = xdyn ? x_lo + bx / xng : blk_begin + pb; blk < blk_last;) {
         unsigned int xclaim = 0;
-        const uint32_t bsz = blk < tail ? B : tbs;  // this block's candidates
-        const uint32_t c0 = blk < tail ? (uint32_t)blk * B : cst + (uint32_t)(blk - tail) * tbs;
+        const bool whole = XD || blk < tail;
+        const uint32_t bsz = whole ? B : tbs;  // this block's candidates
+        const uint32_t c0 = whole ? (uint32_t)blk * B : cst + (uint32_t)(blk - tail) * tbs;
         const uint32_t c1 = min(c0 + bsz, cend) - 1;  // last candidate of the block
 #ifdef PF_K5_BLOCKLOG
         const unsigned long long blog_t0 = __builtin_amdgcn_s_memrealtime();
@@ -1406,6 +1382,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
             ha[kk] = ps.hdr[2 * (size_t)c];
             hb[kk] = ps.hdr[2 * (size_t)c + 1];
         }
+#pragma unroll 1  // (unrolled by two, its second lane set's masks and trip count lived through the block loop)
         for (int j = tid; j < nl; j += kPostThreads)
             rng[j] = list_range(ps, j < H.n_tok ? toks[j].l : sets[j - H.n_tok], c0, c1);
 #pragma unroll
@@ -1423,13 +1400,18 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         __syncthreads();
         K5T(1);
         if (tid < 64) {  // read after the barrier below
+            // (the columns' tokens, read again in every block although they never change: held
+            // through the block loop they would cost every wave two VGPRs for wave 0's sake; the
+            // read is in flight under the prefix)
+            ColPlan cpl = col_tokens(scol, H.n_act, lane);
             wave_prefix(gpre, rng, H.n_tok, lane);
             wave_sync();
+            col_ends(cpl, gpre, H.n_act, lane);
             // the block's rounds, once (every thread used to walk the columns' prefix chain per round)
             {
                 int ci0 = 0, j0 = 0, nr = 0;
                 while (ci0 < H.n_act) {
-                    const Round Rr = next_round(scol, gpre, H.n_act, ci0, j0);
+                    const Round Rr = plan_round(cpl, gpre, H.n_act, lane, ci0, j0);
                     if (lane == 0)
                         rtab[nr] = make_uint2((uint32_t)Rr.ja | (uint32_t)Rr.jb << 16, (uint32_t)Rr.ca | (uint32_t)Rr.ce << 16);
                     if (nr == 0) build_map(mapb, mapc, mapn, gpre, rng, Rr.ja, Rr.jb, lane);
@@ -1562,9 +1544,13 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 {
                     uint32_t xs[U];
                     int js[U];
+                    // (the thread's flat indices and their map words rebuilt per round: as loop
+                    // invariants they held 2 U registers through the whole block loop)
+                    uint32_t ft = (uint32_t)tid;
+                    asm volatile("" : "+v"(ft));
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
-                        const uint32_t f = (uint32_t)(tid + kPostThreads * u);
+                        const uint32_t f = ft + (uint32_t)(kPostThreads * u);
                         // the list map: nonempty lists starting at or before f, minus one
                         js[u] = -1;
                         xs[u] = 0u;  // a valid address
@@ -2033,8 +2019,12 @@ hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t*
     // timed launches (e0, e1 given): the kernel's own start and end timestamps, taken from its
     // dispatch (hipExtLaunchKernelGGL), instead of two marker packets around it
     const dim3 grid = (mode & 2u) ? dim3(nq, blocks) : dim3(blocks, nq);
-    hipExtLaunchKernelGGL(fas_post_kernel, grid, dim3(kPostThreads), post_lds(var_lds), s, e0, e1, 0u, ps, pool, img_off,
-                          blk_begin, blk_end, k, parts, sync, out, out_rows, mode, tail_bs, qconst);
+    // mode bit 3 (every block claimed) is the one-query instantiation's and nobody else's
+    if ((mode & 8u) && (nq != 1 || (mode & 2u))) return hipErrorInvalidValue;
+#define PF_POST(XD) hipExtLaunchKernelGGL(fas_post_kernel<XD>, grid, dim3(kPostThreads), post_lds(var_lds), s, e0, e1, 0u, ps, \
+                                          pool, img_off, blk_begin, blk_end, k, parts, sync, out, out_rows, mode, tail_bs, qconst)
+    if (mode & 8u) PF_POST(true); else PF_POST(false);
+#undef PF_POST
 #ifdef PF_K5_BLOCKLOG
     {
         static int calls = 0;
@@ -2065,13 +2055,17 @@ hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t*
     return hipGetLastError();
 }
 
-int post_blocks_per_cu(uint32_t var_lds) {
-    // per thread, by LDS bytes (a batch asks once per query: the occupancy API once per size)
-    static thread_local std::unordered_map<uint32_t, int> memo;
+int post_blocks_per_cu(uint32_t var_lds, uint32_t mode) {
+    // per thread, by instantiation (the one launch_post takes for this mode) and LDS bytes (a batch
+    // asks once per query: the occupancy API once per size)
+    const bool xd = (mode & 8u) != 0u;
+    static thread_local std::unordered_map<uint32_t, int> memos[2];
+    auto& memo = memos[xd];
     auto it = memo.find(var_lds);
     if (it != memo.end()) return it->second;
     int nb = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel, kPostThreads, post_lds(var_lds));
+    hipError_t e = xd ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true>, kPostThreads, post_lds(var_lds))
+                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false>, kPostThreads, post_lds(var_lds));
     nb = (e == hipSuccess && nb > 0) ? nb : 1;
     if (memo.size() > 4096) memo.clear();
     memo.emplace(var_lds, nb);

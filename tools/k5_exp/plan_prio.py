@@ -7,9 +7,9 @@ s = open(p).read()
 k0 = s.index("void fas_post_kernel(")
 k1 = s.index("// ---------------------------------------------------------------- K2: merge")
 k = s[k0:k1]
-a = "        if (tid < 64) {  // read after the barrier below\n            wave_prefix(gpre, rng, H.n_tok, lane);"
+a = "        if (tid < 64) {  // read after the barrier below\n"
 assert k.count(a) == 1
-k = k.replace(a, "        if (tid < 64) {  // read after the barrier below\n            __builtin_amdgcn_s_setprio(2);\n            wave_prefix(gpre, rng, H.n_tok, lane);", 1)
+k = k.replace(a, a + "            __builtin_amdgcn_s_setprio(2);\n", 1)
 b = "                if (lane == 0) misc[3] = (uint32_t)nr;\n            }\n        }"
 assert k.count(b) == 1
 k = k.replace(b, "                if (lane == 0) misc[3] = (uint32_t)nr;\n            }\n            __builtin_amdgcn_s_setprio(0);\n        }", 1)
