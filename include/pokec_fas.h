@@ -280,6 +280,11 @@ int pf_layout(const pf_ctx* ctx, pf_layout_stats* out);
  * each staging the image once); nq > 1 a batch (each workgroup stages its query's
  * image once for its four blocks). */
 int pf_scan_bytes(pf_ctx* ctx, const int32_t* query_uid, int32_t nq, int64_t* out_bytes);
+/* Counters of the postings scan's pruning, summed over the one-query scans of this process
+ * since the last reset while PF_DEBUG k5_prune_stats=1 is set (zeros otherwise): out[5] =
+ * candidates seen, candidates dropped at a block's start, dropped at a round's end, blocks,
+ * blocks begun before the query had a threshold.  Synchronises the device. */
+int pf_scan_prune_stats(pf_ctx* ctx, int64_t* out, int32_t reset);
 
 /* Statistics of the recommenders' device job pipeline (pf_recommend_collab / _clubs /
  * _interest FoF and the batched drivers) since pf_jobs_stats_reset(ctx, 1): jobs run,

@@ -263,7 +263,13 @@ uint32_t post_mode(int nq) {
     // waits on workgroups dispatched late: cfg 2 1.13e10 -> 1.20e10 candidates/s (r8b / r8c)
     static const bool dyn = pf::debug_long("k5_dyn", 1) != 0;
     const uint32_t x = xcd ? 4u : 0u;
-    return nq == 1 ? ((st ? 0u : 1u) | x | (dyn ? 8u : 0u)) : (tr ? 2u : x);
+    // the one-query instantiation drops candidates that cannot reach the query's shared score
+    // threshold (pf_prune.h): k5_prune=0 off, 1 at block starts only, 2 (default) at round ends too
+    // (A/B; the results are the same bits); k5_prune_stats=1 counts them (pf_scan_prune_stats)
+    static const long pr = pf::debug_long("k5_prune", 2);
+    static const bool prs = pf::debug_long("k5_prune_stats", 0) != 0;
+    const uint32_t p = !dyn || pr <= 0 ? 0u : (pf::kPostPrune | (pr == 1 ? pf::kPostPruneBlockOnly : 0u) | (prs ? pf::kPostPruneStats : 0u));
+    return nq == 1 ? ((st ? 0u : 1u) | x | (dyn ? 8u : 0u) | p) : (tr ? 2u : x);
 }
 
 // Candidates per claimed block past a one-query K5 launch's static rounds (PF_DEBUG k5_tail=N,
@@ -1275,6 +1281,15 @@ int pf_merge_keys_async(pf_ctx* c, const uint64_t* d_parts, int32_t nparts, int3
 
 int pf_jobs_stats_reset(pf_ctx* c, int32_t enable) { return c ? pf::jobs_stats_reset(c, enable) : PF_EINVAL; }
 int pf_jobs_stats_read(pf_ctx* c, pf_jobs_stats* o) { return (c && o) ? pf::jobs_stats_read(c, o) : PF_EINVAL; }
+
+int pf_scan_prune_stats(pf_ctx* c, int64_t* out, int32_t reset) {
+    if (!c || !out) return PF_EINVAL;
+    (void)hipSetDevice(c->device);
+    unsigned long long v[5];
+    HIPCHK(c, pf::k5_prune_stats_read(v, reset != 0));
+    for (int i = 0; i < 5; ++i) out[i] = (int64_t)v[i];
+    return PF_OK;
+}
 
 int pf_scan_bytes(pf_ctx* c, const int32_t* q, int32_t nq, int64_t* out) {
     if (!c || nq < 0 || (nq && (!q || !out))) return PF_EINVAL;

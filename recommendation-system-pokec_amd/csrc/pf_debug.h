@@ -23,6 +23,10 @@
 //   k5_xcd=0|1            K5: contiguous block ranges per XCD in each static round (default 1; A/B)
 //   k5_tail=N             K5: candidates per claimed block past a one-query launch's static rounds
 //                         (default 0 = whole blocks; A/B)
+//   k5_prune=0|1|2        K5: one-query launches drop the candidates that cannot reach the query's shared
+//                         score threshold before their text work (pf_prune.h; the same result bits):
+//                         0 off, 1 at block starts only, 2 (default) at round ends too (A/B)
+//   k5_prune_stats=1      K5: count the candidates seen and dropped (pf_scan_prune_stats)
 //   k5_slice=1            K5s, the wave-private slice kernel: only in the variant build
 //                         PATCH=tools/k5_exp/k5s_slice.patch tools/build_variant.sh k5s
 //                         (A/B: bit-exact, slower)

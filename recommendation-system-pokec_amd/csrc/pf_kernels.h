@@ -42,12 +42,20 @@ uint32_t post_lds(uint32_t var_lds);
 // qconst: nullptr (each image starts with its QConst) or, for a one-query launch from the resident
 // images, the user's QConst elsewhere (its K1' resident image); img = the resident part's start
 // minus sizeof(QConst).  The launch leaves each query's ScanSync zeroed (post_tail).
+// mode: bits 0-3 the block hand-out (pf_api.cpp post_mode); with bit 3, kPostPrune = drop candidates
+// below the query's shared score threshold (pf_prune.h), kPostPruneBlockOnly = at block starts only,
+// kPostPruneStats = count them.
+constexpr uint32_t kPostPrune = 1u << 16, kPostPruneStats = 1u << 17, kPostPruneBlockOnly = 1u << 18;
 hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t* img_off, uint32_t var_lds, int nq,
                        int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
                        const int32_t* out_rows, uint32_t mode, uint32_t tail_bs, hipEvent_t e0, hipEvent_t e1,
                        hipStream_t s, const uint8_t* qconst = nullptr);
 // workgroups per CU of the instantiation launch_post takes for `mode` (bit 3: the one-query claimed one)
 int post_blocks_per_cu(uint32_t var_lds, uint32_t mode);
+// K5 pruning counters of the launches with kPostPruneStats since the last reset (synchronises the device):
+// out[5] = candidates seen, dropped at a block's start, dropped at a round's end, blocks, blocks
+// begun with no threshold yet
+hipError_t k5_prune_stats_read(unsigned long long* out, bool reset);
 // plain merge of key lists (cross-shard merge after the all-gather)
 hipError_t launch_merge(const uint64_t* in, int nparts, int64_t part_stride, int64_t query_stride, int nq, int k,
                         uint64_t* out, hipStream_t s);

@@ -27,6 +27,7 @@
 #include "pf_device.h"
 #include "pf_kernels.h"
 #include "pf_plan.h"
+#include "pf_prune.h"
 
 namespace pf {
 
@@ -41,6 +42,12 @@ __device__ unsigned long long g_k5t[16];
 // waves past the item queue (per-lane fallback), items, epilogue waves
 __device__ unsigned long long g_k1t[12];
 #endif
+
+// K5 pruning counters (mode bit 17, PF_DEBUG k5_prune_stats=1; k5_prune_stats_read): candidates
+// seen, dropped at a block's start, dropped at a round's end, blocks, blocks begun without a threshold
+constexpr int kPruneStats = 5;
+static_assert(kPruneBins <= (int)(sizeof(ScanSync::hist) / sizeof(unsigned int)), "the histogram holds every bin");
+__device__ unsigned long long g_k5_prune[kPruneStats];
 
 #ifdef PF_K5_BLOCKLOG
 // profiling build only (tools/build_variant.sh blog XFLAGS=-DPF_K5_BLOCKLOG): K5's per-block start /
@@ -1107,7 +1114,9 @@ constexpr uint32_t kLdsMapC = kLdsMapN + 2 * 8 * kRoundToks;                  //
 // [ca, ce) = cpre[ce] & ~cpre[ca])
 constexpr uint32_t kLdsLmk = (kLdsMapC + 2 * kMapWords + 7) & ~7u;            // u64 [kPostMaxCols]
 constexpr uint32_t kLdsCpre = kLdsLmk + 8 * kPostMaxCols;                     // u64 [kPostMaxCols + 1]
-constexpr uint32_t kPostFixedLds = (kLdsCpre + 8 * (kPostMaxCols + 1) + 15) & ~15u;
+// pruning (pf_prune.h): the block's need[u] by terms used
+constexpr uint32_t kLdsNeed = kLdsCpre + 8 * (kPostMaxCols + 1);              // f64 [7 + 48 + 1]
+constexpr uint32_t kPostFixedLds = (kLdsNeed + 8 * (kNumFixed + kPostMaxCols + 1) + 15) & ~15u;
 static_assert(kBlockCands == 2 * kPostThreads, "two candidates per thread");
 static_assert(kRoundCap < 65536 && kBlockCands <= kRoundCap, "u16 slots; a one-token round fits");
 static_assert(kPostWaves * kMaxTopK * 8 + 16 + 4 * kMaxTopK <= 8 * kRoundCap, "post_tail scratch in the slots");
@@ -1232,6 +1241,66 @@ __device__ __forceinline__ double tok_product(const PTok* pt, int j, uint32_t tf
 
 // (Round, the serial next_round and the lane-parallel plan_round: pf_plan.h)
 
+// The query's score histogram and theta (ScanSync, pf_prune.h).  At a block's end a wave records the
+// best of its top-k keys that is the block's own (idx in [c0, c1]: each candidate at most once; a key
+// evicted later was still a real candidate with that score) and scores at least thb, the theta the
+// block began with.  One key per wave and block, not all k of them: the true top k of the candidates
+// processed so far are almost surely the best of their own 128, and every agent-scope atomic is
+// served at the memory side, one address at a time: with k keys per wave the first resident
+// round's 36,000 adds on a few dozen bins cost a cfg-2 launch 70 us (0.128 -> 0.200 ms per step).
+// Any subset recorded is valid: theta is the lower edge of the highest bin with >= k recorded scores
+// at or above it, so >= k real candidates score >= theta.  Relaxed atomics: theta only rises and every
+// value it held is valid, so a reader that sees an older one only prunes less.  Returns whether the
+// wave recorded.
+__device__ __forceinline__ bool prune_record(ScanSync* sy, uint64_t best, int k, uint32_t c0, uint32_t c1,
+                                             uint32_t thb, int lane) {
+    uint32_t sb = 0u;
+    bool rec = false;
+    if (lane < k && best != ~0ull) {
+        const uint32_t idx = (uint32_t)best ^ 0x80000000u;
+        sb = __float_as_uint(key_score(best));
+        rec = idx >= c0 && idx <= c1 && sb >= thb && prune_bin(sb) >= 0;
+    }
+    const uint64_t bal = __ballot(rec);
+    if (bal == 0ull) return false;
+    if (lane == __ffsll((unsigned long long)bal) - 1)  // ascending keys: the lowest lane holds the best
+        __hip_atomic_fetch_add(&sy->hist[prune_bin(sb)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return true;
+}
+
+// theta from the histogram, by one wave: lane l sums bins top - 13 l .. top - 13 l - 12, a scan over
+// the lanes from the top finds the bin where the count from above reaches k; published with a max.
+// Returns the new theta (>= thb).  Out of line: a workgroup runs it at the start of a block after
+// one in which it recorded, and its 13 counts per lane stay out of the block loop's register budget.
+static __device__ __attribute__((noinline)) uint32_t prune_derive(ScanSync* sy, int k, uint32_t thb, int lane) {
+    constexpr int kPer = (kPruneBins + 63) / 64;
+    uint32_t cb[kPer], s = 0u;
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) {
+        const int b = kPruneBins - 1 - (kPer * lane + i);
+        cb[i] = b >= 0 ? __hip_atomic_load(&sy->hist[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        s += cb[i];
+    }
+    const uint32_t incl = wave_incl_scan(s);
+    uint32_t run = incl - s, nt = 0u;
+    if (run < (uint32_t)k && incl >= (uint32_t)k) {
+        int bin = 0;
+        bool got = false;
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            run += cb[i];
+            if (!got && run >= (uint32_t)k) {
+                got = true;
+                bin = kPruneBins - 1 - (kPer * lane + i);
+            }
+        }
+        nt = prune_edge(bin);
+        if (nt > thb) __hip_atomic_fetch_max(&sy->theta, nt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    nt = wave_max_u32(nt);
+    return nt > thb ? nt : thb;
+}
+
 #ifdef PF_K5_TIMERS
 // profiling build only (make K5T=1): per-phase clock64() sums over every wave, printed by
 // launch_post every 10th launch
@@ -1302,6 +1371,19 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     uint8_t* mapc = reinterpret_cast<uint8_t*>(base + kLdsMapC);
     uint64_t* lmk = reinterpret_cast<uint64_t*>(base + kLdsLmk);
     uint64_t* cpre = reinterpret_cast<uint64_t*>(base + kLdsCpre);
+    double* need = reinterpret_cast<double*>(base + kLdsNeed);
+    // mode bit 16 (the one-query instantiation only): candidates that cannot reach the query's
+    // shared threshold theta (ScanSync, pf_prune.h) are dropped before their text work; bit 18
+    // leaves out the re-check at round ends; bit 17 counts (g_k5_prune).  Uniform over the launch.
+    // A dropped candidate's skip bit is set and its pending columns cleared; its owner thread
+    // clears its hit mask in each round's slot phase, so it takes no hit slot, and the place phase
+    // passes over the entries whose mask bit is gone: the compaction, the ordered dots, the terms
+    // and its row of the owner sums vanish with them.  (The walk still ORs its bits: testing there
+    // needs a bitmap in LDS, a barrier per block and a read per entry, and spilled registers.)
+    const bool prune = XD && (mode & kPostPrune) != 0u;
+    const bool prune_rnd = prune && !(mode & kPostPruneBlockOnly);
+    const bool pstats = XD && (mode & kPostPruneStats) != 0u;
+    if (tid < 16) misc[tid] = 0u;
     stage(smem, qcp, sizeof(QConst));
     for (int j = tid; j < H.n_act; j += kPostThreads) {
         const QCol c = cols[j];
@@ -1382,6 +1464,9 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
             ha[kk] = ps.hdr[2 * (size_t)c];
             hb[kk] = ps.hdr[2 * (size_t)c + 1];
         }
+        // the threshold as of now (only ever raised: a stale value prunes less), with the headers' loads
+        uint32_t thb = 0u;
+        if (prune) thb = __hip_atomic_load(&sync[qy].theta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll 1  // (unrolled by two, its second lane set's masks and trip count lived through the block loop)
         for (int j = tid; j < nl; j += kPostThreads)
             rng[j] = list_range(ps, j < H.n_tok ? toks[j].l : sets[j - H.n_tok], c0, c1);
@@ -1399,6 +1484,20 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         K5T(0);
         __syncthreads();
         K5T(1);
+        if (prune && tid >= kPostThreads - 64) {
+            // the block's need[u], by the last wave (wave 0 plans the rounds); read after the barrier
+            // below.  After a block in which the workgroup recorded (misc[5], set before that block's
+            // last barrier) the wave first derives theta anew.
+            thb = (uint32_t)__builtin_amdgcn_readfirstlane((int)thb);
+            if (misc[5] != 0u) {
+                thb = prune_derive(sync + qy, k, thb, lane);
+                wave_sync();
+                if (lane == 0) misc[5] = 0u;
+            }
+            const int u = tid - (kPostThreads - 64);
+            if (u == 0) misc[4] = thb;  // the block's theta: read again at its end
+            if (u >= 0 && u <= kNumFixed + kPostMaxCols) need[u] = prune_need(thb, u, kNumFixed + q.n_cols);
+        }
         if (tid < 64) {  // read after the barrier below
             // (the columns' tokens, read again in every block although they never change: held
             // through the block loop they would cost every wave two VGPRs for wave 0's sake; the
@@ -1502,6 +1601,31 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
             sum[kk] = s;
             used |= (uint32_t)(u + __popcll(pend[kk])) << (8 * kk);
         }
+        // 3b. the bound at the block's start: every text term still to come counts 1.  The excluded
+        // and absent candidates lose their text work the same way.
+        if (prune) {
+#pragma unroll
+            for (int kk = 0; kk < kCandsPerThread; ++kk) {
+                const bool sk = (skip >> kk) & 1u;
+                const bool d = !sk && prune_dead(sum[kk], (double)__popcll(pend[kk]), need[(used >> (8 * kk)) & 0xFFu]);
+                if (sk || d) {
+                    skip |= 1u << kk;
+                    pend[kk] = 0ull;
+                }
+                if (pstats) {  // (counted in LDS as they come: no register lives through the block loop for them)
+                    const int p = kk * kPostThreads + tid;
+                    const uint64_t bs = __ballot((uint32_t)p < bsz && c0 + p <= c1), bd = __ballot(d);
+                    if (lane == 0) {
+                        atomicAdd(&misc[8], (uint32_t)__popcll(bs));
+                        atomicAdd(&misc[9], (uint32_t)__popcll(bd));
+                    }
+                }
+            }
+            if (pstats && tid == 0) {
+                misc[11] += 1u;
+                misc[12] += misc[4] == 0u ? 1u : 0u;
+            }
+        }
         K5T(3);
         // 4. text columns in rounds (ascending tokens = ascending columns, then tids)
         double cdot[kCandsPerThread], cnrm[kCandsPerThread];  // a split column's dot / norm so far
@@ -1598,7 +1722,12 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 uint32_t nk[kCandsPerThread], tot = 0;
 #pragma unroll
                 for (int kk = 0; kk < kCandsPerThread; ++kk) {
-                    nk[kk] = (uint32_t)__popcll(mask[kk * kPostThreads + tid]);
+                    uint64_t m = mask[kk * kPostThreads + tid];
+                    if (prune && ((skip >> kk) & 1u) && m != 0ull) {  // dropped: no slots, and place passes over its entries
+                        mask[kk * kPostThreads + tid] = 0ull;
+                        m = 0ull;
+                    }
+                    nk[kk] = (uint32_t)__popcll(m);
                     tot += nk[kk];
                 }
                 uint32_t incl = tot;
@@ -1623,6 +1752,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 for (int u = 0; u < U; ++u) {
                     if (kp[u] == ~0u) continue;
                     const uint32_t p = kp[u] & 1023u, jr = (kp[u] >> 10) & 63u, tf = kp[u] >> 16;
+                    if (prune && !((mask[p] >> jr) & 1ull)) continue;  // a dropped candidate's
                     const uint64_t below = mask[p] & low_bits(jr);
                     const uint32_t r = K5CHK(hbase[p] + (uint32_t)__popcll(below), (uint32_t)kRoundCap, 8);
                     const uint32_t sg = seg[jr], lo = sg & 0xFFu;
@@ -1642,6 +1772,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                     const uint32_t p = (e >> 8) - c0;
                     if (p >= bsz) continue;
                     const uint32_t jr = (uint32_t)(j - ja);
+                    if (prune && !((mask[p] >> jr) & 1ull)) continue;  // a dropped candidate's
                     const uint64_t below = mask[p] & low_bits(jr);
                     const uint32_t r = K5CHK(hbase[p] + (uint32_t)__popcll(below), (uint32_t)kRoundCap, 9);
                     const uint32_t sg = seg[jr];
@@ -1745,6 +1876,24 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 }
                 if (F > 0) mask[p] = 0ull;
             }
+            // f. the bound again with the round's terms in: still to come are the pending columns past
+            // the round, a split column that goes on (t_on) among them
+            if (prune_rnd && rnd + 1 < nrounds) {
+                const uint64_t togo = ~(cpre[R.ce] & ~(t_on >= 0 ? 1ull << t_on : 0ull));
+#pragma unroll
+                for (int kk = 0; kk < kCandsPerThread; ++kk) {
+                    const bool d = !((skip >> kk) & 1u) &&
+                                   prune_dead(sum[kk], (double)__popcll(pend[kk] & togo), need[(used >> (8 * kk)) & 0xFFu]);
+                    if (d) {
+                        skip |= 1u << kk;
+                        pend[kk] = 0ull;
+                    }
+                    if (pstats) {
+                        const uint64_t bal = __ballot(d);
+                        if (lane == 0) atomicAdd(&misc[10], (uint32_t)__popcll(bal));
+                    }
+                }
+            }
             K5T(10);
             if (F == 0 && rnd + 1 < nrounds) {  // an empty round built no list map for the next one
                 if (tid < 64) {
@@ -1782,6 +1931,8 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         if (keys[1] < keys[0]) { const uint64_t x = keys[0]; keys[0] = keys[1]; keys[1] = x; }
 #pragma unroll
         for (int kk = 0; kk < kCandsPerThread; ++kk) topk_push(best, keys[kk], k, lane);
+        // 6. the block's best survivor goes into the query's score histogram
+        if (prune && prune_record(sync + qy, best, k, c0, c1, misc[4], lane) && lane == 0) misc[5] = 1u;
         K5T(12);
 #ifdef PF_K5_BLOCKLOG
         if (tid == 0) {
@@ -1817,6 +1968,10 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         atomicAdd(&g_k5t[15], 1ull);
     }
 #endif
+    if (pstats) {  // a few atomics per workgroup per launch
+        __syncthreads();
+        if (tid < kPruneStats) atomicAdd(&g_k5_prune[tid], (unsigned long long)misc[8 + tid]);
+    }
     // idx -> uid in the wave's list (the same order: uid ascending == idx ascending)
     if (lane < k && best != ~0ull) {
         const uint32_t idx = (uint32_t)best ^ 0x80000000u;
@@ -2053,6 +2208,16 @@ hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t*
     }
 #endif
     return hipGetLastError();
+}
+
+hipError_t k5_prune_stats_read(unsigned long long* out, bool reset) {
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k5_prune), kPruneStats * sizeof(unsigned long long));
+    if (e == hipSuccess && reset) {
+        const unsigned long long z[kPruneStats] = {0};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_k5_prune), z, sizeof(z));
+    }
+    return e;
 }
 
 int post_blocks_per_cu(uint32_t var_lds, uint32_t mode) {

@@ -153,7 +153,13 @@ struct ScanSync {
     unsigned int pad[15];
     unsigned int xcd_next[8 * 16];  // tail tile counter per XCD, 64 B apart
     unsigned int grp[8 * 16];       // K5's group tickets (post_tail), 64 B apart
+    // K5's pruning threshold (pf_prune.h): the float bits of theta, only ever raised, and the
+    // score histogram it is derived from (kPruneBins bins, padded to whole 16-B lines)
+    unsigned int theta;
+    unsigned int pad1[15];
+    unsigned int hist[784];
 };
+static_assert(sizeof(ScanSync) % 16 == 0, "post_tail zeroes ScanSync in 16-B stores");
 
 // top-k key: ascending key == (score desc, uid asc), recommender_graph.cpp:97-101
 __host__ __device__ inline uint64_t score_key(float s, int32_t uid) {

@@ -27,7 +27,7 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_recommend_interest", "pf_recommend_collab", "pf_recommend_clubs", "pf_fof_candidates", "pf_set_adj",
            "pf_set_shard", "pf_scan_keys_async", "pf_merge_keys_async", "pf_decode_keys", "pf_layout",
            "pf_last_scan_ms", "pf_profile_reset", "pf_profile_read", "pf_profile_sample", "pf_set_scan_kernel",
-           "pf_scan_bytes", "pf_jobs_stats_reset", "pf_jobs_stats_read", "pf_recommend_interest_async",
+           "pf_scan_bytes", "pf_scan_prune_stats", "pf_jobs_stats_reset", "pf_jobs_stats_read", "pf_recommend_interest_async",
            "pf_recommend_collab_async", "pf_recommend_clubs_async", "pf_wait", "pf_completed_ticket"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
@@ -116,6 +116,7 @@ def lib():
         L.pf_profile_sample.argtypes = [V, I32]
         L.pf_profile_read.argtypes = [V, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I64)]
         L.pf_scan_bytes.argtypes = [V, V, I32, V]
+        L.pf_scan_prune_stats.argtypes = [V, V, I32]
         L.pf_jobs_stats_reset.argtypes = [V, I32]
         L.pf_jobs_stats_read.argtypes = [V, ctypes.POINTER(PfJobsStats)]
         L.pf_dataset_load.argtypes = [ctypes.c_char_p, I64, ctypes.POINTER(V)]
@@ -339,6 +340,12 @@ class FasEngine:
         s = PfJobsStats()
         self._check(self._L.pf_jobs_stats_read(self.h, ctypes.byref(s)), "pf_jobs_stats_read")
         return {k: getattr(s, k) for k, _ in PfJobsStats._fields_}
+
+    def k5_prune_stats(self, reset=False):
+        """K5's pruning counters (pf_scan_prune_stats; counted under PF_DEBUG k5_prune_stats=1)."""
+        out = np.zeros(5, np.int64)
+        self._check(self._L.pf_scan_prune_stats(self.h, out.ctypes.data, 1 if reset else 0), "pf_scan_prune_stats")
+        return dict(zip(("seen", "dead_block_start", "dead_round_end", "blocks", "cold_blocks"), (int(x) for x in out)))
 
     def scan_bytes(self, uids):
         """Bytes the all-candidates scan kernel reads per query over this shard (pf_scan_bytes)."""
