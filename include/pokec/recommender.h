@@ -83,6 +83,36 @@ using NormMap = std::unordered_map<std::string, std::pair<float, float>>;
 using IdfMap = std::unordered_map<std::string, std::unordered_map<int, float>>;
 using AdjMap = std::unordered_map<int, std::vector<int>>;
 
+// Which candidates recommend_interest_all ranks (pokec_fas.h pf_cand_filter): every member set is
+// one test, all of them must pass.  gender / public_flag: the value to equal (< 0: not tested);
+// age / completion: an inclusive range (max < min: not tested; ages as the profiles hold them);
+// region: each part >= 0 must equal the candidate's part, -1 = any.  A candidate whose tested field
+// is missing (value < 0, age / completion <= 0) fails unless keep_missing.
+struct CandidateFilter {
+    int gender = -1;
+    int public_flag = -1;
+    int age_min = 1, age_max = 0;
+    int completion_min = 1, completion_max = 0;
+    std::array<int, 3> region = {-1, -1, -1};
+    bool keep_missing = false;
+
+    pf_cand_filter c_form() const {
+        pf_cand_filter f{};
+        if (gender >= 0) { f.fields |= PF_FILT_GENDER; f.gender = gender; }
+        if (public_flag >= 0) { f.fields |= PF_FILT_PUBLIC; f.public_flag = public_flag; }
+        if (age_max >= age_min) { f.fields |= PF_FILT_AGE; f.age_min = age_min; f.age_max = age_max; }
+        if (completion_max >= completion_min) {
+            f.fields |= PF_FILT_COMPLETION;
+            f.completion_min = completion_min;
+            f.completion_max = completion_max;
+        }
+        for (int i = 0; i < 3; ++i) f.region[i] = region[(size_t)i] >= 0 ? region[(size_t)i] : -1;
+        if (region[0] >= 0 || region[1] >= 0 || region[2] >= 0) f.fields |= PF_FILT_REGION;
+        if (keep_missing) f.flags |= PF_FILT_KEEP_MISSING;
+        return f;
+    }
+};
+
 namespace detail {
 
 // One engine context and the adjacency rows it currently holds.
@@ -90,6 +120,7 @@ struct Engine {
     pf_ctx* ctx = nullptr;
     std::mutex mu;  // pokec_fas.h: calls on one context are serialised
     AdjMap rows;    // the engine's adj_list (the open-time rows plus every pf_set_adj since)
+    pf_cand_filter scan_filter{};  // the scan filter in force between calls (fields == 0: none)
     int64_t n_users = 0, n_club_entries = 0;
     Engine() = default;
     Engine(const Engine&) = delete;
@@ -221,6 +252,12 @@ public:
     // Build-defined all-candidates interest scan: every profile but the
     // user and its adj_list row, one GPU pass.
     Ranked recommend_interest_all(int user, int topk) const { return run_(3, user, topk, 0); }
+    // The same over the candidates that pass `filter` only (on top of the user's own exclusions);
+    // the engine's filter is set for this call and put back afterwards, under the engine's lock.
+    Ranked recommend_interest_all(int user, int topk, const CandidateFilter& filter) const {
+        const pf_cand_filter f = filter.c_form();
+        return run_(3, user, topk, 0, &f);
+    }
 
     // recommender_similarity.cpp:10-124,126-128, for two profiles of the map
     float profile_similarity(const Profile& A, const Profile& B) const {
@@ -261,7 +298,7 @@ public:
     size_t total_users = 0;
 
 private:
-    Ranked run_(int kind, int user, int topk, int limit) const {
+    Ranked run_(int kind, int user, int topk, int limit, const pf_cand_filter* filter = nullptr) const {
         Ranked out;
         if (!profiles || !adj_list || topk <= 0) return out;
         std::shared_ptr<detail::Engine> e = engine_();
@@ -285,7 +322,14 @@ private:
             case 0: rc = pf_recommend_interest(e->ctx, &q, 1, topk, PF_MODE_FOF, limit, ids.data(), sc.data(), &n); break;
             case 1: rc = pf_recommend_collab(e->ctx, &q, 1, topk, limit, ids.data(), sc.data(), &n); break;
             case 2: rc = pf_recommend_clubs(e->ctx, &q, 1, topk, limit, ids.data(), sc.data(), &n); break;
-            default: rc = pf_recommend_interest(e->ctx, &q, 1, topk, PF_MODE_ALL, 0, ids.data(), sc.data(), &n); break;
+            default:
+                if (filter) rc = pf_set_scan_filter(e->ctx, filter);
+                if (rc == PF_OK) rc = pf_recommend_interest(e->ctx, &q, 1, topk, PF_MODE_ALL, 0, ids.data(), sc.data(), &n);
+                if (filter) {  // the filter in force before the call
+                    const int rr = pf_set_scan_filter(e->ctx, e->scan_filter.fields ? &e->scan_filter : nullptr);
+                    if (rc == PF_OK) rc = rr;
+                }
+                break;
         }
         if (rc != PF_OK) return fail_(e->ctx, out);
         out.reserve((size_t)n);

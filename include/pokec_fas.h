@@ -221,6 +221,41 @@ int pf_set_shard(pf_ctx* ctx, int32_t shard, int32_t nshards);
 int pf_set_scan_kernel(pf_ctx* ctx, int32_t kind);
 
 /*
+ * Candidate filter of the all-candidates scans: only candidates that pass it are ranked ("the k
+ * most similar women aged 20-29 of my region").  Context state like pf_set_shard; it applies to
+ * pf_recommend_interest(PF_MODE_ALL) at any topk and to pf_scan_keys_async, on top of the query's
+ * own exclusions (adj[q] + {q}), and to nothing else: FoF interest, collab, clubs, pf_fas_pairs,
+ * pf_fof_candidates and the hold-out drivers never see it.  Every launch takes the filter by value
+ * as it stands when the call is made, so asynchronous scans already queued keep theirs.  The
+ * reference has no such call: with no filter set every result is what it was.
+ * Values are compared in the domain the corpus was given in (ages as given to pf_open, that is
+ * median-filled); a gender / public value no user has passes nobody.  A field is missing by FAS's
+ * own rules (public / gender < 0, age / completion <= 0, a region part < 0); a candidate whose
+ * tested field is missing fails that test unless PF_FILT_KEEP_MISSING is set.
+ */
+#define PF_FILT_GENDER 1u      /* candidate.gender == gender */
+#define PF_FILT_PUBLIC 2u      /* candidate.public_flag == public_flag */
+#define PF_FILT_AGE 4u         /* age_min <= age <= age_max (ages as given to pf_open: median-filled) */
+#define PF_FILT_COMPLETION 8u  /* completion_min <= completion <= completion_max */
+#define PF_FILT_REGION 16u     /* every region[i] >= 0 equals the candidate's part i; -1 = any */
+#define PF_FILT_KEEP_MISSING 1u /* flags: a candidate whose tested field is missing passes that test */
+
+typedef struct pf_cand_filter {
+    uint32_t fields, flags;
+    int32_t gender, public_flag;
+    int32_t age_min, age_max;
+    int32_t completion_min, completion_max;
+    int32_t region[3], pad;
+} pf_cand_filter;
+
+/* NULL or fields == 0 clears.  PF_EINVAL: unknown bits in fields / flags, a min above its max,
+ * PF_FILT_REGION with all three parts -1. */
+int pf_set_scan_filter(pf_ctx* ctx, const pf_cand_filter* filter);
+/* Candidates of this context's shard that pass the filter (all of them when none is set), the
+ * query's exclusions not counted.  Synchronises the context's stream. */
+int pf_scan_filter_count(pf_ctx* ctx, int64_t* n);
+
+/*
  * Device-resident all-candidates scan for the multi-GPU bench: scores the
  * queries against this context's shard and writes, per query, `topk` packed
  * 64-bit keys to DEVICE memory d_keys[nq*topk] on `stream` (a hipStream_t).
@@ -278,12 +313,15 @@ int pf_layout(const pf_ctx* ctx, pf_layout_stats* out);
  * unknown uid.  The nq queries are taken as ONE launch, as pf_recommend_interest
  * runs them: nq = 1 is the single-query scan (one resident round of workgroups,
  * each staging the image once); nq > 1 a batch (each workgroup stages its query's
- * image once for its four blocks). */
+ * image once for its four blocks).  The candidate filter (pf_set_scan_filter) is ignored: the
+ * bytes are those of the unfiltered scan (a filtered one reads the same headers and ranges and
+ * skips the list entries of the blocks in which nobody passes). */
 int pf_scan_bytes(pf_ctx* ctx, const int32_t* query_uid, int32_t nq, int64_t* out_bytes);
 /* Counters of the postings scan's pruning, summed over the one-query scans of this process
  * since the last reset while PF_DEBUG k5_prune_stats=1 is set (zeros otherwise): out[5] =
  * candidates seen, candidates dropped at a block's start, dropped at a round's end, blocks,
- * blocks begun before the query had a threshold.  Synchronises the device. */
+ * blocks begun before the query had a threshold.  A candidate the scan filter drops counts as seen and
+ * in neither dropped counter.  Synchronises the device. */
 int pf_scan_prune_stats(pf_ctx* ctx, int64_t* out, int32_t reset);
 
 /* Statistics of the recommenders' device job pipeline (pf_recommend_collab / _clubs /

@@ -269,7 +269,11 @@ uint32_t post_mode(int nq) {
     static const long pr = pf::debug_long("k5_prune", 2);
     static const bool prs = pf::debug_long("k5_prune_stats", 0) != 0;
     const uint32_t p = !dyn || pr <= 0 ? 0u : (pf::kPostPrune | (pr == 1 ? pf::kPostPruneBlockOnly : 0u) | (prs ? pf::kPostPruneStats : 0u));
-    return nq == 1 ? ((st ? 0u : 1u) | x | (dyn ? 8u : 0u) | p) : (tr ? 2u : x);
+    // filtered launches (pf_set_scan_filter): k5_filter_blockout=0 runs the blocks in which no
+    // candidate passes to their end (A/B of the whole-block early-out; the results are the same bits)
+    static const bool fko = pf::debug_long("k5_filter_blockout", 1) == 0;
+    const uint32_t f = fko ? pf::kPostFiltKeepBlocks : 0u;
+    return (nq == 1 ? ((st ? 0u : 1u) | x | (dyn ? 8u : 0u) | p) : (tr ? 2u : x)) | f;
 }
 
 // Candidates per claimed block past a one-query K5 launch's static rounds (PF_DEBUG k5_tail=N,
@@ -299,9 +303,11 @@ int batch_blocks_per_wg() {
 uint32_t post_image_lds(const pf::QPostHead* h) {
     return pf::post_lds(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend));
 }
-int post_image_per_cu(const pf::QPostHead* h, int nq) {  // in a launch of nq queries
-    return pf::post_blocks_per_cu(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), post_mode(nq));
+int post_image_per_cu(const pf::QPostHead* h, int nq, bool filtered) {  // in a launch of nq queries
+    return pf::post_blocks_per_cu(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), post_mode(nq), filtered);
 }
+// LDS a filtered launch takes on top of an image's (the filter's words; pf_kernels.h kFiltLds)
+uint32_t filt_lds(const pf_ctx* c) { return c->filt.fields ? pf::kFiltLds : 0u; }
 
 int scan_lanes();
 
@@ -435,7 +441,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
     for (int q = 0; q < nq; ++q) {
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q]->data() + sizeof(pf::QConst));
         vl[q] = pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend);
-        pcu[q] = post_image_per_cu(h, nq);
+        pcu[q] = post_image_per_cu(h, nq, c->filt.fields != 0u);
         order[q] = q;
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pcu[a] > pcu[b]; });
@@ -510,7 +516,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
                                   reinterpret_cast<pf::ScanSync*>(base + offs_b + rows_b) + q0, out_keys,
                                   reinterpret_cast<const int32_t*>(base + offs_b) + q0, post_mode(nq),
                                   tail_block_cands(), (timed && q0 == 0) ? e0 : nullptr,
-                                  (timed && q1 == nq) ? e1 : (ln ? ln->done : nullptr), s));
+                                  (timed && q1 == nq) ? e1 : (ln ? ln->done : nullptr), s, nullptr, c->filt));
         q0 = q1;
     }
     if (ln) {  // the caller's stream: wait for the lane's launch (its stop event), copy its row out
@@ -532,13 +538,13 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
 // the row copy (+ one event record per ring group of eight rows).
 bool resident_ok(const pf_ctx* c, int32_t i) {
     const auto& R = c->rp;
-    return R.on && R.var_lds[i] != 0 && !R.stale[i] && pf::post_lds(R.var_lds[i]) <= kK5LdsCap;
+    return R.on && R.var_lds[i] != 0 && !R.stale[i] && pf::post_lds(R.var_lds[i]) + filt_lds(c) <= kK5LdsCap;
 }
 
 int scan_post_resident(pf_ctx* c, int32_t i, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
     auto& R = c->rp;
     const uint32_t vl = R.var_lds[i];
-    const int per_cu = pf::post_blocks_per_cu(vl, post_mode(1));
+    const int per_cu = pf::post_blocks_per_cu(vl, post_mode(1), c->filt.fields != 0u);
     const int nwb = c->wb_end - c->wb_begin;
     LaneUse lu;
     int rc = lane_begin(c, s, lu);
@@ -562,7 +568,7 @@ int scan_post_resident(pf_ctx* c, int32_t i, int32_t row, int k, uint64_t* d_key
     const uint8_t* qc = c->jb.d_pimg.as<uint8_t>() + c->jb.pimg_off[i];
     HIPCHK(c, pf::launch_post(c->ps, img, R.d_zero.as<uint32_t>(), vl, 1, c->wb_begin, c->wb_end, k, blocks,
                               part_buf.as<uint64_t>(), sync_buf.as<pf::ScanSync>(), out, R.d_zero.as<int32_t>(),
-                              post_mode(1), tail_block_cands(), timed ? e0 : nullptr, stop, ls, qc));
+                              post_mode(1), tail_block_cands(), timed ? e0 : nullptr, stop, ls, qc, c->filt));
     if (ln) {
         rc = lane_end(c, lu, stop, s, d_keys + (size_t)row * k, k);
         if (rc != PF_OK) return rc;
@@ -711,7 +717,7 @@ int scan_stream(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<in
     if (rc != PF_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(e0, s));
     HIPCHK(c, pf::launch_scan(c->ds, d_images, d_refs, im.max_lds, im.gtab, nq, c->tile_begin, c->tile_end, k, blocks,
-                              c->d_part.as<uint64_t>(), d_sync, d_keys, d_rows, s));
+                              c->d_part.as<uint64_t>(), d_sync, d_keys, d_rows, s, c->filt));
     if (timed) {
         HIPCHK(c, hipEventRecord(e1, s));
         c->last_ev0 = e0;
@@ -749,7 +755,7 @@ int scan_all(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<int32
         ex.push_back(u);
         pf::build_query_post(c->hc, c->hp, i, ex, imgs[q]);
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q].data() + sizeof(pf::QConst));
-        fits[q] = post_image_lds(h) <= kK5LdsCap;
+        fits[q] = post_image_lds(h) + filt_lds(c) <= kK5LdsCap;
     });
     std::vector<const std::vector<uint8_t>*> pi;
     std::vector<int32_t> prow, sidx, srow;
@@ -1256,6 +1262,77 @@ int pf_set_scan_kernel(pf_ctx* c, int32_t kind) {
     return PF_OK;
 }
 
+static_assert(PF_FILT_GENDER == pf::kFiltGender && PF_FILT_PUBLIC == pf::kFiltPublic && PF_FILT_AGE == pf::kFiltAge &&
+                  PF_FILT_COMPLETION == pf::kFiltCompletion && PF_FILT_REGION == pf::kFiltRegion &&
+                  PF_FILT_KEEP_MISSING == pf::kFiltKeepMissing,
+              "pf_filter.h restates the public filter bits");
+static_assert(sizeof(pf_cand_filter) == 48, "pf_cand_filter is 48 B");
+
+int pf_set_scan_filter(pf_ctx* c, const pf_cand_filter* f) {
+    if (!c) return PF_EINVAL;
+    if (!f || f->fields == 0u) {
+        c->filt = pf::CandFilter{};
+        return PF_OK;
+    }
+    if ((f->fields & ~pf::kFiltAllFields) || (f->flags & ~pf::kFiltKeepMissing)) return c->fail(PF_EINVAL, "scan filter: unknown bits");
+    if ((f->fields & PF_FILT_AGE) && f->age_min > f->age_max) return c->fail(PF_EINVAL, "scan filter: age_min > age_max");
+    if ((f->fields & PF_FILT_COMPLETION) && f->completion_min > f->completion_max)
+        return c->fail(PF_EINVAL, "scan filter: completion_min > completion_max");
+    if ((f->fields & PF_FILT_REGION) && f->region[0] < 0 && f->region[1] < 0 && f->region[2] < 0)
+        return c->fail(PF_EINVAL, "scan filter: PF_FILT_REGION with no part given");
+    // the headers store public / gender as equality codes: the filter's values are translated once
+    // here; a value no user has gets a code no header holds (and so does a negative one: a missing
+    // field passes through PF_FILT_KEEP_MISSING only)
+    auto code = [](const std::unordered_map<int32_t, uint32_t>& m, int32_t v) -> uint32_t {
+        auto it = v < 0 ? m.end() : m.find(v);
+        return it == m.end() ? pf::kFiltCodeNobody : it->second;
+    };
+    pf::CandFilter d{};
+    d.fields = f->fields;
+    d.flags = f->flags;
+    d.pub = (f->fields & PF_FILT_PUBLIC) ? code(c->hc.pub_code, f->public_flag) : 0u;
+    d.gen = (f->fields & PF_FILT_GENDER) ? code(c->hc.gen_code, f->gender) : 0u;
+    d.age_min = f->age_min;
+    d.age_max = f->age_max;
+    d.comp_min = f->completion_min;
+    d.comp_max = f->completion_max;
+    for (int i = 0; i < 3; ++i) d.reg[i] = (f->fields & PF_FILT_REGION) ? f->region[i] : -1;
+    c->filt = d;
+    return PF_OK;
+}
+
+int pf_scan_filter_count(pf_ctx* c, int64_t* n) {
+    if (!c || !n) return PF_EINVAL;
+    (void)hipSetDevice(c->device);
+    // this shard's candidates, as the kernel the next scan uses sees them: K5's blocks in idx order
+    // (postings headers), else K1's tiles in slot order (tile headers)
+    pf::PostStore ps = c->ps;
+    int64_t i0, i1;
+    if (c->use_post()) {
+        i0 = std::min<int64_t>((int64_t)c->wb_begin * c->ps.bsize, c->ps.n);
+        i1 = std::min<int64_t>((int64_t)c->wb_end * c->ps.bsize, c->ps.n);
+    } else {
+        ps.hdr = nullptr;
+        const auto& s0 = c->hs.tile_slot0;
+        auto slot = [&](int32_t t) -> int64_t { return t < (int32_t)s0.size() ? (int64_t)s0[(size_t)t] : (int64_t)c->ds.n_slots; };
+        i0 = slot(c->tile_begin);
+        i1 = slot(c->tile_end);
+    }
+    if (c->filt.fields == 0u) {  // no filter: everybody
+        *n = std::max<int64_t>(0, i1 - i0);
+        return PF_OK;
+    }
+    HIPCHK(c, c->d_filt_count.ensure(sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->d_filt_count.p, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, pf::launch_filter_count(ps, c->ds, (int32_t)i0, (int32_t)i1, c->filt, c->d_filt_count.as<unsigned long long>(),
+                                      c->stream));
+    unsigned long long v = 0;
+    HIPCHK(c, hipMemcpyAsync(&v, c->d_filt_count.p, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n = (int64_t)v;
+    return PF_OK;
+}
+
 int pf_scan_keys_async(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, uint64_t* d_keys, void* stream) {
     if (!c || nq < 0 || topk <= 0 || topk > pf::kMaxTopK || (nq && (!q || !d_keys))) return PF_EINVAL;
     (void)hipSetDevice(c->device);
@@ -1327,7 +1404,7 @@ int pf_scan_bytes(pf_ctx* c, const int32_t* q, int32_t nq, int64_t* out) {
     }
     // workgroups that stage a query's image, as scan_post launches the fitting queries
     const int nwb = c->wb_end - c->wb_begin;
-    const int wgs = nfit == 1 ? one_query_wgs(c->num_cus * pf::post_blocks_per_cu(pf::post_var_lds(max_tok, max_lists), post_mode(1)), true)
+    const int wgs = nfit == 1 ? one_query_wgs(c->num_cus * pf::post_blocks_per_cu(pf::post_var_lds(max_tok, max_lists), post_mode(1), false), true)
                               : (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg();
     par_jobs((size_t)nq, [&](size_t i) {
         out[i] = kind[i] == 0 ? 0 : (kind[i] == 2 ? k1 : post_query_bytes(c, imgs[i], wgs));

@@ -226,6 +226,10 @@ struct pf_ctx {
     int32_t wb_begin = 0, wb_end = 0;
     int32_t scan_kind = PF_SCAN_AUTO;
     bool use_post() const { return hp.ok && scan_kind != PF_SCAN_STREAM; }
+    // candidate filter of the all-candidates scans (pf_set_scan_filter; fields == 0: none), in its
+    // device form: every scan launch and every kDjAll chunk takes it by value as it stands then
+    pf::CandFilter filt{};
+    DBuf d_filt_count;  // pf_scan_filter_count's counter
     // pinned staging ring for the per-call query upload (a slot is reused only after
     // the copy that read it has completed)
     struct Stage {

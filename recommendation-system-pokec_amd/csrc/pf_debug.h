@@ -27,6 +27,9 @@
 //                         score threshold before their text work (pf_prune.h; the same result bits):
 //                         0 off, 1 at block starts only, 2 (default) at round ends too (A/B)
 //   k5_prune_stats=1      K5: count the candidates seen and dropped (pf_scan_prune_stats)
+//   k5_filter_blockout=0  K5 under a candidate filter (pf_set_scan_filter): blocks in which no candidate
+//                         passes run to their end instead of leaving after the header test (A/B;
+//                         the same result bits)
 //   k5_slice=1            K5s, the wave-private slice kernel: only in the variant build
 //                         PATCH=tools/k5_exp/k5s_slice.patch tools/build_variant.sh k5s
 //                         (A/B: bit-exact, slower)

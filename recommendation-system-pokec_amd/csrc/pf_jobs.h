@@ -18,9 +18,10 @@ struct ImgJob {
     int64_t scr_off;
 };
 
+// filt (fields == 0: none): the candidate filter of the batch's kDjAll jobs, tested on the tile headers of st
 hipError_t launch_gather(const DevJobsStore& g, const DevView& v, const DevJob* jobs, int njobs, const int32_t* pool,
                          const int64_t* pool64, int32_t* ht, int32_t* seq, int32_t* cand_slot, int32_t* cand_id,
-                         int32_t* ncand, hipStream_t s);
+                         int32_t* ncand, const DevStore& st, const CandFilter& filt, hipStream_t s);
 // images [0, n_small) build with kImgLdsSmall bytes of LDS, the next n_big with kImgLds, the next n_glob in
 // global memory
 constexpr uint32_t kImgLdsSmall = 16 * 1024;

@@ -163,7 +163,9 @@ __global__ __launch_bounds__(kGatherThreads) void gather_kernel(DevJobsStore g, 
                                                              const int32_t* __restrict__ pool, int32_t* __restrict__ ht,
                                                              int32_t* __restrict__ seq, int32_t* __restrict__ cand_slot,
                                                              int32_t* __restrict__ cand_id, int32_t* __restrict__ ncand,
-                                                             const int64_t* __restrict__ pool64) {
+                                                             const int64_t* __restrict__ pool64,
+                                                             const uint4* __restrict__ hdr0, const uint4* __restrict__ hdr1,
+                                                             const uint4* __restrict__ hdr2, CandFilter F) {
     __shared__ int wsum[2 * kGatherWaves];
     __shared__ int s_count, s_keep, s_done;
     const DevJob J = jobs[blockIdx.x];
@@ -224,7 +226,10 @@ __global__ __launch_bounds__(kGatherThreads) void gather_kernel(DevJobsStore g, 
                 }
                 h = (h + 1) & mask;
             }
-            slots[i] = ex ? -1 : g.slot_of[i];
+            const int32_t sl = g.slot_of[i];
+            // a candidate the batch's filter (pf_filter.h) fails is left out exactly like an excluded one
+            if (!ex && F.fields != 0u) ex = !filter_pass_tile(F, hdr0[sl], hdr1[sl], hdr2[sl]);
+            slots[i] = ex ? -1 : sl;
             ids[i] = ex ? -1 : g.g_uid[i];
         }
         if (tid == 0) ncand[blockIdx.x] = J.cap;
@@ -1055,10 +1060,10 @@ hipError_t launch_order_pairs(const PairBlock* blocks, int nblocks, const int32_
 
 hipError_t launch_gather(const DevJobsStore& g, const DevView& v, const DevJob* jobs, int njobs, const int32_t* pool,
                          const int64_t* pool64, int32_t* ht, int32_t* seq, int32_t* cand_slot, int32_t* cand_id,
-                         int32_t* ncand, hipStream_t s) {
+                         int32_t* ncand, const DevStore& st, const CandFilter& filt, hipStream_t s) {
     if (njobs <= 0) return hipSuccess;
     hipLaunchKernelGGL(gather_kernel, dim3(njobs), dim3(kGatherThreads), 0, s, g, v, jobs, pool, ht, seq, cand_slot,
-                       cand_id, ncand, pool64);
+                       cand_id, ncand, pool64, st.hdr0, st.hdr1, st.hdr2, filt);
     return hipGetLastError();
 }
 

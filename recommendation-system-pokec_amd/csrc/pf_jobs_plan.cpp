@@ -704,6 +704,9 @@ struct ChunkPlan {
     uint32_t lds_c[3] = {0u, 0u, 0u};  // per pair class: LDS of a block
     int nb_c[3] = {0, 0, 0};           // and its blocks
     int64_t nblk = 0;              // pair blocks of the chunk
+    // the context's candidate filter (pf_set_scan_filter) as it stood when the chunk was planned, when
+    // the chunk holds an all-candidates job (kDjAll: the only kind it applies to); else none
+    CandFilter filt{};
 };
 
 // Step 1: jobs[b, e) (planned in P) as DevJobs, their two pools and their pair-block runs.
@@ -1049,7 +1052,7 @@ int enqueue_chunk(pf_ctx* c, const ChunkPlan& cp, const PlanLayout& L, JobsState
     uint64_t* d_keys = L.keys.at(d);
     HIPCHK(c, launch_expand_pairs(L.gen.at(d), (int)cp.gens.size(), L.gpool.at(d), (int)cp.nblk, d_blk, st.up));  // K9
     HIPCHK(c, launch_gather(J.js, J.view, d_dj, (int)cp.dj.size(), d_p32, L.p64.at(d), W.d_ht.as<int32_t>(),
-                            W.d_seq.as<int32_t>(), slots, ids, d_ncand, st.up));
+                            W.d_seq.as<int32_t>(), slots, ids, d_ncand, c->ds, cp.filt, st.up));
     for (int k = 0, o = 0; k < 3; o += cp.nb_c[k++])  // each launch's dispatch order (relative to its blocks)
         HIPCHK(c, launch_order_pairs(d_blk + o, cp.nb_c[k], slots, c->hc.n, d_ord + o, st.up));
     if (!resident)
@@ -1152,6 +1155,8 @@ int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b
     HpLap hl;
     ChunkPlan cp;
     if (const int rc = layout_jobs(c, jobs, P, b, e, cp); rc != PF_OK || cp.dj.empty()) return rc;
+    for (const DevJob& d : cp.dj)
+        if (d.kind == kDjAll) cp.filt = c->filt;
     if (W.done == nullptr) {
         HIPCHK(c, hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&W.ev_pairs, hipEventDisableTiming));

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pf_filter.h"
 #include "pf_types.h"
 
 namespace pf {
@@ -31,7 +32,7 @@ struct PairGen {
 // the whole launch then uses the global-table variant.
 hipError_t launch_scan(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t lds, bool gtab,
                        int nq, int tile_begin, int tile_end, int k, int blocks, uint64_t* parts, ScanSync* sync,
-                       uint64_t* out, const int32_t* out_rows, hipStream_t s);
+                       uint64_t* out, const int32_t* out_rows, hipStream_t s, const CandFilter& filt);
 // resident scan blocks per CU at this dynamic LDS size (HIP occupancy API)
 int scan_blocks_per_cu(bool packed, bool gtab, uint32_t lds);
 // K5 postings scan over candidate blocks [blk_begin, blk_end) for nq query images (byte
@@ -44,14 +45,25 @@ uint32_t post_lds(uint32_t var_lds);
 // minus sizeof(QConst).  The launch leaves each query's ScanSync zeroed (post_tail).
 // mode: bits 0-3 the block hand-out (pf_api.cpp post_mode); with bit 3, kPostPrune = drop candidates
 // below the query's shared score threshold (pf_prune.h), kPostPruneBlockOnly = at block starts only,
-// kPostPruneStats = count them.
+// kPostPruneStats = count them.  kPostFiltKeepBlocks (filtered launches, A/B): a block in which no
+// candidate passes the filter runs to its end instead of leaving after its first barrier.
+// filt (by value in the launch's arguments; fields == 0: none): the context's candidate filter
+// (pf_filter.h); a filtered launch takes the FILT instantiation of its mode.
 constexpr uint32_t kPostPrune = 1u << 16, kPostPruneStats = 1u << 17, kPostPruneBlockOnly = 1u << 18;
+constexpr uint32_t kPostFiltKeepBlocks = 1u << 19;
+// dynamic LDS a filtered launch takes on top of post_lds(var_lds): the filter, parked past the query's tables
+constexpr uint32_t kFiltLds = (uint32_t)sizeof(CandFilter);
 hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t* img_off, uint32_t var_lds, int nq,
                        int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
                        const int32_t* out_rows, uint32_t mode, uint32_t tail_bs, hipEvent_t e0, hipEvent_t e1,
-                       hipStream_t s, const uint8_t* qconst = nullptr);
-// workgroups per CU of the instantiation launch_post takes for `mode` (bit 3: the one-query claimed one)
-int post_blocks_per_cu(uint32_t var_lds, uint32_t mode);
+                       hipStream_t s, const uint8_t* qconst, const CandFilter& filt);
+// workgroups per CU of the instantiation launch_post takes for `mode` (bit 3: the one-query claimed
+// one) and `filtered` (a filter is set)
+int post_blocks_per_cu(uint32_t var_lds, uint32_t mode, bool filtered);
+// candidates of idx range [i0, i1) of the postings headers (ps.hdr), or with ps.hdr null of slots
+// [i0, i1) of the tile headers, that pass filt: added to *count (device, zeroed by the caller)
+hipError_t launch_filter_count(const PostStore& ps, const DevStore& st, int32_t i0, int32_t i1, const CandFilter& filt,
+                               unsigned long long* count, hipStream_t s);
 // K5 pruning counters of the launches with kPostPruneStats since the last reset (synchronises the device):
 // out[5] = candidates seen, dropped at a block's start, dropped at a round's end, blocks, blocks
 // begun with no threshold yet

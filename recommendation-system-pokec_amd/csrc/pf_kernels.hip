@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "pf_device.h"
+#include "pf_filter.h"
 #include "pf_kernels.h"
 #include "pf_plan.h"
 #include "pf_prune.h"
@@ -974,7 +975,7 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_scan_kernel(DevStore st, 
                                                                 uint64_t* __restrict__ parts,
                                                                 ScanSync* __restrict__ sync,
                                                                 uint64_t* __restrict__ out,
-                                                                const int32_t* __restrict__ out_rows) {
+                                                                const int32_t* __restrict__ out_rows, CandFilter F) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const QImageRef r = refs[blockIdx.y];
     char* scratch;
@@ -1036,13 +1037,15 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_scan_kernel(DevStore st, 
         for (int m = 1; m < (1 << lgk); m <<= 1) cnt += (uint32_t)__shfl_xor((int)cnt, m);
         v.nh[threadIdx.x] = W.nh;
         __builtin_amdgcn_wave_barrier();
-        if (active && ci == 0) {
+        // a candidate the context's filter (pf_filter.h; fields == 0: none) fails gets no epilogue and no key
+        const bool scored = active && ci == 0 && (F.fields == 0u || filter_pass_tile(F, h0, h1, h2));
+        if (scored) {
             const uint32_t* nhp = v.nh + threadIdx.x;
             const TileRec rec{&st, l, q};
             f = fas_epilogue<PACKED>(v, rec, h0, h1, h2, cnt, threadIdx.x, 1u << lgk, [&](uint32_t g) { return nhp[g]; });
         }
         uint64_t key = ~0ull;
-        if (active && ci == 0) {
+        if (scored) {
             const int32_t uid = (int32_t)h1.w;
             if (!excluded<PACKED>(v, (uint32_t)uid)) key = score_key(f, uid);
         }
@@ -1318,13 +1321,17 @@ static __device__ __attribute__((noinline)) uint32_t prune_derive(ScanSync* sy, 
 // and the one-query launches without bit 3 (k5_dyn=0: static rounds, with the tail claimed from
 // the query's counter unless k5_static=1, in k5_tail's finer blocks) and never claims per group.
 // (k5_static=1 alone leaves bit 3 set: such a launch is still <true>'s, the flag without effect)
-template <bool XD>
+// FILT: the context has a candidate filter (pf_filter.h, F; launch_post picks the instantiation): a
+// candidate whose header fails it is dropped like an excluded one, a block in which nobody passes
+// is left after its first barrier.  <XD, false> never reads F and is the code it was without it.
+template <bool XD, bool FILT>
 __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(PostStore ps, const uint8_t* __restrict__ pool,
                                                               const uint32_t* __restrict__ img_off, int32_t blk_begin,
                                                               int32_t blk_end, int32_t k, uint64_t* __restrict__ parts,
                                                               ScanSync* __restrict__ sync, uint64_t* __restrict__ out,
                                                               const int32_t* __restrict__ out_rows, uint32_t mode,
-                                                              uint32_t tail_bs, const uint8_t* __restrict__ qconst) {
+                                                              uint32_t tail_bs, const uint8_t* __restrict__ qconst,
+                                                              CandFilter F) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // mode bit 1 (batches): the grid is transposed, blockIdx.x = the query and blockIdx.y = the block
     // group, so the workgroups resident at once are many queries on the same candidate blocks and
@@ -1383,6 +1390,19 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     const bool prune = XD && (mode & kPostPrune) != 0u;
     const bool prune_rnd = prune && !(mode & kPostPruneBlockOnly);
     const bool pstats = XD && (mode & kPostPruneStats) != 0u;
+    // The drop mechanics (pend cleared, the mask cleared in the slot phase, place passing over the
+    // candidate) serve the filter as well: a filtered instantiation always has them, the batch and
+    // k5_prune=0 included; the theta bound itself stays behind `prune`.
+    const bool drop = FILT || prune;
+    // The filter's 12 uniform words would live in scalar registers through the whole block loop, which
+    // already keeps 84 of them in spill lanes (<true> with them: 125 spilled, 2 VGPRs and 16 B of
+    // scratch): they are parked once in the kFiltLds bytes a filtered launch allocates past the
+    // query's variable part, and each block's header test reads them from there.
+    CandFilter* fl = reinterpret_cast<CandFilter*>(
+        smem + (((uint32_t)(reinterpret_cast<char*>(colof) + H.n_tok - smem) + 15u) & ~15u));
+    if constexpr (FILT) {
+        if (tid == 0) *fl = F;
+    }
     if (tid < 16) misc[tid] = 0u;
     stage(smem, qcp, sizeof(QConst));
     for (int j = tid; j < H.n_act; j += kPostThreads) {
@@ -1482,7 +1502,53 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         }
         if (tid < kBlockCands / 32) exb[tid] = 0u;
         K5T(0);
-        __syncthreads();
+        if constexpr (FILT) {
+            uint32_t fskip = 0;  // bit kk: candidate kk is there and fails the filter
+            // the header test rides on the block's first barrier: when no candidate of the block
+            // passes, the block ends here (no sets, no rounds, no top-k push); kPostFiltKeepBlocks
+            // (A/B) runs such blocks to their end
+            bool any = false;
+            const CandFilter f = *fl;  // (published by the staging barrier before the block loop)
+#pragma unroll
+            for (int kk = 0; kk < kCandsPerThread; ++kk) {
+                const bool there = c0 + kk * kPostThreads + tid <= c1 && (uint32_t)(kk * kPostThreads + tid) < bsz;
+                const bool ok = filter_pass_post(f, ha[kk], hb[kk]);
+                if (there && !ok) fskip |= 1u << kk;
+                any |= there && ok;
+            }
+            if (!__syncthreads_or(any) && !(mode & kPostFiltKeepBlocks)) {
+                if (pstats && tid == 0) {  // seen, in neither dead counter
+                    misc[8] += c1 - c0 + 1u;
+                    misc[11] += 1u;
+                    misc[12] += thb == 0u ? 1u : 0u;
+                }
+                // the next block, as at the loop's end
+                if (xdyn) {
+                    if (tid == 0) misc[0] = (uint32_t)(x_lo + x_nwg) + atomicAdd(xctr, 1u);
+                    __syncthreads();
+                    blk = (int)misc[0];
+                } else if ((mode & 1u) && blk + nbx >= tail) {
+                    if (tid == 0) misc[0] = (uint32_t)tail + atomicAdd(next_blk, 1u);
+                    __syncthreads();
+                    blk = (int)misc[0];
+                } else {
+                    __syncthreads();
+                    blk += nbx;
+                }
+                continue;
+            }
+            // a candidate that fails is marked like an excluded one (the bits were zeroed before the
+            // barrier; the exclusion list ORs into the same words below), so step 3 needs no word of
+            // the filter and no register carries the result there
+#pragma unroll
+            for (int kk = 0; kk < kCandsPerThread; ++kk) {
+                const uint64_t bal = __ballot((fskip >> kk) & 1u);
+                const uint32_t w = (uint32_t)(bal >> (lane & 32));
+                if ((lane & 31) == 0 && w != 0u) atomicOr(&exb[(kk * kPostThreads + tid) >> 5], w);
+            }
+        } else {
+            __syncthreads();
+        }
         K5T(1);
         if (prune && tid >= kPostThreads - 64) {
             // the block's need[u], by the last wave (wave 0 plans the rounds); read after the barrier
@@ -1603,11 +1669,11 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         }
         // 3b. the bound at the block's start: every text term still to come counts 1.  The excluded
         // and absent candidates lose their text work the same way.
-        if (prune) {
+        if (drop) {
 #pragma unroll
             for (int kk = 0; kk < kCandsPerThread; ++kk) {
                 const bool sk = (skip >> kk) & 1u;
-                const bool d = !sk && prune_dead(sum[kk], (double)__popcll(pend[kk]), need[(used >> (8 * kk)) & 0xFFu]);
+                const bool d = prune && !sk && prune_dead(sum[kk], (double)__popcll(pend[kk]), need[(used >> (8 * kk)) & 0xFFu]);
                 if (sk || d) {
                     skip |= 1u << kk;
                     pend[kk] = 0ull;
@@ -1723,7 +1789,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
 #pragma unroll
                 for (int kk = 0; kk < kCandsPerThread; ++kk) {
                     uint64_t m = mask[kk * kPostThreads + tid];
-                    if (prune && ((skip >> kk) & 1u) && m != 0ull) {  // dropped: no slots, and place passes over its entries
+                    if (drop && ((skip >> kk) & 1u) && m != 0ull) {  // dropped: no slots, and place passes over its entries
                         mask[kk * kPostThreads + tid] = 0ull;
                         m = 0ull;
                     }
@@ -1752,7 +1818,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 for (int u = 0; u < U; ++u) {
                     if (kp[u] == ~0u) continue;
                     const uint32_t p = kp[u] & 1023u, jr = (kp[u] >> 10) & 63u, tf = kp[u] >> 16;
-                    if (prune && !((mask[p] >> jr) & 1ull)) continue;  // a dropped candidate's
+                    if (drop && !((mask[p] >> jr) & 1ull)) continue;  // a dropped candidate's
                     const uint64_t below = mask[p] & low_bits(jr);
                     const uint32_t r = K5CHK(hbase[p] + (uint32_t)__popcll(below), (uint32_t)kRoundCap, 8);
                     const uint32_t sg = seg[jr], lo = sg & 0xFFu;
@@ -1772,7 +1838,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                     const uint32_t p = (e >> 8) - c0;
                     if (p >= bsz) continue;
                     const uint32_t jr = (uint32_t)(j - ja);
-                    if (prune && !((mask[p] >> jr) & 1ull)) continue;  // a dropped candidate's
+                    if (drop && !((mask[p] >> jr) & 1ull)) continue;  // a dropped candidate's
                     const uint64_t below = mask[p] & low_bits(jr);
                     const uint32_t r = K5CHK(hbase[p] + (uint32_t)__popcll(below), (uint32_t)kRoundCap, 9);
                     const uint32_t sg = seg[jr];
@@ -2083,14 +2149,56 @@ __global__ PF_K1P_BOUNDS void fas_pairs_kernel(DevStore st, const uint8_t* __res
 #endif
 }
 
+// ---------------------------------------------------------------- filter count
+// Candidates [i0, i1) that pass F: postings headers (POST; idx order) or tile headers (slot order).
+// A block reduction (a wave scan of the lanes' counts, then the waves' sums through LDS) and one
+// atomic add per workgroup.
+constexpr int kCountThreads = 256;
+template <bool POST>
+__global__ __launch_bounds__(kCountThreads) void filter_count_kernel(const uint4* __restrict__ hdr, const uint4* __restrict__ hdr1,
+                                                                     const uint4* __restrict__ hdr2, int32_t i0, int32_t i1,
+                                                                     CandFilter F, unsigned long long* __restrict__ count) {
+    __shared__ uint32_t wsum[kCountThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t n = 0;
+    for (int64_t i = (int64_t)i0 + (int64_t)blockIdx.x * kCountThreads + threadIdx.x; i < i1;
+         i += (int64_t)gridDim.x * kCountThreads) {
+        bool ok;
+        if (POST) ok = filter_pass_post(F, hdr[2 * i], hdr[2 * i + 1]);
+        else ok = filter_pass_tile(F, hdr[i], hdr1[i], hdr2[i]);
+        n += ok ? 1u : 0u;
+    }
+    n = wave_last(wave_incl_scan(n));
+    if (lane == 0) wsum[wave] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < kCountThreads / 64; ++w) t += wsum[w];
+        if (t) atomicAdd(count, (unsigned long long)t);
+    }
+}
+
 // ---------------------------------------------------------------- launchers
+hipError_t launch_filter_count(const PostStore& ps, const DevStore& st, int32_t i0, int32_t i1, const CandFilter& filt,
+                               unsigned long long* count, hipStream_t s) {
+    if (i1 <= i0) return hipSuccess;
+    const int blocks = std::max(1, std::min(1024, (i1 - i0 + kCountThreads - 1) / kCountThreads));
+    if (ps.hdr)
+        hipLaunchKernelGGL(filter_count_kernel<true>, dim3(blocks), dim3(kCountThreads), 0, s, ps.hdr, (const uint4*)nullptr,
+                           (const uint4*)nullptr, i0, i1, filt, count);
+    else
+        hipLaunchKernelGGL(filter_count_kernel<false>, dim3(blocks), dim3(kCountThreads), 0, s, st.hdr0, st.hdr1, st.hdr2, i0,
+                           i1, filt, count);
+    return hipGetLastError();
+}
+
 hipError_t launch_scan(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t lds, bool gtab,
                        int nq, int tile_begin, int tile_end, int k, int blocks, uint64_t* parts, ScanSync* sync,
-                       uint64_t* out, const int32_t* out_rows, hipStream_t s) {
+                       uint64_t* out, const int32_t* out_rows, hipStream_t s, const CandFilter& filt) {
     if (nq <= 0) return hipSuccess;
     dim3 grid(blocks, nq), block(kScanThreads);
 #define PF_SCAN(P, G) hipLaunchKernelGGL((fas_scan_kernel<P, G>), grid, block, lds, s, st, pool, refs_dev, tile_begin, \
-                                         tile_end, k, parts, sync, out, out_rows)
+                                         tile_end, k, parts, sync, out, out_rows, filt)
     if (st.packed) { if (gtab) PF_SCAN(true, true); else PF_SCAN(true, false); }
     else { if (gtab) PF_SCAN(false, true); else PF_SCAN(false, false); }
 #undef PF_SCAN
@@ -2169,16 +2277,19 @@ static void blog_report(int nbx) {
 hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t* img_off, uint32_t var_lds, int nq,
                        int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
                        const int32_t* out_rows, uint32_t mode, uint32_t tail_bs, hipEvent_t e0, hipEvent_t e1,
-                       hipStream_t s, const uint8_t* qconst) {
+                       hipStream_t s, const uint8_t* qconst, const CandFilter& filt) {
     if (nq <= 0) return hipSuccess;
     // timed launches (e0, e1 given): the kernel's own start and end timestamps, taken from its
     // dispatch (hipExtLaunchKernelGGL), instead of two marker packets around it
     const dim3 grid = (mode & 2u) ? dim3(nq, blocks) : dim3(blocks, nq);
     // mode bit 3 (every block claimed) is the one-query instantiation's and nobody else's
     if ((mode & 8u) && (nq != 1 || (mode & 2u))) return hipErrorInvalidValue;
-#define PF_POST(XD) hipExtLaunchKernelGGL(fas_post_kernel<XD>, grid, dim3(kPostThreads), post_lds(var_lds), s, e0, e1, 0u, ps, \
-                                          pool, img_off, blk_begin, blk_end, k, parts, sync, out, out_rows, mode, tail_bs, qconst)
-    if (mode & 8u) PF_POST(true); else PF_POST(false);
+#define PF_POST(XD, FILT) hipExtLaunchKernelGGL((fas_post_kernel<XD, FILT>), grid, dim3(kPostThreads), lds, s, e0, e1, 0u, ps, \
+                                                pool, img_off, blk_begin, blk_end, k, parts, sync, out, out_rows, mode, tail_bs, qconst, filt)
+    const uint32_t lds = post_lds(var_lds) + (filt.fields ? kFiltLds : 0u);  // + the filter's words (fas_post_kernel)
+    // the filter travels in the launch's own arguments: a later pf_set_scan_filter does not reach it
+    if (filt.fields) { if (mode & 8u) PF_POST(true, true); else PF_POST(false, true); }
+    else { if (mode & 8u) PF_POST(true, false); else PF_POST(false, false); }
 #undef PF_POST
 #ifdef PF_K5_BLOCKLOG
     {
@@ -2220,17 +2331,21 @@ hipError_t k5_prune_stats_read(unsigned long long* out, bool reset) {
     return e;
 }
 
-int post_blocks_per_cu(uint32_t var_lds, uint32_t mode) {
-    // per thread, by instantiation (the one launch_post takes for this mode) and LDS bytes (a batch
-    // asks once per query: the occupancy API once per size)
+int post_blocks_per_cu(uint32_t var_lds, uint32_t mode, bool filtered) {
+    // per thread, by instantiation (the one launch_post takes for this mode and filter) and LDS bytes
+    // (a batch asks once per query: the occupancy API once per size)
     const bool xd = (mode & 8u) != 0u;
-    static thread_local std::unordered_map<uint32_t, int> memos[2];
-    auto& memo = memos[xd];
+    static thread_local std::unordered_map<uint32_t, int> memos[4];
+    auto& memo = memos[2 * (int)filtered + (int)xd];
     auto it = memo.find(var_lds);
     if (it != memo.end()) return it->second;
     int nb = 0;
-    hipError_t e = xd ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true>, kPostThreads, post_lds(var_lds))
-                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false>, kPostThreads, post_lds(var_lds));
+    const size_t lds = post_lds(var_lds) + (filtered ? kFiltLds : 0u);
+    hipError_t e;
+    if (filtered) e = xd ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true, true>, kPostThreads, lds)
+                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false, true>, kPostThreads, lds);
+    else e = xd ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true, false>, kPostThreads, lds)
+                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false, false>, kPostThreads, lds);
     nb = (e == hipSuccess && nb > 0) ? nb : 1;
     if (memo.size() > 4096) memo.clear();
     memo.emplace(var_lds, nb);

@@ -49,6 +49,9 @@ PF_HD inline float prune_float(uint32_t bits) {
 //        neighbourhood, that is < theta: a candidate scoring exactly theta is never dropped.
 // A term is a sigmoid value, (1 or e) / (1 + e) with e >= 0, at most 1.0 as computed, so
 // acc so far + the number of terms still to come bounds the final acc.
+// theta itself is valid because only keyed candidates are recorded in the histogram: an excluded
+// candidate, and one the scan's candidate filter drops (pf_filter.h), is never keyed, so at least k
+// candidates that can be ranked score >= theta, with or without a filter.
 PF_HD inline double prune_need(uint32_t theta_bits, int u, int nterms) {
     if (theta_bits == 0u) return 0.0;
     const double t = (double)prune_float(theta_bits) * (1.0 - 1.0 / 1048576.0);

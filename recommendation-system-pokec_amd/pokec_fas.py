@@ -21,6 +21,9 @@ PF_MODE_FOF, PF_MODE_ALL = 0, 1
 PF_FOF_GRAPH, PF_FOF_COLLAB = 0, 1
 PF_SCAN_AUTO, PF_SCAN_STREAM, PF_SCAN_POSTINGS = 0, 1, 2
 MAX_TOPK_DEVICE = 64
+# candidate filter of the all-candidates scans (pf_cand_filter)
+PF_FILT_GENDER, PF_FILT_PUBLIC, PF_FILT_AGE, PF_FILT_COMPLETION, PF_FILT_REGION = 1, 2, 4, 8, 16
+PF_FILT_KEEP_MISSING = 1
 
 # every entry point of include/pokec_fas.h
 EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_users", "pf_idf", "pf_fas_pairs",
@@ -28,7 +31,8 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_set_shard", "pf_scan_keys_async", "pf_merge_keys_async", "pf_decode_keys", "pf_layout",
            "pf_last_scan_ms", "pf_profile_reset", "pf_profile_read", "pf_profile_sample", "pf_set_scan_kernel",
            "pf_scan_bytes", "pf_scan_prune_stats", "pf_jobs_stats_reset", "pf_jobs_stats_read", "pf_recommend_interest_async",
-           "pf_recommend_collab_async", "pf_recommend_clubs_async", "pf_wait", "pf_completed_ticket"]
+           "pf_recommend_collab_async", "pf_recommend_clubs_async", "pf_wait", "pf_completed_ticket",
+           "pf_set_scan_filter", "pf_scan_filter_count"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
               "pf_dataset_profile_order", "pf_dataset_adj_order", "pf_dataset_profile_json", "pf_dataset_club_name",
@@ -44,6 +48,49 @@ class PfLayoutStats(ctypes.Structure):
                 ("alg_bytes", ctypes.c_int64), ("packed_tokens", ctypes.c_int32), ("n_tiles", ctypes.c_int32),
                 ("post_bytes", ctypes.c_int64), ("scan_kernel", ctypes.c_int32), ("pad", ctypes.c_int32),
                 ("shard_cands", ctypes.c_int64), ("shard_entries", ctypes.c_int64)]
+
+
+class CandFilter(ctypes.Structure):
+    """pf_cand_filter: which candidates the all-candidates scans rank.  `fields` says which tests
+    apply (PF_FILT_*); `flags` = PF_FILT_KEEP_MISSING lets a candidate whose tested field is missing
+    pass that test.  CandFilter.make(...) builds one from keyword arguments."""
+    _fields_ = [("fields", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("gender", ctypes.c_int32),
+                ("public_flag", ctypes.c_int32), ("age_min", ctypes.c_int32), ("age_max", ctypes.c_int32),
+                ("completion_min", ctypes.c_int32), ("completion_max", ctypes.c_int32),
+                ("region", ctypes.c_int32 * 3), ("pad", ctypes.c_int32)]
+
+    @classmethod
+    def make(cls, gender=None, public_flag=None, age=None, completion=None, region=None, keep_missing=False):
+        """gender / public_flag: the value to equal; age / completion: (min, max), either end None =
+        open; region: up to three parts, None or -1 = any."""
+        f = cls()
+        f.region[0] = f.region[1] = f.region[2] = -1
+        if gender is not None:
+            f.fields |= PF_FILT_GENDER
+            f.gender = int(gender)
+        if public_flag is not None:
+            f.fields |= PF_FILT_PUBLIC
+            f.public_flag = int(public_flag)
+        if age is not None:
+            f.fields |= PF_FILT_AGE
+            f.age_min = 1 if age[0] is None else int(age[0])
+            f.age_max = 2**31 - 1 if age[1] is None else int(age[1])
+        if completion is not None:
+            f.fields |= PF_FILT_COMPLETION
+            f.completion_min = 1 if completion[0] is None else int(completion[0])
+            f.completion_max = 2**31 - 1 if completion[1] is None else int(completion[1])
+        if region is not None:
+            f.fields |= PF_FILT_REGION
+            for i, r in enumerate(list(region)[:3]):
+                f.region[i] = -1 if r is None else int(r)
+        if keep_missing:
+            f.flags |= PF_FILT_KEEP_MISSING
+        return f
+
+    def copy(self):
+        g = CandFilter()
+        ctypes.memmove(ctypes.byref(g), ctypes.byref(self), ctypes.sizeof(CandFilter))
+        return g
 
 
 class PfJobsStats(ctypes.Structure):
@@ -105,6 +152,8 @@ def lib():
         L.pf_set_adj.argtypes = [V, I32, V, I32]
         L.pf_set_shard.argtypes = [V, I32, I32]
         L.pf_set_scan_kernel.argtypes = [V, I32]
+        L.pf_set_scan_filter.argtypes = [V, ctypes.POINTER(CandFilter)]
+        L.pf_scan_filter_count.argtypes = [V, ctypes.POINTER(I64)]
         L.pf_scan_keys_async.argtypes = [V, V, I32, I32, V, V]
         L.pf_merge_keys_async.argtypes = [V, V, I32, I32, I32, V, V]
         L.pf_decode_keys.argtypes = [V, I32, V, V, V]
@@ -163,6 +212,7 @@ class FasEngine:
         # whenever the queue drains (pf_wait, or any synchronous call), so the engine, not the
         # caller's handle, keeps them alive until a wait covers them or the engine closes
         self._inflight = {}
+        self._filter = None  # the candidate filter in force (a CandFilter copy), None = none
         rc = L.pf_open(desc_ptr, device, ctypes.byref(self.h))
         if rc != PF_OK:
             raise FasError(f"pf_open failed ({rc}): {L.pf_last_error(None).decode()}")
@@ -275,9 +325,17 @@ class FasEngine:
     recommend_friends_by_interest = recommend_graph_registration
     recommend_friends_collab = recommend_collaborative
 
-    def recommend_interest_all(self, users, topk):
-        """All-candidates interest scan."""
-        return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
+    def recommend_interest_all(self, users, topk, filter=None):
+        """All-candidates interest scan.  filter (a CandFilter): rank only the candidates
+        that pass it; the filter in force before the call is restored afterwards."""
+        if filter is None:
+            return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
+        prev = self._filter
+        self.set_scan_filter(filter)
+        try:
+            return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
+        finally:
+            self.set_scan_filter(prev)
 
     def fof_candidates(self, uid, limit, flavour=PF_FOF_GRAPH):
         cap = max(int(limit), 1) + 1
@@ -300,6 +358,28 @@ class FasEngine:
     def set_scan_kernel(self, kind):
         """PF_SCAN_AUTO / PF_SCAN_STREAM (record walk, K1) / PF_SCAN_POSTINGS (K5)."""
         self._check(self._L.pf_set_scan_kernel(self.h, kind), "pf_set_scan_kernel")
+
+    # -- candidate filter of the all-candidates scans (pf_set_scan_filter): context state, read by
+    #    every recommend_interest(..., PF_MODE_ALL) and scan_keys_async launch; nothing else sees it
+    def set_scan_filter(self, filter=None, **kw):
+        """Set the filter (a CandFilter, or CandFilter.make's keyword arguments); None clears it."""
+        if filter is None and kw:
+            filter = CandFilter.make(**kw)
+        if filter is None or filter.fields == 0:
+            self._check(self._L.pf_set_scan_filter(self.h, None), "pf_set_scan_filter")
+            self._filter = None
+            return
+        self._check(self._L.pf_set_scan_filter(self.h, ctypes.byref(filter)), "pf_set_scan_filter")
+        self._filter = filter.copy()
+
+    def clear_scan_filter(self):
+        self.set_scan_filter(None)
+
+    def scan_filter_count(self):
+        """Candidates of this context's shard that pass the filter in force (all without one)."""
+        n = ctypes.c_int64()
+        self._check(self._L.pf_scan_filter_count(self.h, ctypes.byref(n)), "pf_scan_filter_count")
+        return n.value
 
     # -- device-resident scan for multi-GPU benches (device pointers and a hipStream_t
     #    handle as ints; stream 0 is the HIP null stream, exactly as given)
