@@ -242,54 +242,27 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
     return PF_OK;
 }
 
-// K5 mode word: bit 0 dynamic block hand-out (each workgroup's first block, then the next
-// unclaimed one), for one-query launches only.  r2fb A/B: 205.3 / 205.6 us vs 206.9 / 206.9 us
-// static per cfg-2 launch; batches (one block per workgroup in L2-sharing order) stay static
-// (cfg 4 9.83e9 dynamic vs 9.88e9 static).
-// K5 launch mode: bit 0 = dynamic block hand-out (one query); bit 1 = transposed grid (batches:
-// the resident workgroups are many queries on the same candidate blocks; PF_DEBUG k5_transposed=1.
-// Measured slower than the query-major grid: cfg 4 216.9 vs 203.4 ms per 1024-query launch, r4c)
-uint32_t post_mode(int nq) {
-    static const bool tr = pf::debug_long("k5_transposed", 0) != 0;
-    // A/B: static hand-out for one query, no claimed tail (takes k5_dyn=0 as well: bit 3 overrides it)
-    static const bool st = pf::debug_long("k5_static", 0) != 0;
-    // each XCD's workgroups take a contiguous range of every static round's blocks (neighbouring
-    // blocks share the cache lines at their list segments' ends); the query-major batch grid too
-    // (a query's workgroups are a multiple of 8 there, so bx mod 8 is still the XCD); k5_xcd=0 A/B
-    static const bool xcd = pf::debug_long("k5_xcd", 1) != 0;
-    // every block claimed per XCD group (default; k5_dyn=0 A/B: static rounds, the tail claimed).
-    // Neutral on an isolated launch (178.8 vs 179.2 us, r6-era), but with the scan lanes the next
-    // query's workgroups start while this one's last blocks run, so a static share of blocks
-    // waits on workgroups dispatched late: cfg 2 1.13e10 -> 1.20e10 candidates/s (r8b / r8c)
-    static const bool dyn = pf::debug_long("k5_dyn", 1) != 0;
-    const uint32_t x = xcd ? 4u : 0u;
+// K5 mode word (pf_kernels.h): flags only; the block hand-out is launch_post's `claimed`, true for
+// the one-query launches (scan_post with a batch of one, scan_post_resident) and false for batches.
+uint32_t post_mode(bool claimed) {
     // the one-query instantiation drops candidates that cannot reach the query's shared score
     // threshold (pf_prune.h): k5_prune=0 off, 1 at block starts only, 2 (default) at round ends too
     // (A/B; the results are the same bits); k5_prune_stats=1 counts them (pf_scan_prune_stats)
     static const long pr = pf::debug_long("k5_prune", 2);
     static const bool prs = pf::debug_long("k5_prune_stats", 0) != 0;
-    const uint32_t p = !dyn || pr <= 0 ? 0u : (pf::kPostPrune | (pr == 1 ? pf::kPostPruneBlockOnly : 0u) | (prs ? pf::kPostPruneStats : 0u));
+    const uint32_t p = pr <= 0 ? 0u : (pf::kPostPrune | (pr == 1 ? pf::kPostPruneBlockOnly : 0u) | (prs ? pf::kPostPruneStats : 0u));
     // filtered launches (pf_set_scan_filter): k5_filter_blockout=0 runs the blocks in which no
     // candidate passes to their end (A/B of the whole-block early-out; the results are the same bits)
     static const bool fko = pf::debug_long("k5_filter_blockout", 1) == 0;
     const uint32_t f = fko ? pf::kPostFiltKeepBlocks : 0u;
-    return (nq == 1 ? ((st ? 0u : 1u) | x | (dyn ? 8u : 0u) | p) : (tr ? 2u : x)) | f;
-}
-
-// Candidates per claimed block past a one-query K5 launch's static rounds (PF_DEBUG k5_tail=N,
-// A/B; 0 or >= the block size: whole blocks).  r6g, one box: whole blocks 177.0 us, 256 177.2,
-// 128 177.5 / 178.6, 64 180.2: the claimed tail is not where a launch loses time
-
-uint32_t tail_block_cands() {
-    static const long n = pf::debug_long("k5_tail", 0);
-    return (uint32_t)std::max(0L, n);
+    return (claimed ? p : 0u) | f;
 }
 
 // Blocks per workgroup of a batched postings scan: a workgroup stages its query's tables once
 // for them (blocks w, w + n/4, ... of one query, so the query's neighbouring blocks still run
 // side by side and share its lists in L2).  cfg 4, r2bs: 1 -> 9.36e9, 2 -> 9.62e9, 4 -> 9.87e9
-// candidates/s.  Round 4 (static block rounds with a claimed tail, the rounds table built once
-// per block): r4t/r4v, one box: 2 -> 1.07e10, 4 -> 1.11e10, 8 -> 1.14e10, 16 -> 1.162e10,
+// candidates/s.  Round 4 (static block rounds with a claimed tail, a hand-out since retired; the
+// rounds table built once per block): r4t/r4v, one box: 2 -> 1.07e10, 4 -> 1.11e10, 8 -> 1.14e10, 16 -> 1.162e10,
 // 32 -> 1.162e10, 64 -> 1.14e10, 128 -> 1.09e10.  Round 5 final tree (r8q, one box, alternating):
 // 8 -> 1.411e10, 16 -> 1.424-1.428e10, 24 -> 1.435e10, 32 -> 1.432-1.438e10.
 constexpr int kBatchBlocksPerWgDefault = 32;
@@ -303,8 +276,8 @@ int batch_blocks_per_wg() {
 uint32_t post_image_lds(const pf::QPostHead* h) {
     return pf::post_lds(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend));
 }
-int post_image_per_cu(const pf::QPostHead* h, int nq, bool filtered) {  // in a launch of nq queries
-    return pf::post_blocks_per_cu(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), post_mode(nq), filtered);
+int post_image_per_cu(const pf::QPostHead* h, bool claimed, bool filtered) {
+    return pf::post_blocks_per_cu(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), claimed, filtered);
 }
 // LDS a filtered launch takes on top of an image's (the filter's words; pf_kernels.h kFiltLds)
 uint32_t filt_lds(const pf_ctx* c) { return c->filt.fields ? pf::kFiltLds : 0u; }
@@ -438,10 +411,12 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
     // batch at one workgroup per CU
     std::vector<uint32_t> vl(nq);
     std::vector<int> pcu(nq), order(nq);
+    // the hand-out is the call's, not a launch's: a class of one query of a batch stays a batch launch
+    const bool claimed = nq == 1;
     for (int q = 0; q < nq; ++q) {
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q]->data() + sizeof(pf::QConst));
         vl[q] = pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend);
-        pcu[q] = post_image_per_cu(h, nq, c->filt.fields != 0u);
+        pcu[q] = post_image_per_cu(h, claimed, c->filt.fields != 0u);
         order[q] = q;
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pcu[a] > pcu[b]; });
@@ -514,8 +489,8 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
                                   nq == 1 ? wave_lds : vmax, q1 - q0, c->wb_begin, c->wb_end, k, blocks,
                                   part_buf.as<uint64_t>() + (size_t)q0 * (blocks + 8) * k,
                                   reinterpret_cast<pf::ScanSync*>(base + offs_b + rows_b) + q0, out_keys,
-                                  reinterpret_cast<const int32_t*>(base + offs_b) + q0, post_mode(nq),
-                                  tail_block_cands(), (timed && q0 == 0) ? e0 : nullptr,
+                                  reinterpret_cast<const int32_t*>(base + offs_b) + q0, claimed,
+                                  post_mode(claimed), (timed && q0 == 0) ? e0 : nullptr,
                                   (timed && q1 == nq) ? e1 : (ln ? ln->done : nullptr), s, nullptr, c->filt));
         q0 = q1;
     }
@@ -544,7 +519,7 @@ bool resident_ok(const pf_ctx* c, int32_t i) {
 int scan_post_resident(pf_ctx* c, int32_t i, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
     auto& R = c->rp;
     const uint32_t vl = R.var_lds[i];
-    const int per_cu = pf::post_blocks_per_cu(vl, post_mode(1), c->filt.fields != 0u);
+    const int per_cu = pf::post_blocks_per_cu(vl, true, c->filt.fields != 0u);
     const int nwb = c->wb_end - c->wb_begin;
     LaneUse lu;
     int rc = lane_begin(c, s, lu);
@@ -568,7 +543,7 @@ int scan_post_resident(pf_ctx* c, int32_t i, int32_t row, int k, uint64_t* d_key
     const uint8_t* qc = c->jb.d_pimg.as<uint8_t>() + c->jb.pimg_off[i];
     HIPCHK(c, pf::launch_post(c->ps, img, R.d_zero.as<uint32_t>(), vl, 1, c->wb_begin, c->wb_end, k, blocks,
                               part_buf.as<uint64_t>(), sync_buf.as<pf::ScanSync>(), out, R.d_zero.as<int32_t>(),
-                              post_mode(1), tail_block_cands(), timed ? e0 : nullptr, stop, ls, qc, c->filt));
+                              true, post_mode(true), timed ? e0 : nullptr, stop, ls, qc, c->filt));
     if (ln) {
         rc = lane_end(c, lu, stop, s, d_keys + (size_t)row * k, k);
         if (rc != PF_OK) return rc;
@@ -1404,7 +1379,7 @@ int pf_scan_bytes(pf_ctx* c, const int32_t* q, int32_t nq, int64_t* out) {
     }
     // workgroups that stage a query's image, as scan_post launches the fitting queries
     const int nwb = c->wb_end - c->wb_begin;
-    const int wgs = nfit == 1 ? one_query_wgs(c->num_cus * pf::post_blocks_per_cu(pf::post_var_lds(max_tok, max_lists), post_mode(1), false), true)
+    const int wgs = nfit == 1 ? one_query_wgs(c->num_cus * pf::post_blocks_per_cu(pf::post_var_lds(max_tok, max_lists), true, false), true)
                               : (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg();
     par_jobs((size_t)nq, [&](size_t i) {
         out[i] = kind[i] == 0 ? 0 : (kind[i] == 2 ? k1 : post_query_bytes(c, imgs[i], wgs));

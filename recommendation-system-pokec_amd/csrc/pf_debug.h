@@ -8,9 +8,6 @@
 //   stage_limit=BYTES     query tables above this are probed in global memory (default 49152)
 //   tile_steps=N          tile-store chunk limit in 16-B steps, splits records over lanes (48)
 //   k5_block=N            postings-scan block size in candidates (kBlockCands, 512; tests)
-//   k5_transposed=1       batched postings scans on the query-fastest grid (A/B; measured slower)
-//   k5_static=1           one-query postings scans with the static block hand-out and no claimed tail
-//                         (A/B; with k5_dyn=0: alone, every block is still claimed per XCD group)
 //   k5_batch_blocks=N     blocks per workgroup of a batched postings scan (default 32; A/B)
 //   k5_wgs=N              workgroups of a one-query postings scan (default: one resident round; on the
 //                         scan lanes 7/8 of one with 3-5 lanes, 1/2 with 6-11, 3/16 with 12-15; A/B)
@@ -18,11 +15,6 @@
 //                         default 3 (the context's stream, aux, aux2), so consecutive queries' launches
 //                         overlap; 2 leaves out aux2; 4..16 add lanes on streams of their own (for a
 //                         process with more hardware queues, GPU_MAX_HW_QUEUES)
-//   k5_dyn=0              K5: one-query launches in static block rounds, the tail claimed (A/B;
-//                         default: every block claimed per XCD group)
-//   k5_xcd=0|1            K5: contiguous block ranges per XCD in each static round (default 1; A/B)
-//   k5_tail=N             K5: candidates per claimed block past a one-query launch's static rounds
-//                         (default 0 = whole blocks; A/B)
 //   k5_prune=0|1|2        K5: one-query launches drop the candidates that cannot reach the query's shared
 //                         score threshold before their text work (pf_prune.h; the same result bits):
 //                         0 off, 1 at block starts only, 2 (default) at round ends too (A/B)

@@ -39,27 +39,28 @@ int scan_blocks_per_cu(bool packed, bool gtab, uint32_t lds);
 // offsets img_off[] into pool); var_lds = post_var_lds(max n_tok, max lists of an image)
 uint32_t post_var_lds(int n_tok, int n_lists);
 uint32_t post_lds(uint32_t var_lds);
-// tail_bs: a one-query launch's claimed blocks past its static rounds take tail_bs candidates each.
+// claimed: the block hand-out, which is the instantiation.  true (nq == 1 only): the grid's workgroups
+// claim every block per XCD group; false: workgroup x of query y takes every blocks-th block of the
+// range, in XCD-contiguous order (the batches, a class of one query of a batch included).
 // qconst: nullptr (each image starts with its QConst) or, for a one-query launch from the resident
 // images, the user's QConst elsewhere (its K1' resident image); img = the resident part's start
 // minus sizeof(QConst).  The launch leaves each query's ScanSync zeroed (post_tail).
-// mode: bits 0-3 the block hand-out (pf_api.cpp post_mode); with bit 3, kPostPrune = drop candidates
-// below the query's shared score threshold (pf_prune.h), kPostPruneBlockOnly = at block starts only,
+// mode: flags (pf_api.cpp post_mode).  Claimed launches only: kPostPrune = drop candidates below the
+// query's shared score threshold (pf_prune.h), kPostPruneBlockOnly = at block starts only,
 // kPostPruneStats = count them.  kPostFiltKeepBlocks (filtered launches, A/B): a block in which no
 // candidate passes the filter runs to its end instead of leaving after its first barrier.
 // filt (by value in the launch's arguments; fields == 0: none): the context's candidate filter
-// (pf_filter.h); a filtered launch takes the FILT instantiation of its mode.
+// (pf_filter.h); a filtered launch takes the FILT instantiation of its hand-out.
 constexpr uint32_t kPostPrune = 1u << 16, kPostPruneStats = 1u << 17, kPostPruneBlockOnly = 1u << 18;
 constexpr uint32_t kPostFiltKeepBlocks = 1u << 19;
 // dynamic LDS a filtered launch takes on top of post_lds(var_lds): the filter, parked past the query's tables
 constexpr uint32_t kFiltLds = (uint32_t)sizeof(CandFilter);
 hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t* img_off, uint32_t var_lds, int nq,
                        int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
-                       const int32_t* out_rows, uint32_t mode, uint32_t tail_bs, hipEvent_t e0, hipEvent_t e1,
+                       const int32_t* out_rows, bool claimed, uint32_t mode, hipEvent_t e0, hipEvent_t e1,
                        hipStream_t s, const uint8_t* qconst, const CandFilter& filt);
-// workgroups per CU of the instantiation launch_post takes for `mode` (bit 3: the one-query claimed
-// one) and `filtered` (a filter is set)
-int post_blocks_per_cu(uint32_t var_lds, uint32_t mode, bool filtered);
+// workgroups per CU of the instantiation launch_post takes for `claimed` and `filtered` (a filter is set)
+int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered);
 // candidates of idx range [i0, i1) of the postings headers (ps.hdr), or with ps.hdr null of slots
 // [i0, i1) of the tile headers, that pass filt: added to *count (device, zeroed by the caller)
 hipError_t launch_filter_count(const PostStore& ps, const DevStore& st, int32_t i0, int32_t i1, const CandFilter& filt,

@@ -1315,12 +1315,12 @@ static __device__ __attribute__((noinline)) uint32_t prune_derive(ScanSync* sy, 
 #ifndef PF_K5_MINB
 #define PF_K5_MINB 4  // workgroups per CU the register budget is sized for (LDS allows 4 for most queries)
 #endif
-// XD: the one-query launch with every block claimed per XCD group (mode bit 3; launch_post picks
-// the instantiation).  The mode booleans below are constants there, so the transposed grid, the
-// static hand-out, the finer claimed tail and their scalars fold away; <false> serves the batches
-// and the one-query launches without bit 3 (k5_dyn=0: static rounds, with the tail claimed from
-// the query's counter unless k5_static=1, in k5_tail's finer blocks) and never claims per group.
-// (k5_static=1 alone leaves bit 3 set: such a launch is still <true>'s, the flag without effect)
+// XD: how the launch's blocks (B = ps.bsize candidates each) are handed out; launch_post's caller
+// picks the instantiation (`claimed`).
+//   <true>  the one-query launch (grid x = workgroups): every block is claimed per XCD group.
+//   <false> the batches (grid = workgroups x queries): a static stride, workgroup bx takes blocks
+//           pb, pb + nbx, ... of its query, pb = bx in XCD-contiguous order.
+// The pruning bound and its counters are <true>'s alone.
 // FILT: the context has a candidate filter (pf_filter.h, F; launch_post picks the instantiation): a
 // candidate whose header fails it is dropped like an excluded one, a block in which nobody passes
 // is left after its first barrier.  <XD, false> never reads F and is the code it was without it.
@@ -1330,16 +1330,11 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                                                               int32_t blk_end, int32_t k, uint64_t* __restrict__ parts,
                                                               ScanSync* __restrict__ sync, uint64_t* __restrict__ out,
                                                               const int32_t* __restrict__ out_rows, uint32_t mode,
-                                                              uint32_t tail_bs, const uint8_t* __restrict__ qconst,
-                                                              CandFilter F) {
+                                                              const uint8_t* __restrict__ qconst, CandFilter F) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // mode bit 1 (batches): the grid is transposed, blockIdx.x = the query and blockIdx.y = the block
-    // group, so the workgroups resident at once are many queries on the same candidate blocks and
-    // the lists they share (popular tokens, clubs) are read from HBM once and then served by L2
-    const bool tr = !XD && (mode & 2u) != 0u;
-    const int qy = XD ? 0 : tr ? (int)blockIdx.x : (int)blockIdx.y;
-    const int bx = tr ? (int)blockIdx.y : (int)blockIdx.x;
-    const int nbx = tr ? (int)gridDim.y : (int)gridDim.x;
+    const int qy = XD ? 0 : (int)blockIdx.y;
+    const int bx = (int)blockIdx.x;
+    const int nbx = (int)gridDim.x;
     const uint8_t* img = pool + img_off[qy];
     // the query's QConst: the image's own prefix, or (qconst given: one-query launches from the
     // resident images) the job pipeline's resident K1' image of the same user, whose QConst K6
@@ -1429,47 +1424,45 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     uint64_t tprev = clock64();
     const uint64_t tstart = tprev;
 #endif
-    // Blocks: the workgroup's own first block, then either every gridDim.x-th block (static)
-    // or (mode bit 0) the next unclaimed block of the query from a counter in its ScanSync, so the
-    // blocks past the first resident round go to the workgroups that finish first.
-    unsigned int* next_blk = &sync[qy].next;
-    // dynamic mode (one query): whole static rounds of nbx blocks, then the rest of the range by
-    // claim, in blocks of tail_bs candidates: the ~117 blocks past three static rounds of a cfg-2
-    // launch would run on ~11 % of the workgroups; cut four times finer they spread over ~470
-    const int tail = XD ? blk_end : (mode & 1u) ? blk_begin + max(1, (blk_end - blk_begin) / nbx) * nbx : blk_end;
     const uint32_t B = (uint32_t)ps.bsize;
     const uint32_t cend = min((uint32_t)blk_end * B, (uint32_t)ps.n);  // the range's end
-    // (mode bit 3 counts every block in whole B-candidate blocks: finer tail blocks apply to the
-    // static-rounds mode only)
-    const uint32_t tbs = (!XD && tail_bs > 0u && tail_bs < B && !(mode & 8u)) ? tail_bs : B;
-    const uint32_t cst = min((uint32_t)tail * B, cend);                 // the claimed part's start
-    int blk_last = tail + (int)((cend - cst + tbs - 1) / tbs);
     const bool short_excl = H.n_excl <= kPostThreads;
     const uint32_t ex0 = short_excl && H.n_excl > 0 ? excl[min(tid, H.n_excl - 1)] : ~0u;  // the query's, once
-    // mode bit 2 (one query, query-major batches): the workgroups of XCD x (bx mod 8 under the
+    // <false>: blocks pb, pb + nbx, ... of the query.  The workgroups of XCD x (bx mod 8 under the
     // round-robin dispatch when nbx is a multiple of 8) take blocks [x nbx/8, (x + 1) nbx/8) of each
-    // static round, so a list segment's boundary cache lines are shared inside one L2 instead of
+    // stride round, so a list segment's boundary cache lines are shared inside one L2 instead of
     // fetched by two XCDs (cfg 2 PMC traffic 236 -> 175 MB per launch, r4w -> r5h)
-    const int pb = ((mode & 4u) && (nbx & 7) == 0) ? (bx & 7) * (nbx >> 3) + (bx >> 3) : bx;
-    // mode bit 3 (one query): every block claimed, per group g = bx mod 8 (with round-robin dispatch,
-    // one XCD) from a contiguous eighth of the range, in order, from the group's own counter.  The
-    // workgroups dispatched last (the third and fourth of a CU) lose VALU arbitration to the older
-    // ones by age and ran their static blocks ~25 % slower every round (r6j block log): claimed
-    // blocks let the faster workgroups take more.  The next block is claimed at the start of a
-    // block's last text round, so the claim's round trip hides behind that round.
-    const bool xdyn = XD;
+    const int pb = (nbx & 7) == 0 ? (bx & 7) * (nbx >> 3) + (bx >> 3) : bx;
+    // <true>: every block claimed, per group g = bx mod 8 (with round-robin dispatch, one XCD) from
+    // a contiguous eighth of the range, in order, from the group's own counter.  The workgroups
+    // dispatched last (the third and fourth of a CU) lose VALU arbitration to the older ones by age
+    // and ran a static share of blocks ~25 % slower every round (r6j block log): claimed blocks let
+    // the faster workgroups take more.  The next block is claimed at the start of a block's last
+    // text round, so the claim's round trip hides behind that round.
     const int xng = min(8, nbx), xg = bx % xng;
     const int x_lo = blk_begin + (int)((int64_t)(blk_end - blk_begin) * xg / xng);
     const int x_hi = blk_begin + (int)((int64_t)(blk_end - blk_begin) * (xg + 1) / xng);
     const int x_nwg = (nbx - xg + xng - 1) / xng;
     unsigned int* xctr = &sync[qy].xcd_next[xg * 16];
-    if (xdyn) blk_last = x_hi;
-    for (int blk = xdyn ? x_lo + bx / xng : blk_begin + pb; blk < blk_last;) {
+    const int blk_last = XD ? x_hi : blk_end;
+    for (int blk = XD ? x_lo + bx / xng : blk_begin + pb; blk < blk_last;) {
         unsigned int xclaim = 0;
-        const bool whole = XD || blk < tail;
-        const uint32_t bsz = whole ? B : tbs;  // this block's candidates
-        const uint32_t c0 = whole ? (uint32_t)blk * B : cst + (uint32_t)(blk - tail) * tbs;
-        const uint32_t c1 = min(c0 + bsz, cend) - 1;  // last candidate of the block
+        // The next block, behind a barrier (the next block rewrites the exclusion bits the owners
+        // read in this one).  <true>: thread 0 publishes the group's next claim through misc[0],
+        // the one fetched at the start of the last text round (xclaim) or, `now`, one taken on the
+        // spot; <false>: the stride.
+        auto next_block = [&](bool now) __attribute__((always_inline)) {
+            if constexpr (XD) {
+                if (tid == 0) misc[0] = (uint32_t)(x_lo + x_nwg) + (now ? atomicAdd(xctr, 1u) : xclaim);
+                __syncthreads();
+                blk = (int)misc[0];
+            } else {
+                __syncthreads();
+                blk += nbx;
+            }
+        };
+        const uint32_t c0 = (uint32_t)blk * B;
+        const uint32_t c1 = min(c0 + B, cend) - 1;  // last candidate of the block
 #ifdef PF_K5_BLOCKLOG
         const unsigned long long blog_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1493,7 +1486,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
 #pragma unroll
         for (int kk = 0; kk < kCandsPerThread; ++kk) {
             const uint32_t c = c0 + kk * kPostThreads + tid;
-            if (!(c <= c1 && (uint32_t)(kk * kPostThreads + tid) < bsz)) {
+            if (!(c <= c1 && (uint32_t)(kk * kPostThreads + tid) < B)) {
                 ha[kk] = make_uint4(0, 0, 0, 0);
                 hb[kk] = make_uint4(0, 0, 0, 0);
             }
@@ -1511,7 +1504,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
             const CandFilter f = *fl;  // (published by the staging barrier before the block loop)
 #pragma unroll
             for (int kk = 0; kk < kCandsPerThread; ++kk) {
-                const bool there = c0 + kk * kPostThreads + tid <= c1 && (uint32_t)(kk * kPostThreads + tid) < bsz;
+                const bool there = c0 + kk * kPostThreads + tid <= c1 && (uint32_t)(kk * kPostThreads + tid) < B;
                 const bool ok = filter_pass_post(f, ha[kk], hb[kk]);
                 if (there && !ok) fskip |= 1u << kk;
                 any |= there && ok;
@@ -1522,19 +1515,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                     misc[11] += 1u;
                     misc[12] += thb == 0u ? 1u : 0u;
                 }
-                // the next block, as at the loop's end
-                if (xdyn) {
-                    if (tid == 0) misc[0] = (uint32_t)(x_lo + x_nwg) + atomicAdd(xctr, 1u);
-                    __syncthreads();
-                    blk = (int)misc[0];
-                } else if ((mode & 1u) && blk + nbx >= tail) {
-                    if (tid == 0) misc[0] = (uint32_t)tail + atomicAdd(next_blk, 1u);
-                    __syncthreads();
-                    blk = (int)misc[0];
-                } else {
-                    __syncthreads();
-                    blk += nbx;
-                }
+                next_block(true);  // nothing of this block was claimed ahead
                 continue;
             }
             // a candidate that fails is marked like an excluded one (the bits were zeroed before the
@@ -1589,7 +1570,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         // barrier of its own), else bisect and walk until past the block
         if (short_excl) {
             const uint32_t p = ex0 - c0;
-            if (tid < H.n_excl && p < bsz) atomicOr(&exb[p >> 5], 1u << (p & 31));
+            if (tid < H.n_excl && p < B) atomicOr(&exb[p >> 5], 1u << (p & 31));
         } else {
             uint32_t lo = 0, hi = (uint32_t)H.n_excl;
             while (lo < hi) {  // first entry >= c0
@@ -1601,8 +1582,8 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 const uint32_t x = b + tid;
                 const uint32_t e = x < hi ? excl[x] : ~0u;
                 const uint32_t p = e - c0;
-                if (p < bsz) atomicOr(&exb[p >> 5], 1u << (p & 31));
-                if (__syncthreads_or(e >= c0 + bsz)) break;  // sorted: the rest lies beyond the block
+                if (p < B) atomicOr(&exb[p >> 5], 1u << (p & 31));
+                if (__syncthreads_or(e >= c0 + B)) break;  // sorted: the rest lies beyond the block
             }
         }
         // 2. clubs / friends, by waves 1-3 while wave 0 plans the rounds: each computes the set
@@ -1626,7 +1607,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const uint32_t p = (e[u] >> 8) - c0;
-                    if (js[u] >= 0 && p < bsz) atomicAdd(&cnt[p], (e[u] & 0xFFu) << (js[u] < H.n_club ? 0 : 16));
+                    if (js[u] >= 0 && p < B) atomicAdd(&cnt[p], (e[u] & 0xFFu) << (js[u] < H.n_club ? 0 : 16));
                 }
             }
         }
@@ -1642,7 +1623,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         for (int kk = 0; kk < kCandsPerThread; ++kk) {
             const int p = kk * kPostThreads + tid;
             const uint32_t ct = cnt[p];
-            if ((uint32_t)p >= bsz || c0 + p > c1 || ((exb[p >> 5] >> (p & 31)) & 1u)) skip |= 1u << kk;
+            if ((uint32_t)p >= B || c0 + p > c1 || ((exb[p >> 5] >> (p & 31)) & 1u)) skip |= 1u << kk;
             const uint64_t cm = (uint64_t)ha[kk].x | ((uint64_t)(ha[kk].y & 0xFFFFu) << 32);
             pend[kk] = cm & q.colmask;
             double s = 0.0;
@@ -1680,7 +1661,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 }
                 if (pstats) {  // (counted in LDS as they come: no register lives through the block loop for them)
                     const int p = kk * kPostThreads + tid;
-                    const uint64_t bs = __ballot((uint32_t)p < bsz && c0 + p <= c1), bd = __ballot(d);
+                    const uint64_t bs = __ballot((uint32_t)p < B && c0 + p <= c1), bd = __ballot(d);
                     if (lane == 0) {
                         atomicAdd(&misc[8], (uint32_t)__popcll(bs));
                         atomicAdd(&misc[9], (uint32_t)__popcll(bd));
@@ -1699,9 +1680,9 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
 #pragma unroll
         for (int kk = 0; kk < kCandsPerThread; ++kk) { cdot[kk] = 0.0; cnrm[kk] = 0.0; }
         int nrounds = (int)misc[3];  // written before the barrier above
-        if (xdyn && nrounds == 0 && tid == 0) xclaim = atomicAdd(xctr, 1u);
+        if (XD && nrounds == 0 && tid == 0) xclaim = atomicAdd(xctr, 1u);
         for (int rnd = 0; rnd < nrounds; ++rnd) {
-            if (xdyn && rnd == nrounds - 1 && tid == 0) xclaim = atomicAdd(xctr, 1u);
+            if (XD && rnd == nrounds - 1 && tid == 0) xclaim = atomicAdd(xctr, 1u);
             const uint2 rr = rtab[rnd];
             Round R;
             R.ja = (int)(rr.x & 0xFFFFu);
@@ -1763,7 +1744,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                     for (int u = 0; u < U; ++u) {
                         const uint32_t p = (ent[u] >> 8) - c0;
                         kp[u] = ~0u;
-                        if (js[u] >= 0 && p < bsz) {
+                        if (js[u] >= 0 && p < B) {
                             const uint32_t jr = (uint32_t)(js[u] - ja);
                             kp[u] = p | jr << 10 | (ent[u] & 0xFFu) << 16;
                             atomicOr(reinterpret_cast<unsigned long long*>(&mask[p]), 1ull << jr);
@@ -1773,7 +1754,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 for (uint32_t f = (uint32_t)(tid + kRoundCap); f < F; f += kPostThreads) {  // one-token rounds past the cap
                     const int j = round_list(gpre, ja, jb, g0 + f);
                     const uint32_t p = (ps.post[K5CHK(rng[j].x + (g0 + f - gpre[j]), ps.n_tok_entries, 6)] >> 8) - c0;
-                    if (p < bsz) atomicOr(reinterpret_cast<unsigned long long*>(&mask[p]), 1ull << (j - ja));
+                    if (p < B) atomicOr(reinterpret_cast<unsigned long long*>(&mask[p]), 1ull << (j - ja));
                 }
                 K5T(4);
                 __syncthreads();
@@ -1836,7 +1817,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                     const uint32_t x = K5CHK(rng[j].x + (g0 + f - gpre[j]), ps.n_tok_entries, 7);
                     const uint32_t e = ps.post[x];
                     const uint32_t p = (e >> 8) - c0;
-                    if (p >= bsz) continue;
+                    if (p >= B) continue;
                     const uint32_t jr = (uint32_t)(j - ja);
                     if (drop && !((mask[p] >> jr) & 1ull)) continue;  // a dropped candidate's
                     const uint64_t below = mask[p] & low_bits(jr);
@@ -2010,22 +1991,7 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
             }
         }
 #endif
-        if (xdyn) {
-            if (tid == 0) misc[0] = (uint32_t)(x_lo + x_nwg) + xclaim;
-            __syncthreads();
-            blk = (int)misc[0];
-        } else if ((mode & 1u) && blk + nbx >= tail) {
-            // the tail past the static rounds from the query's counter: one claim per workgroup
-            // (every workgroup claiming every block serialised ~3,000 atomics on one address).
-            // misc[0] was last read before this block's first barrier; claimed here, not at the
-            // block's start: an early claim measured 190 -> 200 us (r4i)
-            if (tid == 0) misc[0] = (uint32_t)tail + atomicAdd(next_blk, 1u);
-            __syncthreads();
-            blk = (int)misc[0];
-        } else {
-            __syncthreads();  // the next block rewrites the exclusion bits the owners read above
-            blk += nbx;
-        }
+        next_block(false);
     }
 #ifdef PF_K5_TIMERS
     tacc[13] = clock64() - tstart;
@@ -2231,8 +2197,9 @@ uint32_t post_var_lds(int n_tok, int n_lists) {
 uint32_t post_lds(uint32_t var_lds) { return (uint32_t)sizeof(QConst) + kPostFixedLds + var_lds; }
 
 #ifdef PF_K5_BLOCKLOG
-// per-block times of one launch: the span, and per static round (blk / nbx) the blocks' start and
-// end offsets and durations (us, from the launch's first block start)
+// per-block times of one launch: the span, and per nbx consecutive blocks (blk / nbx: one-query
+// launches claim their blocks, so these are ranges of the block index, not rounds in time) the
+// blocks' start and end offsets and durations (us, from the launch's first block start)
 static void blog_report(int nbx) {
     static unsigned long long t[2 * kBlogCap];
     static unsigned int meta[kBlogCap];
@@ -2276,20 +2243,20 @@ static void blog_report(int nbx) {
 
 hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t* img_off, uint32_t var_lds, int nq,
                        int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
-                       const int32_t* out_rows, uint32_t mode, uint32_t tail_bs, hipEvent_t e0, hipEvent_t e1,
+                       const int32_t* out_rows, bool claimed, uint32_t mode, hipEvent_t e0, hipEvent_t e1,
                        hipStream_t s, const uint8_t* qconst, const CandFilter& filt) {
     if (nq <= 0) return hipSuccess;
+    // the claimed hand-out is the one-query instantiation's and nobody else's
+    if (claimed && nq != 1) return hipErrorInvalidValue;
     // timed launches (e0, e1 given): the kernel's own start and end timestamps, taken from its
     // dispatch (hipExtLaunchKernelGGL), instead of two marker packets around it
-    const dim3 grid = (mode & 2u) ? dim3(nq, blocks) : dim3(blocks, nq);
-    // mode bit 3 (every block claimed) is the one-query instantiation's and nobody else's
-    if ((mode & 8u) && (nq != 1 || (mode & 2u))) return hipErrorInvalidValue;
+    const dim3 grid(blocks, nq);
 #define PF_POST(XD, FILT) hipExtLaunchKernelGGL((fas_post_kernel<XD, FILT>), grid, dim3(kPostThreads), lds, s, e0, e1, 0u, ps, \
-                                                pool, img_off, blk_begin, blk_end, k, parts, sync, out, out_rows, mode, tail_bs, qconst, filt)
+                                                pool, img_off, blk_begin, blk_end, k, parts, sync, out, out_rows, mode, qconst, filt)
     const uint32_t lds = post_lds(var_lds) + (filt.fields ? kFiltLds : 0u);  // + the filter's words (fas_post_kernel)
     // the filter travels in the launch's own arguments: a later pf_set_scan_filter does not reach it
-    if (filt.fields) { if (mode & 8u) PF_POST(true, true); else PF_POST(false, true); }
-    else { if (mode & 8u) PF_POST(true, false); else PF_POST(false, false); }
+    if (filt.fields) { if (claimed) PF_POST(true, true); else PF_POST(false, true); }
+    else { if (claimed) PF_POST(true, false); else PF_POST(false, false); }
 #undef PF_POST
 #ifdef PF_K5_BLOCKLOG
     {
@@ -2331,21 +2298,20 @@ hipError_t k5_prune_stats_read(unsigned long long* out, bool reset) {
     return e;
 }
 
-int post_blocks_per_cu(uint32_t var_lds, uint32_t mode, bool filtered) {
-    // per thread, by instantiation (the one launch_post takes for this mode and filter) and LDS bytes
-    // (a batch asks once per query: the occupancy API once per size)
-    const bool xd = (mode & 8u) != 0u;
+int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered) {
+    // per thread, by instantiation (the one launch_post takes for `claimed` and the filter) and LDS
+    // bytes (a batch asks once per query: the occupancy API once per size)
     static thread_local std::unordered_map<uint32_t, int> memos[4];
-    auto& memo = memos[2 * (int)filtered + (int)xd];
+    auto& memo = memos[2 * (int)filtered + (int)claimed];
     auto it = memo.find(var_lds);
     if (it != memo.end()) return it->second;
     int nb = 0;
     const size_t lds = post_lds(var_lds) + (filtered ? kFiltLds : 0u);
     hipError_t e;
-    if (filtered) e = xd ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true, true>, kPostThreads, lds)
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false, true>, kPostThreads, lds);
-    else e = xd ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true, false>, kPostThreads, lds)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false, false>, kPostThreads, lds);
+    if (filtered) e = claimed ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true, true>, kPostThreads, lds)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false, true>, kPostThreads, lds);
+    else e = claimed ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true, false>, kPostThreads, lds)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false, false>, kPostThreads, lds);
     nb = (e == hipSuccess && nb > 0) ? nb : 1;
     if (memo.size() > 4096) memo.clear();
     memo.emplace(var_lds, nb);

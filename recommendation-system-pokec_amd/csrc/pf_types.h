@@ -143,15 +143,12 @@ struct QImageRef {
     uint32_t lds_bytes;   // bytes of keys+vals staged in LDS (0 = probe global memory)
 };
 
-// Per-query rendezvous of one scan launch: blocks finished, K5's block hand-out counter,
-// and the tail tile counters.  Zeroed by the host before every launch (it rides in the
-// query upload).
+// Per-query rendezvous of one scan launch: blocks finished and the per-XCD hand-out counters.
+// Zeroed by the host before every launch (it rides in the query upload).
 struct ScanSync {
     unsigned int done;
     unsigned int pad0[15];
-    unsigned int next;  // K5 dynamic hand-out: blocks claimed past the first gridDim.x, 64 B from done
-    unsigned int pad[15];
-    unsigned int xcd_next[8 * 16];  // tail tile counter per XCD, 64 B apart
+    unsigned int xcd_next[8 * 16];  // K1: tail tile counter, K5: claimed blocks, per XCD group, 64 B apart
     unsigned int grp[8 * 16];       // K5's group tickets (post_tail), 64 B apart
     // K5's pruning threshold (pf_prune.h): the float bits of theta, only ever raised, and the
     // score histogram it is derived from (kPruneBins bins, padded to whole 16-B lines)

@@ -1,9 +1,10 @@
 """Child process of test_gpu_k5_modes: the engine reads PF_DEBUG once per process, so each launch
-shape (k5_wgs, k5_block, k5_static) runs in its own.  On the edge corpus "E" and its first 2, 511,
-512, 513 and 1025 users, the same queries go through K5's one-query instantiation on the scan lanes
-(one query per call on a caller's stream) and on the context's own stream (a one-query call),
-through the generic instantiation (2-query batches; under k5_dyn=0 the one-query calls too: the
-static rounds, the claimed tail, k5_tail's finer tail blocks) and through K1 (the record walk); every list must carry the same ids and the same float32 bits.
+shape (k5_wgs, k5_block, k5_batch_blocks) runs in its own.  On the edge corpus "E" and its first 2,
+511, 512, 513 and 1025 users, the same queries go through K5's one-query instantiation (every block
+claimed) on the scan lanes (one query per call on a caller's stream) and on the context's own stream
+(a one-query call), through the batch instantiation (2-query batches: the static stride, with
+k5_batch_blocks and k5_block several workgroups of several blocks each) and through K1 (the record
+walk); every list must carry the same ids and the same float32 bits.
 Exits non-zero on any mismatch."""
 import sys
 import tempfile

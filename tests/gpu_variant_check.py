@@ -1,5 +1,5 @@
 """Child process of test_gpu_parity.test_kernel_variants: the engine reads PF_DEBUG's
-stage_limit, tile_steps, scan, k5_block, k5_wgs and resident_images once per process/context, so each
+stage_limit, tile_steps, scan, k5_block, k5_wgs, k5_batch_blocks and resident_images once per process/context, so each
 forced kernel variant (global-memory query tables, records split over lanes, postings block sizes,
 few workgroups per one-query launch, per-call query images, a variant library via PF_LIB_PATH) runs
 in its own process.  Besides the batched calls, every query is also scanned alone on a caller's

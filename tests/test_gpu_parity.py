@@ -393,14 +393,14 @@ def test_big_top64_vs_oracle(big, kernel):
                                  {"PF_DEBUG": "scan=postings"},
                                  {"PF_DEBUG": "scan=postings,k5_block=64"},
                                  {"PF_DEBUG": "scan=postings,k5_block=333"},
-                                 {"PF_DEBUG": "scan=postings,k5_static=1,k5_transposed=1"},
+                                 {"PF_DEBUG": "scan=postings,k5_batch_blocks=5"},
                                  {"PF_DEBUG": "resident_images=0"},
                                  {"PF_DEBUG": "scan=postings,k5_wgs=16"},
                                  {"PF_DEBUG": "scan=postings,k5_wgs=40"},
                                  {"PF_LIB_PATH": "variants/ticket1/libpokec_fas.so"},
                                  {"GPU_MAX_HW_QUEUES": "16", "PF_DEBUG": "scan_lanes=15"}],
                          ids=["global-tables", "threshold-1k", "split-records", "split-records-global", "postings",
-                              "postings-block64", "postings-block333", "postings-static-transposed",
+                              "postings-block64", "postings-block333", "postings-batch-5-blocks",
                               "per-call-images", "postings-16wg-claims", "postings-40wg-claims",
                               "ticket-mode-1", "hw-queues-16"])
 def test_kernel_variants(env):
@@ -408,7 +408,8 @@ def test_kernel_variants(env):
     query of the batch has tables above 1 KiB (the whole launch then probes global);
     records split over up to 64 lanes (tiles capped at 3 or 1 steps); one-query K5 launches of 16
     or 40 workgroups, so every workgroup claims several blocks from its XCD group's counter (the
-    20k corpus has 40 blocks); the library built with PF_TICKET_MODE 1 (release tickets and the
+    20k corpus has 40 blocks); batches of 5 blocks per workgroup, so an 8-query batch runs 8
+    workgroups per query in the XCD-contiguous order, 5 stride rounds each; the library built with PF_TICKET_MODE 1 (release tickets and the
     acquire fence: the memory-model-ordered cross-workgroup hand-off, pf_device.h); 16 hardware
     queues with 15 scan lanes (streams of their own, launches of 3/16 of a round each)."""
     import os
@@ -830,7 +831,7 @@ def test_full_size_kernels_agree(full):
 def test_full_size_single_query_lanes(full):
     """The exact launch bench.py times for cfg 2 (BASELINE configs[1]) at full size: one query per
     pf_scan_keys_async call on a caller's stream (bench.py `step`), so every launch runs on the scan
-    lanes in post_mode(1) with its 3,189 blocks claimed per XCD group by ~1,024 workgroups, half of
+    lanes on the claimed instantiation with its 3,189 blocks claimed per XCD group by ~1,024 workgroups, half of
     them with the bench's HIP events.  The bench's own seeded query stream (seed 2); every row equals
     the record-stream scan K1 (an independent kernel) on the same queries, ids and score bits, and
     two rows equal the oracle (the reference algorithm, recommender_graph.cpp:46-52,97-101)."""

@@ -16,7 +16,7 @@
 #   pmc:NAME:C1,C2..  one rocprofv3 --pmc pass over a 20-step cfg-2 run -> pmc_NAME/
 #   ab:W:N:R:A/B  alternating A/B bench lines (replaces the per-run tools/r*.sh scripts of rounds 4-5):
 #                 workload W (cfg2..cfg5), N timed steps, R pairs; A and B are each "-" (the default
-#                 tree), a PF_DEBUG setting (e.g. k5_dyn=0), or lib=V (the variant library vlib/V);
+#                 tree), a PF_DEBUG setting (e.g. k5_prune=0), or lib=V (the variant library vlib/V);
 #                 every line appended to ab_W.txt as "A|B <json>"
 #   trace:N       rocprofv3 kernel trace (csv, no stats) of an N-step cfg-2 run -> trace/
 set -o pipefail
