@@ -40,7 +40,8 @@
 //     profiles after construction.
 //   - profile_similarity(A, B[, text_columns]) scores two profiles OF THE MAP (by user_id), which
 //     is how every reference caller uses it.  It returns NaN otherwise.  A text_columns list other
-//     than set_text_columns' uses the engine for that list.
+//     than set_text_columns' uses the engine for that list; a proper prefix of set_text_columns'
+//     list is scored on the one engine through a field selection (no second engine is opened).
 //   - The legacy user_feats constructor and recommend_from_supernodes
 //     (recommender_clubs.cpp:75-...) are not provided: no live caller uses them
 //     (SURVEY.md §8 A12).
@@ -113,6 +114,23 @@ struct CandidateFilter {
     }
 };
 
+// Which fields FAS is computed over (pokec_fas.h pf_field_select): `fixed` bit k = PF_F_* (public,
+// gender, completion, age, region, clubs, friends), `cols` bit t = column t of set_text_columns'
+// list (bits past the list are ignored).  A deselected fixed field counts as missing on the user's
+// side; the denominator is 7 + (selected columns), the reference's own for that column list, so
+// scores under different selections are not comparable with each other.
+struct FieldSelect {
+    uint32_t fixed = PF_SEL_FIXED_ALL;
+    uint64_t cols = ~0ull;
+
+    pf_field_select c_form() const {
+        pf_field_select s{};
+        s.fixed = fixed;
+        s.cols = cols;
+        return s;
+    }
+};
+
 namespace detail {
 
 // One engine context and the adjacency rows it currently holds.
@@ -121,6 +139,8 @@ struct Engine {
     std::mutex mu;  // pokec_fas.h: calls on one context are serialised
     AdjMap rows;    // the engine's adj_list (the open-time rows plus every pf_set_adj since)
     pf_cand_filter scan_filter{};  // the scan filter in force between calls (fields == 0: none)
+    pf_field_select scan_select{};  // the scan selection in force between calls, when has_scan_select
+    bool has_scan_select = false;
     int64_t n_users = 0, n_club_entries = 0;
     Engine() = default;
     Engine(const Engine&) = delete;
@@ -258,6 +278,17 @@ public:
         const pf_cand_filter f = filter.c_form();
         return run_(3, user, topk, 0, &f);
     }
+    // The same scored over the selected fields only ("similar in what respect"); the engine's
+    // selection (and filter) are set for this call and put back afterwards, under the engine's lock.
+    Ranked recommend_interest_all(int user, int topk, const FieldSelect& select) const {
+        const pf_field_select s = select.c_form();
+        return run_(3, user, topk, 0, nullptr, &s);
+    }
+    Ranked recommend_interest_all(int user, int topk, const FieldSelect& select, const CandidateFilter& filter) const {
+        const pf_cand_filter f = filter.c_form();
+        const pf_field_select s = select.c_form();
+        return run_(3, user, topk, 0, &f, &s);
+    }
 
     // recommender_similarity.cpp:10-124,126-128, for two profiles of the map
     float profile_similarity(const Profile& A, const Profile& B) const {
@@ -266,9 +297,22 @@ public:
     // recommender_similarity.cpp:10-124 over a caller-given column list (include/recommender.h:41):
     // its names pick the normalisers and idf maps, its length the columns compared and F's
     // denominator.
+    // A proper prefix of set_text_columns' list (the only other list whose position t reads
+    // token_cols[t] of the same column) is a selection of the first columns on the one engine.
     float profile_similarity(const Profile& A, const Profile& B, const std::vector<std::string>& text_columns) const {
         if (text_columns == text_columns_internal_) return profile_similarity(A, B);
+        if (text_columns.size() < text_columns_internal_.size() && text_columns_internal_.size() <= 64 &&
+            std::equal(text_columns.begin(), text_columns.end(), text_columns_internal_.begin())) {
+            FieldSelect s;
+            s.cols = ((uint64_t)1 << text_columns.size()) - 1;  // (size < 64 here)
+            return profile_similarity(A, B, s);
+        }
         return pair_(open_for_(text_columns), A.user_id, B.user_id);
+    }
+    // FAS over the selected fields only, for two profiles of the map (pf_fas_pairs_select)
+    float profile_similarity(const Profile& A, const Profile& B, const FieldSelect& select) const {
+        const pf_field_select s = select.c_form();
+        return pair_(engine_(), A.user_id, B.user_id, &s);
     }
 
     // Push adj_list row `uid` to the engine now.  Never needed for correctness (every call
@@ -298,7 +342,8 @@ public:
     size_t total_users = 0;
 
 private:
-    Ranked run_(int kind, int user, int topk, int limit, const pf_cand_filter* filter = nullptr) const {
+    Ranked run_(int kind, int user, int topk, int limit, const pf_cand_filter* filter = nullptr,
+                const pf_field_select* select = nullptr) const {
         Ranked out;
         if (!profiles || !adj_list || topk <= 0) return out;
         std::shared_ptr<detail::Engine> e = engine_();
@@ -324,9 +369,14 @@ private:
             case 2: rc = pf_recommend_clubs(e->ctx, &q, 1, topk, limit, ids.data(), sc.data(), &n); break;
             default:
                 if (filter) rc = pf_set_scan_filter(e->ctx, filter);
+                if (select && rc == PF_OK) rc = pf_set_scan_select(e->ctx, select);
                 if (rc == PF_OK) rc = pf_recommend_interest(e->ctx, &q, 1, topk, PF_MODE_ALL, 0, ids.data(), sc.data(), &n);
                 if (filter) {  // the filter in force before the call
                     const int rr = pf_set_scan_filter(e->ctx, e->scan_filter.fields ? &e->scan_filter : nullptr);
+                    if (rc == PF_OK) rc = rr;
+                }
+                if (select) {  // and the selection
+                    const int rr = pf_set_scan_select(e->ctx, e->has_scan_select ? &e->scan_select : nullptr);
                     if (rc == PF_OK) rc = rr;
                 }
                 break;
@@ -337,13 +387,13 @@ private:
         return out;
     }
 
-    float pair_(const std::shared_ptr<detail::Engine>& e, int a, int b) const {
+    float pair_(const std::shared_ptr<detail::Engine>& e, int a, int b, const pf_field_select* select = nullptr) const {
         if (!e) return NAN;
         std::lock_guard<std::mutex> g(e->mu);
         const int32_t x = a, y = b;
         float out = NAN;
-        if (pf_fas_pairs(e->ctx, &x, &y, 1, &out) != PF_OK) return NAN;
-        return out;
+        const int rc = select ? pf_fas_pairs_select(e->ctx, &x, &y, 1, select, &out) : pf_fas_pairs(e->ctx, &x, &y, 1, &out);
+        return rc == PF_OK ? out : NAN;
     }
 
     Ranked fail_(pf_ctx* c, Ranked& out) const {

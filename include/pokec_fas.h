@@ -256,6 +256,36 @@ int pf_set_scan_filter(pf_ctx* ctx, const pf_cand_filter* filter);
 int pf_scan_filter_count(pf_ctx* ctx, int64_t* n);
 
 /*
+ * Field selection of the all-candidates scans: "similar in what respect".  A selection is a set
+ * of FAS's fixed fields (bit k of `fixed` = PF_F_*: public .. friends) and a set of text columns
+ * (bit t of `cols` = column t of the engine's list).  FAS(A, B | selection) is
+ * profile_similarity(A, B, the selected columns in ascending index) with every deselected fixed
+ * field treated as missing on the query's side (public / gender < 0, age / completion = 0, all
+ * region parts -1, an empty clubs / friends list: what the reference does for a user who left the
+ * field empty).  Each selected column keeps its own idf map and normaliser, and everything
+ * selected is computed bit for bit as without a selection.  The denominator is the reference's
+ * own for that column list, 7 + (selected columns): deselecting a fixed field does not shrink the
+ * 7.  Scores of scans with different selections are therefore NOT comparable with each other.
+ * Ranking order, exclusions, the candidate filter and shards behave as without a selection.
+ * Context state like the filter: read by pf_recommend_interest(PF_MODE_ALL) at any topk and by
+ * pf_scan_keys_async, and by nothing else (FoF interest, collab, clubs, plain pf_fas_pairs,
+ * pf_fof_candidates and the hold-out drivers never see it).  Every launch takes the selection by
+ * value as it stands when the call is made, so asynchronous scans already queued keep theirs.  No
+ * query image changes and no second engine is opened.
+ */
+#define PF_SEL_FIXED_ALL 0x7Fu
+typedef struct pf_field_select {
+    uint32_t fixed, flags;  /* fixed: bits above PF_SEL_FIXED_ALL are PF_EINVAL; flags: must be 0 */
+    uint64_t cols;          /* bits at or above n_cols are ignored: ~0 = all columns */
+} pf_field_select;
+/* NULL, or a selection that leaves nothing out, clears.  PF_EINVAL: a NULL context, unknown bits
+ * in fixed, a non-zero flags. */
+int pf_set_scan_select(pf_ctx* ctx, const pf_field_select* select);
+/* pf_fas_pairs under a selection (NULL = none), whatever the context's scan selection is. */
+int pf_fas_pairs_select(pf_ctx* ctx, const int32_t* a_uid, const int32_t* b_uid, int64_t n,
+                        const pf_field_select* select, float* out);
+
+/*
  * Device-resident all-candidates scan for the multi-GPU bench: scores the
  * queries against this context's shard and writes, per query, `topk` packed
  * 64-bit keys to DEVICE memory d_keys[nq*topk] on `stream` (a hipStream_t).
@@ -315,7 +345,9 @@ int pf_layout(const pf_ctx* ctx, pf_layout_stats* out);
  * each staging the image once); nq > 1 a batch (each workgroup stages its query's
  * image once for its four blocks).  The candidate filter (pf_set_scan_filter) is ignored: the
  * bytes are those of the unfiltered scan (a filtered one reads the same headers and ranges and
- * skips the list entries of the blocks in which nobody passes). */
+ * skips the list entries of the blocks in which nobody passes).  The field selection
+ * (pf_set_scan_select) is ignored as well: the bytes are those of the unselected scan (a selected
+ * one reads no entry of a deselected column's or set's lists). */
 int pf_scan_bytes(pf_ctx* ctx, const int32_t* query_uid, int32_t nq, int64_t* out_bytes);
 /* Counters of the postings scan's pruning, summed over the one-query scans of this process
  * since the last reset while PF_DEBUG k5_prune_stats=1 is set (zeros otherwise): out[5] =

@@ -138,8 +138,10 @@ pf::AdjView plain_view(const pf_ctx* c) {
 // distinct query's image is built once per chunk, on host threads.
 // keep (optional): every chunk's scores stay on the device in one buffer, group g at
 // (*goff)[g] (the collaborative sums read their matrix rows there)
+// sel (on == 0: none): a field selection every pair is scored under (pf_fas_pairs_select)
 int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
-              std::vector<std::vector<float>>& out, DBuf* keep = nullptr, std::vector<int64_t>* goff = nullptr) {
+              std::vector<std::vector<float>>& out, DBuf* keep = nullptr, std::vector<int64_t>* goff = nullptr,
+              const pf::FieldSel& sel = pf::FieldSel{}) {
     out.assign(qidx.size(), {});
     if (keep) {
         size_t tot = 0;
@@ -226,7 +228,7 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
         }
         HIPCHK(c, pf::launch_pairs(c->ds, c->d_pool.as<uint8_t>(), c->d_refs.as<pf::QImageRef>(), im.max_lds, im.gtab,
                                    c->d_blocks.as<pf::PairBlock>(), (int)blocks.size(), nullptr, c->d_slots.as<int32_t>(), dsc,
-                                   c->stream));
+                                   c->stream, sel));
         c->jb.n_dispatch += !blocks.empty();  // pf_jobs_stats.pair_dispatches counts every K1' dispatch
         const float* res = c->h_scores.as<float>();
         HIPCHK(c, hipMemcpyAsync(c->h_scores.p, dsc, npairs * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -276,8 +278,8 @@ int batch_blocks_per_wg() {
 uint32_t post_image_lds(const pf::QPostHead* h) {
     return pf::post_lds(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend));
 }
-int post_image_per_cu(const pf::QPostHead* h, bool claimed, bool filtered) {
-    return pf::post_blocks_per_cu(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), claimed, filtered);
+int post_image_per_cu(const pf::QPostHead* h, bool claimed, bool filtered, bool selected) {
+    return pf::post_blocks_per_cu(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), claimed, filtered, selected);
 }
 // LDS a filtered launch takes on top of an image's (the filter's words; pf_kernels.h kFiltLds)
 uint32_t filt_lds(const pf_ctx* c) { return c->filt.fields ? pf::kFiltLds : 0u; }
@@ -416,7 +418,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
     for (int q = 0; q < nq; ++q) {
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q]->data() + sizeof(pf::QConst));
         vl[q] = pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend);
-        pcu[q] = post_image_per_cu(h, claimed, c->filt.fields != 0u);
+        pcu[q] = post_image_per_cu(h, claimed, c->filt.fields != 0u, c->sel.on != 0u);
         order[q] = q;
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pcu[a] > pcu[b]; });
@@ -491,7 +493,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
                                   reinterpret_cast<pf::ScanSync*>(base + offs_b + rows_b) + q0, out_keys,
                                   reinterpret_cast<const int32_t*>(base + offs_b) + q0, claimed,
                                   post_mode(claimed), (timed && q0 == 0) ? e0 : nullptr,
-                                  (timed && q1 == nq) ? e1 : (ln ? ln->done : nullptr), s, nullptr, c->filt));
+                                  (timed && q1 == nq) ? e1 : (ln ? ln->done : nullptr), s, nullptr, c->filt, c->sel));
         q0 = q1;
     }
     if (ln) {  // the caller's stream: wait for the lane's launch (its stop event), copy its row out
@@ -519,7 +521,7 @@ bool resident_ok(const pf_ctx* c, int32_t i) {
 int scan_post_resident(pf_ctx* c, int32_t i, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
     auto& R = c->rp;
     const uint32_t vl = R.var_lds[i];
-    const int per_cu = pf::post_blocks_per_cu(vl, true, c->filt.fields != 0u);
+    const int per_cu = pf::post_blocks_per_cu(vl, true, c->filt.fields != 0u, c->sel.on != 0u);
     const int nwb = c->wb_end - c->wb_begin;
     LaneUse lu;
     int rc = lane_begin(c, s, lu);
@@ -543,7 +545,7 @@ int scan_post_resident(pf_ctx* c, int32_t i, int32_t row, int k, uint64_t* d_key
     const uint8_t* qc = c->jb.d_pimg.as<uint8_t>() + c->jb.pimg_off[i];
     HIPCHK(c, pf::launch_post(c->ps, img, R.d_zero.as<uint32_t>(), vl, 1, c->wb_begin, c->wb_end, k, blocks,
                               part_buf.as<uint64_t>(), sync_buf.as<pf::ScanSync>(), out, R.d_zero.as<int32_t>(),
-                              true, post_mode(true), timed ? e0 : nullptr, stop, ls, qc, c->filt));
+                              true, post_mode(true), timed ? e0 : nullptr, stop, ls, qc, c->filt, c->sel));
     if (ln) {
         rc = lane_end(c, lu, stop, s, d_keys + (size_t)row * k, k);
         if (rc != PF_OK) return rc;
@@ -692,7 +694,7 @@ int scan_stream(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<in
     if (rc != PF_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(e0, s));
     HIPCHK(c, pf::launch_scan(c->ds, d_images, d_refs, im.max_lds, im.gtab, nq, c->tile_begin, c->tile_end, k, blocks,
-                              c->d_part.as<uint64_t>(), d_sync, d_keys, d_rows, s, c->filt));
+                              c->d_part.as<uint64_t>(), d_sync, d_keys, d_rows, s, c->filt, c->sel));
     if (timed) {
         HIPCHK(c, hipEventRecord(e1, s));
         c->last_ev0 = e0;
@@ -1022,8 +1024,49 @@ float pf_idf(const pf_ctx* c, int32_t col, int32_t tid) {
     return c->hc.idf_of_tid(col, tid);
 }
 
+static_assert(PF_SEL_FIXED_ALL == pf::kSelFixedAll && (1u << PF_F_PUBLIC) == pf::kSelPublic &&
+                  (1u << PF_F_GENDER) == pf::kSelGender && (1u << PF_F_COMPLETION) == pf::kSelCompletion &&
+                  (1u << PF_F_AGE) == pf::kSelAge && (1u << PF_F_REGION) == pf::kSelRegion &&
+                  (1u << PF_F_CLUBS) == pf::kSelClubs && (1u << PF_F_FRIENDS) == pf::kSelFriends,
+              "pf_select.h restates the public field bits");
+static_assert(sizeof(pf_field_select) == 16 && sizeof(pf_field_select) == sizeof(pf::FieldSel), "pf_field_select is 16 B");
+
+// The device form of a public selection: PF_EINVAL for unknown bits; NULL, or one that leaves out
+// nothing of this engine's T columns, is no selection (on == 0).
+static int make_select(const pf_ctx* c, const pf_field_select* s, pf::FieldSel& d) {
+    d = pf::FieldSel{};
+    if (!s) return PF_OK;
+    if ((s->fixed & ~pf::kSelFixedAll) || s->flags != 0u) return PF_EINVAL;
+    if (pf::select_is_all(s->fixed, s->cols, c->hc.T)) return PF_OK;
+    d.fixed = s->fixed;
+    d.on = 1u;
+    d.cols = s->cols & pf::select_low(c->hc.T);
+    return PF_OK;
+}
+
+int pf_set_scan_select(pf_ctx* c, const pf_field_select* s) {
+    if (!c) return PF_EINVAL;
+    pf::FieldSel d;
+    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "scan select: unknown bits in fixed / flags");
+    c->sel = d;
+    return PF_OK;
+}
+
+static int fas_pairs(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, float* out, const pf::FieldSel& sel);
+
 int pf_fas_pairs(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, float* out) {
     if (!c || n < 0 || (n && (!a || !b || !out))) return PF_EINVAL;
+    return fas_pairs(c, a, b, n, out, pf::FieldSel{});
+}
+
+int pf_fas_pairs_select(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, const pf_field_select* s, float* out) {
+    if (!c || n < 0 || (n && (!a || !b || !out))) return PF_EINVAL;
+    pf::FieldSel d;
+    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "pairs select: unknown bits in fixed / flags");
+    return fas_pairs(c, a, b, n, out, d);
+}
+
+static int fas_pairs(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, float* out, const pf::FieldSel& sel) {
     (void)hipSetDevice(c->device);
     std::unordered_map<int32_t, int32_t> group;  // query idx -> group
     std::vector<int32_t> qidx;
@@ -1043,7 +1086,7 @@ int pf_fas_pairs(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, float
         slots[it->second].push_back(c->hs.slot_of_idx[ib]);
     }
     std::vector<std::vector<float>> res;
-    int rc = run_pairs(c, qidx, slots, res);
+    int rc = run_pairs(c, qidx, slots, res, nullptr, nullptr, sel);
     if (rc != PF_OK) return rc;
     for (int64_t i = 0; i < n; ++i)
         if (where[i].first >= 0) out[i] = res[where[i].first][where[i].second];
@@ -1379,7 +1422,7 @@ int pf_scan_bytes(pf_ctx* c, const int32_t* q, int32_t nq, int64_t* out) {
     }
     // workgroups that stage a query's image, as scan_post launches the fitting queries
     const int nwb = c->wb_end - c->wb_begin;
-    const int wgs = nfit == 1 ? one_query_wgs(c->num_cus * pf::post_blocks_per_cu(pf::post_var_lds(max_tok, max_lists), true, false), true)
+    const int wgs = nfit == 1 ? one_query_wgs(c->num_cus * pf::post_blocks_per_cu(pf::post_var_lds(max_tok, max_lists), true, false, false), true)
                               : (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg();
     par_jobs((size_t)nq, [&](size_t i) {
         out[i] = kind[i] == 0 ? 0 : (kind[i] == 2 ? k1 : post_query_bytes(c, imgs[i], wgs));

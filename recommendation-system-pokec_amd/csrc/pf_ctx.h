@@ -230,6 +230,9 @@ struct pf_ctx {
     // device form: every scan launch and every kDjAll chunk takes it by value as it stands then
     pf::CandFilter filt{};
     DBuf d_filt_count;  // pf_scan_filter_count's counter
+    // field selection of the all-candidates scans (pf_set_scan_select; on == 0: none), in its device
+    // form: taken by value like the filter, by every scan launch and every kDjAll chunk's pair stage
+    pf::FieldSel sel{};
     // pinned staging ring for the per-call query upload (a slot is reused only after
     // the copy that read it has completed)
     struct Stage {

@@ -707,6 +707,8 @@ struct ChunkPlan {
     // the context's candidate filter (pf_set_scan_filter) as it stood when the chunk was planned, when
     // the chunk holds an all-candidates job (kDjAll: the only kind it applies to); else none
     CandFilter filt{};
+    // and its field selection (pf_set_scan_select), handed to the chunk's pair stage: on the same condition
+    FieldSel sel{};
 };
 
 // Step 1: jobs[b, e) (planned in P) as DevJobs, their two pools and their pair-block runs.
@@ -1074,7 +1076,7 @@ int enqueue_chunk(pf_ctx* c, const ChunkPlan& cp, const PlanLayout& L, JobsState
     }
     for (int k = 0, o = 0; k < 3; o += cp.nb_c[k++]) {  // the pair-scoring stage (timed)
         HIPCHK(c, launch_pairs(c->ds, ipl, L.refs.at(d), cp.lds_c[k], k == 2, d_blk + o, cp.nb_c[k], d_ord + o, slots, fl,
-                               st.sp));
+                               st.sp, cp.sel));
         J.n_dispatch += cp.nb_c[k] > 0;
     }
     if (pe1) {
@@ -1156,7 +1158,10 @@ int launch_chunk(pf_ctx* c, std::vector<Job>& jobs, std::vector<JP>& P, size_t b
     ChunkPlan cp;
     if (const int rc = layout_jobs(c, jobs, P, b, e, cp); rc != PF_OK || cp.dj.empty()) return rc;
     for (const DevJob& d : cp.dj)
-        if (d.kind == kDjAll) cp.filt = c->filt;
+        if (d.kind == kDjAll) {
+            cp.filt = c->filt;
+            cp.sel = c->sel;
+        }
     if (W.done == nullptr) {
         HIPCHK(c, hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&W.ev_pairs, hipEventDisableTiming));

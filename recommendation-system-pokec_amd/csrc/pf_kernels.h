@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pf_filter.h"
+#include "pf_select.h"
 #include "pf_types.h"
 
 namespace pf {
@@ -30,9 +31,12 @@ struct PairGen {
 //   sizeof(QConst) + staged keys/vals + n_hits_max * threads + 2048
 // gtab: at least one image of the batch probes its table in global memory (lds_bytes == 0);
 // the whole launch then uses the global-table variant.
+// sel (by value in the launch's arguments; on == 0: none): the context's field selection
+// (pf_select.h), applied to each block's staged copy of its query's constants.
 hipError_t launch_scan(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t lds, bool gtab,
                        int nq, int tile_begin, int tile_end, int k, int blocks, uint64_t* parts, ScanSync* sync,
-                       uint64_t* out, const int32_t* out_rows, hipStream_t s, const CandFilter& filt);
+                       uint64_t* out, const int32_t* out_rows, hipStream_t s, const CandFilter& filt,
+                       const FieldSel& sel);
 // resident scan blocks per CU at this dynamic LDS size (HIP occupancy API)
 int scan_blocks_per_cu(bool packed, bool gtab, uint32_t lds);
 // K5 postings scan over candidate blocks [blk_begin, blk_end) for nq query images (byte
@@ -51,6 +55,9 @@ uint32_t post_lds(uint32_t var_lds);
 // candidate passes the filter runs to its end instead of leaving after its first barrier.
 // filt (by value in the launch's arguments; fields == 0: none): the context's candidate filter
 // (pf_filter.h); a filtered launch takes the FILT instantiation of its hand-out.
+// sel (by value likewise; on == 0: none): the context's field selection (pf_select.h); a selected
+// launch takes the SEL instantiation, which patches its staged copy of the query's constants and
+// leaves the deselected columns and set lists out of its tables.  It needs no LDS of its own.
 constexpr uint32_t kPostPrune = 1u << 16, kPostPruneStats = 1u << 17, kPostPruneBlockOnly = 1u << 18;
 constexpr uint32_t kPostFiltKeepBlocks = 1u << 19;
 // dynamic LDS a filtered launch takes on top of post_lds(var_lds): the filter, parked past the query's tables
@@ -58,9 +65,10 @@ constexpr uint32_t kFiltLds = (uint32_t)sizeof(CandFilter);
 hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t* img_off, uint32_t var_lds, int nq,
                        int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
                        const int32_t* out_rows, bool claimed, uint32_t mode, hipEvent_t e0, hipEvent_t e1,
-                       hipStream_t s, const uint8_t* qconst, const CandFilter& filt);
-// workgroups per CU of the instantiation launch_post takes for `claimed` and `filtered` (a filter is set)
-int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered);
+                       hipStream_t s, const uint8_t* qconst, const CandFilter& filt, const FieldSel& sel);
+// workgroups per CU of the instantiation launch_post takes for `claimed`, `filtered` (a filter is
+// set) and `selected` (a field selection is set)
+int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered, bool selected);
 // candidates of idx range [i0, i1) of the postings headers (ps.hdr), or with ps.hdr null of slots
 // [i0, i1) of the tile headers, that pass filt: added to *count (device, zeroed by the caller)
 hipError_t launch_filter_count(const PostStore& ps, const DevStore& st, int32_t i0, int32_t i1, const CandFilter& filt,
@@ -73,8 +81,10 @@ hipError_t k5_prune_stats_read(unsigned long long* out, bool reset);
 hipError_t launch_merge(const uint64_t* in, int nparts, int64_t part_stride, int64_t query_stride, int nq, int k,
                         uint64_t* out, hipStream_t s);
 // order (nullable): the dispatch order, block blockIdx.x scores blocks[order[blockIdx.x]]
+// sel (on == 0: none): a field selection applied to every block's staged constants (pf_fas_pairs_select,
+// the pair stage of an all-candidates job chunk)
 hipError_t launch_pairs(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t max_lds,
                         bool gtab, const PairBlock* blocks, int nblocks, const int32_t* order, const int32_t* slots,
-                        float* out, hipStream_t s);
+                        float* out, hipStream_t s, const FieldSel& sel = FieldSel{});
 
 }  // namespace pf

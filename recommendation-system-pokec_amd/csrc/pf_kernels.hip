@@ -29,6 +29,7 @@
 #include "pf_kernels.h"
 #include "pf_plan.h"
 #include "pf_prune.h"
+#include "pf_select.h"
 
 namespace pf {
 
@@ -378,6 +379,9 @@ __device__ __forceinline__ float fas_epilogue(const QView& v, const Rec& rec, co
                 have = next();
             }
             if (have) nrm = rec.norm(cmask, (int)H::col(e));
+            // a hit column the query's colmask lacks is one a field selection (pf_select.h) left
+            // out: the walk still finds its tokens in the table, and it gets no term
+            if (!((common >> t) & 1ull)) continue;
             uint64_t below = common & ((1ull << t) - 1ull);
             common &= ~below & ~(1ull << t);
             while (below) {
@@ -516,10 +520,16 @@ __device__ __forceinline__ float pair_epilogue(const QView& v, const DevStore& s
 #pragma unroll
     for (int i = 0; i < (int)kHitCap; ++i) hw[i] = (uint32_t)i < nhl ? hl[i * kPairThreads + threadIdx.x] : 0u;
     auto colw = [](uint32_t w) { return (w >> kTidBits) & 63u; };
+    // the query's columns (uniform: scalar registers).  A hit column not among them is one a field
+    // selection (pf_select.h) left out: the walk still finds its tokens, and it gets no item
+    // (each half through uint32_t: readfirstlane returns int, and bit 31 must not extend)
+    const uint64_t qcm = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)q.colmask) |
+                         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(q.colmask >> 32)) << 32);
     uint32_t ncol = 0;
 #pragma unroll
     for (int i = 0; i < (int)kHitCap; ++i)
-        ncol += ((uint32_t)i < nhl && (i == 0 || colw(hw[i]) != colw(hw[i > 0 ? i - 1 : 0]))) ? 1u : 0u;
+        ncol += ((uint32_t)i < nhl && (i == 0 || colw(hw[i]) != colw(hw[i > 0 ? i - 1 : 0])) && ((qcm >> colw(hw[i])) & 1ull))
+                    ? 1u : 0u;
     const uint32_t nc = h2.y, nf = h2.z;
     const int ic = (int)(cnt & 0xFFFFu), ifr = (int)(cnt >> 16);
     const bool dense = active && !overflow;
@@ -597,7 +607,7 @@ __device__ __forceinline__ float pair_epilogue(const QView& v, const DevStore& s
                     const bool first = i == 0 || col != colw(hw[i > 0 ? i - 1 : 0]);
                     dot = (first ? 0.0 : dot) + hit_product(v, val & kTidMask, (int32_t)(w >> 24));
                     const bool last = (uint32_t)(i + 1) == nhl || col != colw(hw[i + 1 < (int)kHitCap ? i + 1 : i]);
-                    if (last) {
+                    if (last && ((qcm >> col) & 1ull)) {
                         const uint32_t rank = (uint32_t)__popcll(cmask & ((1ull << col) - 1ull));
                         *item(k++) = make_uint4((uint32_t)__double2loint(dot), (uint32_t)__double2hiint(dot), nbase,
                                                 (kItemText << 16) | (rank << 8) | col);
@@ -630,8 +640,7 @@ __device__ __forceinline__ float pair_epilogue(const QView& v, const DevStore& s
             // read), adding where the candidate has the column too
             const uint32_t ke = rbase + nit;
             uint32_t nextc = kk < ke ? (item(kk)->w & 0xFFu) : 0xFFu;
-            uint64_t qm = __builtin_amdgcn_readfirstlane((uint32_t)q.colmask) |
-                          ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(q.colmask >> 32)) << 32);
+            uint64_t qm = qcm;
             while (qm) {
                 const uint32_t c = (uint32_t)__ffsll((unsigned long long)qm) - 1u;
                 qm &= qm - 1ull;
@@ -791,7 +800,8 @@ __device__ __forceinline__ void stage4(void* dst, const void* src, uint32_t byte
 // pointer: a merged pointer would compile to flat loads, whose waits also drain the
 // HBM prefetch).  GTAB = true (query too large for LDS): probes read global memory.
 template <bool GTAB>
-__device__ __forceinline__ QView stage_query(char* smem, const uint8_t* pool, const QImageRef& r, char** scratch) {
+__device__ __forceinline__ QView stage_query(char* smem, const uint8_t* pool, const QImageRef& r, char** scratch,
+                                             const FieldSel& S) {
     if constexpr (!GTAB) {
         // the sizes from the image in global memory; QConst | tables | values are contiguous in
         // every image pool (tables of >= 2^4 8-B entries keep the values 16-B aligned)
@@ -809,6 +819,12 @@ __device__ __forceinline__ QView stage_query(char* smem, const uint8_t* pool, co
         stage(smem, pool + (size_t)r.const_off * 16u, sizeof(QConst));
     }
     __syncthreads();
+    // a field selection (pf_select.h; uniform, on == 0: none) patches the staged copy of the
+    // constants, never the image: the fixed terms, the common columns and the denominator follow
+    if (S.on != 0u) {
+        if (threadIdx.x == 0) select_apply(*reinterpret_cast<QConst*>(smem), S);
+        __syncthreads();
+    }
     const QConst* q = reinterpret_cast<const QConst*>(smem);
     // the image's sizes are workgroup-uniform: read into SGPRs (as LDS loads they would sit in a
     // VGPR each for the whole kernel, and the walk loops are register-bound)
@@ -975,11 +991,12 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_scan_kernel(DevStore st, 
                                                                 uint64_t* __restrict__ parts,
                                                                 ScanSync* __restrict__ sync,
                                                                 uint64_t* __restrict__ out,
-                                                                const int32_t* __restrict__ out_rows, CandFilter F) {
+                                                                const int32_t* __restrict__ out_rows, CandFilter F,
+                                                                FieldSel S) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const QImageRef r = refs[blockIdx.y];
     char* scratch;
-    const QView v = stage_query<GTAB>(smem, pool, r, &scratch);
+    const QView v = stage_query<GTAB>(smem, pool, r, &scratch, S);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint64_t list = ~0ull;
     // Tile hand-out, longest tiles first.  Static zig-zag for all but the last two bands
@@ -1130,6 +1147,8 @@ constexpr uint32_t kHitCand = 1u << 15;
 // token segment (per token of a round): segment start | end << 8 (round-relative) | column << 16 |
 // split (the column spans several rounds) << 24
 constexpr uint32_t kSegSplit = 1u << 24;
+// colof of a token whose column a field selection left out (active column indices are < kPostMaxCols)
+constexpr uint8_t kColDead = 0xFFu;
 
 #ifdef PF_K5_CHECK
 // checked build (tools/build_variant.sh k5chk XFLAGS=-DPF_K5_CHECK): every global index of K5 is
@@ -1146,6 +1165,11 @@ __device__ __forceinline__ uint32_t k5_chk(uint32_t i, uint32_t n, int what) {
 #define K5CHK(i, n, w) (i)
 #endif
 
+
+// K5 under a field selection: the high word of a deselected column's token's weight in the staged
+// tokens (a NaN no real weight has).  The block's prefix scan counts such a token's range as empty,
+// so no entry of it is ever walked.
+constexpr uint32_t kTokDeadHi = 0xFFFFFFFFu;
 
 // entries of list L for candidates [c0, c1] (cells c0 >> shift .. c1 >> shift)
 __device__ __forceinline__ uint2 list_range(const PostStore& ps, const PList& L, uint32_t c0, uint32_t c1) {
@@ -1164,11 +1188,16 @@ __device__ __forceinline__ int set_list(const uint32_t* spre, int n, uint32_t f)
 }
 
 // gpre[j] = sum of the lengths of ranges 0 .. j-1 (j <= nl), by one wave
-__device__ __forceinline__ void wave_prefix(uint32_t* gpre, const uint2* rng, int nl, int lane) {
+// DEAD: list j whose staged token weight carries the dead mark (dead[j], kTokDeadHi) counts as empty
+template <bool DEAD = false>
+__device__ __forceinline__ void wave_prefix(uint32_t* gpre, const uint2* rng, int nl, int lane, const PTok* dead = nullptr) {
     uint32_t carry = 0;
     for (int b = 0; b < nl; b += 64) {
         const int j = b + lane;
-        const uint32_t len = j < nl ? rng[j].y - rng[j].x : 0u;
+        uint32_t len = j < nl ? rng[j].y - rng[j].x : 0u;
+        if constexpr (DEAD) {
+            if (j < nl && reinterpret_cast<const uint32_t*>(dead)[4 * j + 1] == kTokDeadHi) len = 0u;
+        }
         uint32_t x = len;
         x = wave_incl_scan(x);
         if (j < nl) gpre[j] = carry + x - len;
@@ -1324,13 +1353,21 @@ static __device__ __attribute__((noinline)) uint32_t prune_derive(ScanSync* sy, 
 // FILT: the context has a candidate filter (pf_filter.h, F; launch_post picks the instantiation): a
 // candidate whose header fails it is dropped like an excluded one, a block in which nobody passes
 // is left after its first barrier.  <XD, false> never reads F and is the code it was without it.
-template <bool XD, bool FILT>
+// SEL: the context has a field selection (pf_select.h, S; launch_post picks the instantiation): the
+// staged copy of the query's constants is patched before the staging barrier publishes it, so the
+// fixed terms, pend, ftab and need[] (the pruning bound's 7 + T') follow by themselves; the
+// deselected columns are left out of scol / cpre / colof, their tokens count no entries in any
+// block's prefix (no entry is walked, no round is planned for them), and the deselected club /
+// friend lists are left out of the set lists.  S is read during staging only: nothing of it lives
+// through the block loop.  <XD, FILT, false> never reads S and is the code it was without it.
+template <bool XD, bool FILT, bool SEL>
 __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(PostStore ps, const uint8_t* __restrict__ pool,
                                                               const uint32_t* __restrict__ img_off, int32_t blk_begin,
                                                               int32_t blk_end, int32_t k, uint64_t* __restrict__ parts,
                                                               ScanSync* __restrict__ sync, uint64_t* __restrict__ out,
                                                               const int32_t* __restrict__ out_rows, uint32_t mode,
-                                                              const uint8_t* __restrict__ qconst, CandFilter F) {
+                                                              const uint8_t* __restrict__ qconst, CandFilter F,
+                                                              FieldSel S) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int qy = XD ? 0 : (int)blockIdx.y;
     const int bx = (int)blockIdx.x;
@@ -1340,10 +1377,20 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     // resident images) the job pipeline's resident K1' image of the same user, whose QConst K6
     // builds from the same tables; the image's own part then starts sizeof(QConst) past img
     const uint8_t* qcp = qconst ? qconst : img;
-    const QPostHead H = *reinterpret_cast<const QPostHead*>(img + sizeof(QConst));
+    QPostHead H = *reinterpret_cast<const QPostHead*>(img + sizeof(QConst));
     const QTok* toks = reinterpret_cast<const QTok*>(img + H.tok_off);
     const QCol* cols = reinterpret_cast<const QCol*>(img + H.col_off);
     const PList* sets = reinterpret_cast<const PList*>(img + H.set_off);
+    const int n_act_img = H.n_act;  // the image's active columns (SEL: H.n_act becomes the selected ones)
+    if constexpr (SEL) {
+        // a deselected set's lists (the clubs' come first) are not there at all: the LDS carve below
+        // only shrinks
+        if (!(S.fixed & kSelClubs)) { sets += H.n_club; H.n_club = 0; }
+        if (!(S.fixed & kSelFriends)) H.n_friend = 0;
+        int na = 0;
+        for (int j = 0; j < n_act_img; ++j) na += (int)((S.cols >> cols[j].t) & 1ull);
+        H.n_act = na;
+    }
     const uint32_t* excl = reinterpret_cast<const uint32_t*>(img + H.excl_off);
     const int tid = (int)threadIdx.x, lane = tid & 63;
     char* base = smem + sizeof(QConst);
@@ -1400,21 +1447,54 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     }
     if (tid < 16) misc[tid] = 0u;
     stage(smem, qcp, sizeof(QConst));
-    for (int j = tid; j < H.n_act; j += kPostThreads) {
-        const QCol c = cols[j];
-        scol[j] = c;
-        for (int x = c.j0; x < c.j1; ++x) colof[x] = (uint8_t)j;
+    if constexpr (!SEL) {
+        for (int j = tid; j < H.n_act; j += kPostThreads) {
+            const QCol c = cols[j];
+            scol[j] = c;
+            for (int x = c.j0; x < c.j1; ++x) colof[x] = (uint8_t)j;
+        }
+        if (tid == 0) {  // prefix masks of the active columns (<= 48, ascending)
+            uint64_t m = 0;
+            for (int j = 0; j < H.n_act; ++j) { cpre[j] = m; m |= 1ull << cols[j].t; }
+            cpre[H.n_act] = m;
+        }
+        for (int j = tid; j <= kNumFixed + kPostMaxCols; j += kPostThreads)
+            ftab[j] = (double)j / (double)(kNumFixed + reinterpret_cast<const QConst*>(qcp)->n_cols);
+    } else {
+        // the selected columns only, in their order; a deselected column's tokens keep their place
+        // in the token arrays (the images are not edited) and are marked kColDead here and
+        // kTokDeadHi in the staged tokens below, so every block's prefix scan counts them no entries
+        for (int j = tid; j < n_act_img; j += kPostThreads) {
+            const QCol c = cols[j];
+            int js = 0;  // selected columns before this one
+            for (int x = 0; x < j; ++x) js += (int)((S.cols >> cols[x].t) & 1ull);
+            const bool on = (S.cols >> c.t) & 1ull;
+            if (on) scol[js] = c;
+            for (int x = c.j0; x < c.j1; ++x) colof[x] = on ? (uint8_t)js : kColDead;
+        }
+        if (tid == 0) {
+            uint64_t m = 0;
+            int js = 0;
+            for (int j = 0; j < n_act_img; ++j) {
+                const int t = cols[j].t;
+                if ((S.cols >> t) & 1ull) { cpre[js++] = m; m |= 1ull << t; }
+            }
+            cpre[js] = m;
+        }
+        const int ncs = select_ncols(S.cols, reinterpret_cast<const QConst*>(qcp)->n_cols);
+        for (int j = tid; j <= kNumFixed + kPostMaxCols; j += kPostThreads)
+            ftab[j] = (double)j / (double)(kNumFixed + ncs);
+        // the constants' patch: after every thread's part of the copy, before the barrier below
+        // publishes the staged tables
+        __syncthreads();
+        if (tid == 0) select_apply(*reinterpret_cast<QConst*>(smem), S);
     }
-    if (tid == 0) {  // prefix masks of the active columns (<= 48, ascending)
-        uint64_t m = 0;
-        for (int j = 0; j < H.n_act; ++j) { cpre[j] = m; m |= 1ull << cols[j].t; }
-        cpre[H.n_act] = m;
-    }
-    for (int j = tid; j <= kNumFixed + kPostMaxCols; j += kPostThreads)
-        ftab[j] = (double)j / (double)(kNumFixed + reinterpret_cast<const QConst*>(qcp)->n_cols);
     for (int j = tid; j < H.n_tok; j += kPostThreads) {
         const QTok t = toks[j];
         pt[j] = PTok{t.wq, t.idf};
+        if constexpr (SEL) {  // (colof is complete: SEL's barrier above)
+            if (colof[j] == kColDead) reinterpret_cast<uint32_t*>(pt + j)[1] = kTokDeadHi;
+        }
     }
     __syncthreads();  // the staged tables are read by other threads
     const QConst& q = *reinterpret_cast<const QConst*>(smem);
@@ -1550,13 +1630,15 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
             // through the block loop they would cost every wave two VGPRs for wave 0's sake; the
             // read is in flight under the prefix)
             ColPlan cpl = col_tokens(scol, H.n_act, lane);
-            wave_prefix(gpre, rng, H.n_tok, lane);
+            wave_prefix<SEL>(gpre, rng, H.n_tok, lane, pt);  // SEL: a deselected column's tokens count no entries
             wave_sync();
             col_ends(cpl, gpre, H.n_act, lane);
             // the block's rounds, once (every thread used to walk the columns' prefix chain per round)
             {
                 int ci0 = 0, j0 = 0, nr = 0;
                 while (ci0 < H.n_act) {
+                    // (a round never starts among the tokens of deselected columns before column ci0)
+                    if constexpr (SEL) j0 = max(j0, __builtin_amdgcn_readlane(cpl.j0, ci0));
                     const Round Rr = plan_round(cpl, gpre, H.n_act, lane, ci0, j0);
                     if (lane == 0)
                         rtab[nr] = make_uint2((uint32_t)Rr.ja | (uint32_t)Rr.jb << 16, (uint32_t)Rr.ca | (uint32_t)Rr.ce << 16);
@@ -1696,7 +1778,8 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 // token segments of the round (read after the walk's barrier)
                 if (tid < jb - ja) {
                     const int j = ja + tid;
-                    const QCol c = scol[colof[j]];
+                    // (SEL: a deselected column's token inside the round has no entries; its segment is never read)
+                    const QCol c = scol[SEL ? min((int)colof[j], kPostMaxCols - 1) : (int)colof[j]];
                     const int lo = max(c.j0, ja) - ja, hi = min(c.j1, jb) - ja;
                     seg[tid] = (uint32_t)lo | (uint32_t)hi << 8 | (uint32_t)c.t << 16 |
                                ((c.j0 < ja || c.j1 > jb) ? kSegSplit : 0u);
@@ -2064,7 +2147,8 @@ __global__ PF_K1P_BOUNDS void fas_pairs_kernel(DevStore st, const uint8_t* __res
                                                         const QImageRef* __restrict__ refs,
                                                         const PairBlock* __restrict__ blocks,
                                                         const int32_t* __restrict__ order,
-                                                        const int32_t* __restrict__ slots, float* __restrict__ out) {
+                                                        const int32_t* __restrict__ slots, float* __restrict__ out,
+                                                        FieldSel S) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef PF_K5_TIMERS
     const uint64_t t0 = clock64();
@@ -2082,7 +2166,7 @@ __global__ PF_K1P_BOUNDS void fas_pairs_kernel(DevStore st, const uint8_t* __res
     if (!__syncthreads_or(active)) return;
     const PairHdr H = load_pair_hdr(st, p, active);
     char* scratch;
-    const QView v = stage_query<GTAB>(smem, pool, refs[b.qimg], &scratch);
+    const QView v = stage_query<GTAB>(smem, pool, refs[b.qimg], &scratch, S);
 #ifdef PF_K5_TIMERS
     const uint64_t t1 = clock64();
 #endif
@@ -2160,11 +2244,11 @@ hipError_t launch_filter_count(const PostStore& ps, const DevStore& st, int32_t 
 
 hipError_t launch_scan(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t lds, bool gtab,
                        int nq, int tile_begin, int tile_end, int k, int blocks, uint64_t* parts, ScanSync* sync,
-                       uint64_t* out, const int32_t* out_rows, hipStream_t s, const CandFilter& filt) {
+                       uint64_t* out, const int32_t* out_rows, hipStream_t s, const CandFilter& filt, const FieldSel& sel) {
     if (nq <= 0) return hipSuccess;
     dim3 grid(blocks, nq), block(kScanThreads);
 #define PF_SCAN(P, G) hipLaunchKernelGGL((fas_scan_kernel<P, G>), grid, block, lds, s, st, pool, refs_dev, tile_begin, \
-                                         tile_end, k, parts, sync, out, out_rows, filt)
+                                         tile_end, k, parts, sync, out, out_rows, filt, sel)
     if (st.packed) { if (gtab) PF_SCAN(true, true); else PF_SCAN(true, false); }
     else { if (gtab) PF_SCAN(false, true); else PF_SCAN(false, false); }
 #undef PF_SCAN
@@ -2244,19 +2328,25 @@ static void blog_report(int nbx) {
 hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t* img_off, uint32_t var_lds, int nq,
                        int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
                        const int32_t* out_rows, bool claimed, uint32_t mode, hipEvent_t e0, hipEvent_t e1,
-                       hipStream_t s, const uint8_t* qconst, const CandFilter& filt) {
+                       hipStream_t s, const uint8_t* qconst, const CandFilter& filt, const FieldSel& sel) {
     if (nq <= 0) return hipSuccess;
     // the claimed hand-out is the one-query instantiation's and nobody else's
     if (claimed && nq != 1) return hipErrorInvalidValue;
     // timed launches (e0, e1 given): the kernel's own start and end timestamps, taken from its
     // dispatch (hipExtLaunchKernelGGL), instead of two marker packets around it
     const dim3 grid(blocks, nq);
-#define PF_POST(XD, FILT) hipExtLaunchKernelGGL((fas_post_kernel<XD, FILT>), grid, dim3(kPostThreads), lds, s, e0, e1, 0u, ps, \
-                                                pool, img_off, blk_begin, blk_end, k, parts, sync, out, out_rows, mode, qconst, filt)
+#define PF_POST(XD, FILT, SEL) hipExtLaunchKernelGGL((fas_post_kernel<XD, FILT, SEL>), grid, dim3(kPostThreads), lds, s, e0, e1, 0u, ps, \
+                                                     pool, img_off, blk_begin, blk_end, k, parts, sync, out, out_rows, mode, qconst, filt, sel)
     const uint32_t lds = post_lds(var_lds) + (filt.fields ? kFiltLds : 0u);  // + the filter's words (fas_post_kernel)
     // the filter travels in the launch's own arguments: a later pf_set_scan_filter does not reach it
-    if (filt.fields) { if (claimed) PF_POST(true, true); else PF_POST(false, true); }
-    else { if (claimed) PF_POST(true, false); else PF_POST(false, false); }
+    // and so does the field selection (pf_set_scan_select)
+    if (sel.on) {
+        if (filt.fields) { if (claimed) PF_POST(true, true, true); else PF_POST(false, true, true); }
+        else { if (claimed) PF_POST(true, false, true); else PF_POST(false, false, true); }
+    } else {
+        if (filt.fields) { if (claimed) PF_POST(true, true, false); else PF_POST(false, true, false); }
+        else { if (claimed) PF_POST(true, false, false); else PF_POST(false, false, false); }
+    }
 #undef PF_POST
 #ifdef PF_K5_BLOCKLOG
     {
@@ -2298,20 +2388,25 @@ hipError_t k5_prune_stats_read(unsigned long long* out, bool reset) {
     return e;
 }
 
-int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered) {
-    // per thread, by instantiation (the one launch_post takes for `claimed` and the filter) and LDS
-    // bytes (a batch asks once per query: the occupancy API once per size)
-    static thread_local std::unordered_map<uint32_t, int> memos[4];
-    auto& memo = memos[2 * (int)filtered + (int)claimed];
+int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered, bool selected) {
+    // per thread, by instantiation (the one launch_post takes for `claimed`, the filter and the
+    // selection) and LDS bytes (a batch asks once per query: the occupancy API once per size)
+    static thread_local std::unordered_map<uint32_t, int> memos[8];
+    auto& memo = memos[4 * (int)selected + 2 * (int)filtered + (int)claimed];
     auto it = memo.find(var_lds);
     if (it != memo.end()) return it->second;
     int nb = 0;
     const size_t lds = post_lds(var_lds) + (filtered ? kFiltLds : 0u);
     hipError_t e;
-    if (filtered) e = claimed ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true, true>, kPostThreads, lds)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false, true>, kPostThreads, lds);
-    else e = claimed ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<true, false>, kPostThreads, lds)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<false, false>, kPostThreads, lds);
+#define PF_OCC(XD, FILT, SEL) hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<XD, FILT, SEL>, kPostThreads, lds)
+    if (selected) {
+        if (filtered) e = claimed ? PF_OCC(true, true, true) : PF_OCC(false, true, true);
+        else e = claimed ? PF_OCC(true, false, true) : PF_OCC(false, false, true);
+    } else {
+        if (filtered) e = claimed ? PF_OCC(true, true, false) : PF_OCC(false, true, false);
+        else e = claimed ? PF_OCC(true, false, false) : PF_OCC(false, false, false);
+    }
+#undef PF_OCC
     nb = (e == hipSuccess && nb > 0) ? nb : 1;
     if (memo.size() > 4096) memo.clear();
     memo.emplace(var_lds, nb);
@@ -2328,10 +2423,10 @@ hipError_t launch_merge(const uint64_t* in, int nparts, int64_t part_stride, int
 
 hipError_t launch_pairs(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t max_lds,
                         bool gtab, const PairBlock* blocks, int nblocks, const int32_t* order, const int32_t* slots,
-                        float* out, hipStream_t s) {
+                        float* out, hipStream_t s, const FieldSel& sel) {
     if (nblocks <= 0) return hipSuccess;
 #define PF_PAIRS(P, G) hipLaunchKernelGGL((fas_pairs_kernel<P, G>), dim3(nblocks), dim3(kPairThreads), max_lds, s, st, pool, \
-                                          refs_dev, blocks, order, slots, out)
+                                          refs_dev, blocks, order, slots, out, sel)
     if (st.packed) { if (gtab) PF_PAIRS(true, true); else PF_PAIRS(true, false); }
     else { if (gtab) PF_PAIRS(false, true); else PF_PAIRS(false, false); }
 #undef PF_PAIRS

@@ -24,6 +24,10 @@ MAX_TOPK_DEVICE = 64
 # candidate filter of the all-candidates scans (pf_cand_filter)
 PF_FILT_GENDER, PF_FILT_PUBLIC, PF_FILT_AGE, PF_FILT_COMPLETION, PF_FILT_REGION = 1, 2, 4, 8, 16
 PF_FILT_KEEP_MISSING = 1
+# field selection of the all-candidates scans (pf_field_select): bit k of `fixed` = PF_F_*
+PF_F_PUBLIC, PF_F_GENDER, PF_F_COMPLETION, PF_F_AGE, PF_F_REGION, PF_F_CLUBS, PF_F_FRIENDS = range(7)
+PF_SEL_FIXED_ALL = 0x7F
+FIXED_FIELD_NAMES = ("public", "gender", "completion", "age", "region", "clubs", "friends")
 
 # every entry point of include/pokec_fas.h
 EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_users", "pf_idf", "pf_fas_pairs",
@@ -32,7 +36,7 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_last_scan_ms", "pf_profile_reset", "pf_profile_read", "pf_profile_sample", "pf_set_scan_kernel",
            "pf_scan_bytes", "pf_scan_prune_stats", "pf_jobs_stats_reset", "pf_jobs_stats_read", "pf_recommend_interest_async",
            "pf_recommend_collab_async", "pf_recommend_clubs_async", "pf_wait", "pf_completed_ticket",
-           "pf_set_scan_filter", "pf_scan_filter_count"]
+           "pf_set_scan_filter", "pf_scan_filter_count", "pf_set_scan_select", "pf_fas_pairs_select"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
               "pf_dataset_profile_order", "pf_dataset_adj_order", "pf_dataset_profile_json", "pf_dataset_club_name",
@@ -90,6 +94,43 @@ class CandFilter(ctypes.Structure):
     def copy(self):
         g = CandFilter()
         ctypes.memmove(ctypes.byref(g), ctypes.byref(self), ctypes.sizeof(CandFilter))
+        return g
+
+
+class FieldSelect(ctypes.Structure):
+    """pf_field_select: which fields FAS is computed over in the all-candidates scans.  `fixed` is
+    a mask of the seven fixed fields (bit k = PF_F_*), `cols` a mask of the engine's text columns
+    (bits at or above its column count are ignored).  The denominator is 7 + (selected columns), so
+    scores under different selections are not comparable with each other."""
+    _fields_ = [("fixed", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("cols", ctypes.c_uint64)]
+
+    @classmethod
+    def make(cls, fixed=None, cols=None):
+        """fixed: None = all seven, else a mask or an iterable of PF_F_* numbers / names ("public",
+        "gender", "completion", "age", "region", "clubs", "friends"); cols: None = every column,
+        else a mask or an iterable of column indices."""
+        s = cls()
+        if fixed is None:
+            s.fixed = PF_SEL_FIXED_ALL
+        elif isinstance(fixed, int):
+            s.fixed = fixed
+        else:
+            for f in fixed:
+                s.fixed |= 1 << (FIXED_FIELD_NAMES.index(f) if isinstance(f, str) else int(f))
+        if cols is None:
+            s.cols = 2**64 - 1
+        elif isinstance(cols, int):
+            s.cols = cols
+        else:
+            m = 0
+            for t in cols:
+                m |= 1 << int(t)
+            s.cols = m
+        return s
+
+    def copy(self):
+        g = FieldSelect()
+        ctypes.memmove(ctypes.byref(g), ctypes.byref(self), ctypes.sizeof(FieldSelect))
         return g
 
 
@@ -154,6 +195,8 @@ def lib():
         L.pf_set_scan_kernel.argtypes = [V, I32]
         L.pf_set_scan_filter.argtypes = [V, ctypes.POINTER(CandFilter)]
         L.pf_scan_filter_count.argtypes = [V, ctypes.POINTER(I64)]
+        L.pf_set_scan_select.argtypes = [V, ctypes.POINTER(FieldSelect)]
+        L.pf_fas_pairs_select.argtypes = [V, V, V, I64, ctypes.POINTER(FieldSelect), V]
         L.pf_scan_keys_async.argtypes = [V, V, I32, I32, V, V]
         L.pf_merge_keys_async.argtypes = [V, V, I32, I32, I32, V, V]
         L.pf_decode_keys.argtypes = [V, I32, V, V, V]
@@ -213,6 +256,7 @@ class FasEngine:
         # caller's handle, keeps them alive until a wait covers them or the engine closes
         self._inflight = {}
         self._filter = None  # the candidate filter in force (a CandFilter copy), None = none
+        self._select = None  # the field selection in force (a FieldSelect copy), None = none
         rc = L.pf_open(desc_ptr, device, ctypes.byref(self.h))
         if rc != PF_OK:
             raise FasError(f"pf_open failed ({rc}): {L.pf_last_error(None).decode()}")
@@ -246,9 +290,15 @@ class FasEngine:
         return s
 
     # -- profile_similarity (recommender_similarity.cpp:10-124), batched
-    def fas_pairs(self, a_uid, b_uid):
+    def fas_pairs(self, a_uid, b_uid, select=None):
+        """select (a FieldSelect): the pairs are scored under it (pf_fas_pairs_select); the scan
+        selection in force plays no part either way."""
         a, b = _i32(a_uid), _i32(b_uid)
         out = np.empty(len(a), np.float32)
+        if select is not None:
+            self._check(self._L.pf_fas_pairs_select(self.h, a.ctypes.data, b.ctypes.data, len(a), ctypes.byref(select),
+                                                    out.ctypes.data), "pf_fas_pairs_select")
+            return out
         self._check(self._L.pf_fas_pairs(self.h, a.ctypes.data, b.ctypes.data, len(a), out.ctypes.data),
                     "pf_fas_pairs")
         return out
@@ -325,17 +375,24 @@ class FasEngine:
     recommend_friends_by_interest = recommend_graph_registration
     recommend_friends_collab = recommend_collaborative
 
-    def recommend_interest_all(self, users, topk, filter=None):
+    def recommend_interest_all(self, users, topk, filter=None, select=None):
         """All-candidates interest scan.  filter (a CandFilter): rank only the candidates
-        that pass it; the filter in force before the call is restored afterwards."""
-        if filter is None:
+        that pass it; select (a FieldSelect): score over the selected fields only.  The filter and the
+        selection in force before the call are restored afterwards."""
+        if filter is None and select is None:
             return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
-        prev = self._filter
-        self.set_scan_filter(filter)
+        prev, prev_sel = self._filter, self._select
         try:
+            if filter is not None:
+                self.set_scan_filter(filter)
+            if select is not None:
+                self.set_scan_select(select)
             return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
         finally:
-            self.set_scan_filter(prev)
+            if filter is not None:
+                self.set_scan_filter(prev)
+            if select is not None:
+                self.set_scan_select(prev_sel)
 
     def fof_candidates(self, uid, limit, flavour=PF_FOF_GRAPH):
         cap = max(int(limit), 1) + 1
@@ -374,6 +431,21 @@ class FasEngine:
 
     def clear_scan_filter(self):
         self.set_scan_filter(None)
+
+    # -- field selection of the all-candidates scans (pf_set_scan_select): context state like the filter
+    def set_scan_select(self, select=None, **kw):
+        """Set the selection (a FieldSelect, or FieldSelect.make's keyword arguments); None clears it."""
+        if select is None and kw:
+            select = FieldSelect.make(**kw)
+        if select is None:
+            self._check(self._L.pf_set_scan_select(self.h, None), "pf_set_scan_select")
+            self._select = None
+            return
+        self._check(self._L.pf_set_scan_select(self.h, ctypes.byref(select)), "pf_set_scan_select")
+        self._select = select.copy()
+
+    def clear_scan_select(self):
+        self.set_scan_select(None)
 
     def scan_filter_count(self):
         """Candidates of this context's shard that pass the filter in force (all without one)."""
