@@ -226,9 +226,10 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
             HIPCHK(c, c->d_scores.ensure(npairs * sizeof(float)));
             dsc = c->d_scores.as<float>();
         }
-        HIPCHK(c, pf::launch_pairs(c->ds, c->d_pool.as<uint8_t>(), c->d_refs.as<pf::QImageRef>(), im.max_lds, im.gtab,
-                                   c->d_blocks.as<pf::PairBlock>(), (int)blocks.size(), nullptr, c->d_slots.as<int32_t>(), dsc,
-                                   c->stream, sel));
+        HIPCHK(c, pf::launch_pairs({.st = c->ds, .pool = c->d_pool.as<uint8_t>(), .refs_dev = c->d_refs.as<pf::QImageRef>(),
+                                    .max_lds = im.max_lds, .gtab = im.gtab, .blocks = c->d_blocks.as<pf::PairBlock>(),
+                                    .nblocks = (int)blocks.size(), .order = nullptr, .slots = c->d_slots.as<int32_t>(),
+                                    .out = dsc, .s = c->stream, .sel = sel}));
         c->jb.n_dispatch += !blocks.empty();  // pf_jobs_stats.pair_dispatches counts every K1' dispatch
         const float* res = c->h_scores.as<float>();
         HIPCHK(c, hipMemcpyAsync(c->h_scores.p, dsc, npairs * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -278,9 +279,6 @@ int batch_blocks_per_wg() {
 uint32_t post_image_lds(const pf::QPostHead* h) {
     return pf::post_lds(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend));
 }
-int post_image_per_cu(const pf::QPostHead* h, bool claimed, bool filtered, bool selected) {
-    return pf::post_blocks_per_cu(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), claimed, filtered, selected);
-}
 // LDS a filtered launch takes on top of an image's (the filter's words; pf_kernels.h kFiltLds)
 uint32_t filt_lds(const pf_ctx* c) { return c->filt.fields ? pf::kFiltLds : 0u; }
 
@@ -311,24 +309,18 @@ int one_query_wgs(int resident, bool lanes) {
 int scan_events(pf_ctx* c, bool& timed, hipEvent_t& e0, hipEvent_t& e1) {
     e0 = c->ev0;
     e1 = c->ev1;
-    if (!timed) {
+    const auto untimed = [&] {
+        timed = false;
         c->last_ev0 = c->last_ev1 = nullptr;
-        return PF_OK;
-    }
+        return (int)PF_OK;
+    };
+    if (!timed) return untimed();
     if (c->prof_on) {
         // a timed launch costs ~9 us of stream time (two timestamped events, measured at
         // 231 vs 222 us per single-query step): sampled launches only when asked
-        if (c->prof_seen++ % c->prof_every != 0) {
-            timed = false;
-            c->last_ev0 = c->last_ev1 = nullptr;
-            return PF_OK;
-        }
+        if (c->prof_seen++ % c->prof_every != 0) return untimed();
         if (c->prof_used == c->prof_ev.size()) {
-            if (c->prof_ev.size() >= kProfCap) {  // pool full: the launch runs untimed
-                timed = false;
-                c->last_ev0 = c->last_ev1 = nullptr;
-                return PF_OK;
-            }
+            if (c->prof_ev.size() >= kProfCap) return untimed();  // pool full: the launch runs untimed
             hipEvent_t a, b;
             HIPCHK(c, pf::timing_event(&a));
             HIPCHK(c, pf::timing_event(&b));
@@ -401,109 +393,144 @@ int lane_end(pf_ctx* c, const LaneUse& u, hipEvent_t stop, hipStream_t caller, u
     return PF_OK;
 }
 
+// Workgroups of a one-query K5 launch before the clamp to the shard's blocks (the launches, pf_scan_bytes)
+int one_query_grid(const pf_ctx* c, uint32_t var_lds, bool filtered, bool selected, bool lanes) {
+    return one_query_wgs(c->num_cus * pf::post_blocks_per_cu(var_lds, true, filtered, selected), lanes);
+}
+
+// Where a K5 launch reads its queries: image q at pool + img_off[q] (its QConst there, or at qconst
+// for a resident image), its ScanSync sync[q], its result row out_rows[q]
+struct PostQueries {
+    const uint8_t *pool, *qconst;
+    const uint32_t* img_off;
+    pf::ScanSync* sync;
+    const int32_t* out_rows;
+};
+
+// Prebuilt images in the order `order` with result rows orows, staged as [image offsets | rows |
+// sync | images] and sent to pool_buf in one async copy on s
+int stage_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, const std::vector<int>& order,
+               const std::vector<int32_t>& orows, DBuf& pool_buf, hipStream_t s, PostQueries& Q) {
+    const size_t nq = order.size();
+    std::vector<uint32_t> offs;
+    size_t pool_b = 0;
+    for (size_t i = 0; i < nq; ++i) {
+        offs.push_back((uint32_t)pool_b);
+        pool_b += imgs[order[i]]->size();
+    }
+    const size_t offs_b = (nq * 4 + 15) & ~(size_t)15, rows_b = offs_b, sync_b = nq * sizeof(pf::ScanSync);
+    const size_t total = offs_b + rows_b + sync_b + pool_b;
+    pf::HpLap lw;
+    uint8_t* h = c->stage_acquire(total);
+    lw.lap(pf::kHpScanStageWait);
+    if (!h) return c->fail(PF_ENOMEM, "pinned staging allocation failed");
+    std::memcpy(h, offs.data(), nq * 4);
+    std::memcpy(h + offs_b, orows.data(), nq * 4);
+    std::memset(h + offs_b + rows_b, 0, sync_b);
+    for (size_t i = 0; i < nq; ++i)
+        std::memcpy(h + offs_b + rows_b + sync_b + offs[i], imgs[order[i]]->data(), imgs[order[i]]->size());
+    HIPCHK(c, pool_buf.ensure(total));
+    HIPCHK(c, hipMemcpyAsync(pool_buf.p, h, total, hipMemcpyHostToDevice, s));
+    HIPCHK(c, c->stage_release(s));
+    uint8_t* base = pool_buf.as<uint8_t>();
+    Q = PostQueries{base + offs_b + rows_b + sync_b, nullptr, reinterpret_cast<const uint32_t*>(base),
+                    reinterpret_cast<pf::ScanSync*>(base + offs_b + rows_b), reinterpret_cast<const int32_t*>(base + offs_b)};
+    return PF_OK;
+}
+
+// K5 for one query, into row `row` of d_keys: one resident round of workgroups claims the blocks.  A
+// query on a caller's stream goes to the next scan lane: `place` and the launch run on the lane's
+// stream ls with the lane's buffers, and the row is copied out on the caller's stream after the
+// launch's stop event.  place(ln, ls, Q) puts the query where the launch reads it and fills Q (its row
+// a zero: `out` is the row's address): scan_post uploads it, scan_post_resident points into the images.
+template <class Place>
+int scan_post_one(pf_ctx* c, uint32_t var_lds, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed, Place place) {
+    LaneUse lu;
+    int rc = lane_begin(c, s, lu);
+    if (rc != PF_OK) return rc;
+    pf_ctx::ScanLane* ln = lu.ln;
+    const hipStream_t ls = ln ? ln->st : s;
+    const int blocks = std::max(1, std::min(c->wb_end - c->wb_begin,
+                                            one_query_grid(c, var_lds, c->filt.fields != 0u, c->sel.on != 0u, ln != nullptr)));
+    PostQueries Q;
+    rc = place(ln, ls, Q);
+    if (rc != PF_OK) return rc;
+    DBuf& part_buf = ln ? ln->part : c->d_part;
+    HIPCHK(c, part_buf.ensure((size_t)(blocks + 8) * k * sizeof(uint64_t)));  // + 8 group lists (post_tail)
+    hipEvent_t e0, e1;
+    rc = scan_events(c, timed, e0, e1);
+    if (rc != PF_OK) return rc;
+    // timed: the events ride in the kernel's dispatch (its own start / end; r2ff: 1.8 us less per
+    // launch than two marker packets around it); a lane's stop event is bound to the dispatch likewise
+    const hipEvent_t stop = timed ? e1 : (ln ? ln->done : nullptr);
+    uint64_t* dst = d_keys + (size_t)row * k;
+    HIPCHK(c, pf::launch_post({.ps = c->ps, .pool = Q.pool, .img_off = Q.img_off, .var_lds = var_lds, .nq = 1,
+                               .blk_begin = c->wb_begin, .blk_end = c->wb_end, .k = k, .blocks = blocks,
+                               .parts = part_buf.as<uint64_t>(), .out = ln ? lu.keys : dst, .sync = Q.sync,
+                               .out_rows = Q.out_rows, .claimed = true, .mode = post_mode(true), .e0 = timed ? e0 : nullptr,
+                               .e1 = stop, .s = ls, .qconst = Q.qconst, .filt = c->filt, .sel = c->sel}));
+    // the caller's stream: wait for the lane's launch (its stop event), copy its row out
+    if (ln && (rc = lane_end(c, lu, stop, s, dst, k)) != PF_OK) return rc;
+    if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
+    return PF_OK;
+}
+
 // K5: the postings scan of prebuilt images (pf_types.h QPostHead layout) into d_keys rows
-// `rows`.  Staging: [image offsets | rows | sync | images], one async copy.
+// `rows`: one query by scan_post_one, a batch in one launch per occupancy class.
 int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, const std::vector<int32_t>& rows, int k,
               uint64_t* d_keys, hipStream_t s, bool timed) {
     const int nq = (int)imgs.size();
     if (nq == 0) return PF_OK;
+    if (nq == 1) {  // its upload and launch on the lane's stream (or the caller's, without lanes)
+        const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[0]->data() + sizeof(pf::QConst));
+        return scan_post_one(c, pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), rows[0], k, d_keys, s, timed,
+                             [&](pf_ctx::ScanLane* ln, hipStream_t ls, PostQueries& Q) {
+                                 return stage_post(c, imgs, {0}, {0}, ln ? ln->pool : c->d_pool, ls, Q);
+                             });
+    }
     // LDS classes: a launch's workgroups all take the LDS of its largest query, so the batch goes
     // out in one launch per occupancy class (workgroups per CU), the queries of a class contiguous
     // in the staged arrays; one query with thousands of friends no longer runs every query of a
     // batch at one workgroup per CU
     std::vector<uint32_t> vl(nq);
     std::vector<int> pcu(nq), order(nq);
-    // the hand-out is the call's, not a launch's: a class of one query of a batch stays a batch launch
-    const bool claimed = nq == 1;
     for (int q = 0; q < nq; ++q) {
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q]->data() + sizeof(pf::QConst));
         vl[q] = pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend);
-        pcu[q] = post_image_per_cu(h, claimed, c->filt.fields != 0u, c->sel.on != 0u);
+        // the hand-out is the call's, not a launch's: a class of one query of a batch stays a batch launch
+        pcu[q] = pf::post_blocks_per_cu(vl[q], false, c->filt.fields != 0u, c->sel.on != 0u);
         order[q] = q;
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pcu[a] > pcu[b]; });
-    std::vector<uint32_t> offs;
     std::vector<int32_t> orows(nq);
-    size_t pool_b = 0;
-    for (int i = 0; i < nq; ++i) {
-        offs.push_back((uint32_t)pool_b);
-        pool_b += imgs[order[i]]->size();
-        orows[i] = rows[order[i]];
-    }
-    const uint32_t wave_lds = vl[order[0]];  // the one-query case
+    for (int i = 0; i < nq; ++i) orows[i] = rows[order[i]];
+    // A few blocks per workgroup (batch_blocks_per_wg), so the resident workgroups (dispatched
+    // x-fastest) cover a few queries at a time and share their lists and cells in L2; with one
+    // resident round looping over every query's range instead, as for one query, 256 queries run
+    // at once and L2 hits collapse (per-query time 0.2 ms at 4 queries per launch, 0.68 ms at 1024).
     const int nwb = c->wb_end - c->wb_begin;
-    const int per_cu = pcu[order[0]];
-    // One query: one resident round of workgroups loops over the blocks.  A batch: a few blocks
-    // per workgroup (batch_blocks_per_wg), so the resident workgroups (dispatched x-fastest)
-    // cover a few queries at a time and share their lists and cells in L2; with one resident
-    // round looping over every query's range instead, 256 queries run at once and L2 hits
-    // collapse (per-query time 0.2 ms at 4 queries per launch, 0.68 ms at 1024).
-    const bool on_lane = nq == 1 && scan_lanes() >= 2 && s != c->stream;  // lane_begin's choice, below
-    const int blocks = nq == 1 ? std::max(1, std::min(nwb, one_query_wgs(c->num_cus * per_cu, on_lane)))
-                               : std::max(1, (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg());
-    const size_t offs_b = ((size_t)nq * 4 + 15) & ~(size_t)15;
-    const size_t rows_b = ((size_t)nq * 4 + 15) & ~(size_t)15;
-    const size_t sync_b = (size_t)nq * sizeof(pf::ScanSync);
-    const size_t total = offs_b + rows_b + sync_b + pool_b;
-    // a single query on a caller's stream goes to the next scan lane: its upload and launch on the
-    // lane's stream, its row copied out on the caller's stream
-    LaneUse lu;
-    if (nq == 1) {
-        const int rc = lane_begin(c, s, lu);
-        if (rc != PF_OK) return rc;
-    }
-    pf_ctx::ScanLane* ln = lu.ln;
-    const hipStream_t caller = s;
-    uint64_t* out_keys = d_keys;
-    const int32_t out_row0 = rows[order[0]];
-    if (ln) {
-        s = ln->st;
-        out_keys = lu.keys;
-        orows[0] = 0;  // the lane's own one-row result
-    }
-    DBuf& pool_buf = ln ? ln->pool : c->d_pool;
-    DBuf& part_buf = ln ? ln->part : c->d_part;
-    pf::HpLap lw;
-    uint8_t* h = c->stage_acquire(total);
-    lw.lap(pf::kHpScanStageWait);
-    if (!h) return c->fail(PF_ENOMEM, "pinned staging allocation failed");
-    std::memcpy(h, offs.data(), (size_t)nq * 4);
-    std::memcpy(h + offs_b, orows.data(), (size_t)nq * 4);
-    std::memset(h + offs_b + rows_b, 0, sync_b);
-    for (int i = 0; i < nq; ++i)
-        std::memcpy(h + offs_b + rows_b + sync_b + offs[i], imgs[order[i]]->data(), imgs[order[i]]->size());
-    HIPCHK(c, pool_buf.ensure(total));
-    HIPCHK(c, hipMemcpyAsync(pool_buf.p, h, total, hipMemcpyHostToDevice, s));
-    HIPCHK(c, c->stage_release(s));
-    uint8_t* base = pool_buf.as<uint8_t>();
-    HIPCHK(c, part_buf.ensure((size_t)nq * (blocks + 8) * k * sizeof(uint64_t)));  // + 8 group lists (post_tail)
-    hipEvent_t e0, e1;
-    int rc = scan_events(c, timed, e0, e1);
+    const int blocks = std::max(1, (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg());
+    PostQueries Q;
+    int rc = stage_post(c, imgs, order, orows, c->d_pool, s, Q);
     if (rc != PF_OK) return rc;
-    // timed: the events ride in the kernel's dispatch (its own start / end; r2ff: 1.8 us less
-    // per launch than two marker packets around it)
-    // one launch per class (the first one's start and the last one's end time the call)
+    HIPCHK(c, c->d_part.ensure((size_t)nq * (blocks + 8) * k * sizeof(uint64_t)));  // + 8 group lists (post_tail)
+    hipEvent_t e0, e1;
+    rc = scan_events(c, timed, e0, e1);
+    if (rc != PF_OK) return rc;
+    // one launch per class (timed: the first one's start and the last one's end time the call)
     for (int q0 = 0; q0 < nq;) {
         int q1 = q0;
         uint32_t vmax = 0;
         while (q1 < nq && pcu[order[q1]] == pcu[order[q0]]) vmax = std::max(vmax, vl[order[q1++]]);
-        HIPCHK(c, pf::launch_post(c->ps, base + offs_b + rows_b + sync_b, reinterpret_cast<const uint32_t*>(base) + q0,
-                                  nq == 1 ? wave_lds : vmax, q1 - q0, c->wb_begin, c->wb_end, k, blocks,
-                                  part_buf.as<uint64_t>() + (size_t)q0 * (blocks + 8) * k,
-                                  reinterpret_cast<pf::ScanSync*>(base + offs_b + rows_b) + q0, out_keys,
-                                  reinterpret_cast<const int32_t*>(base + offs_b) + q0, claimed,
-                                  post_mode(claimed), (timed && q0 == 0) ? e0 : nullptr,
-                                  (timed && q1 == nq) ? e1 : (ln ? ln->done : nullptr), s, nullptr, c->filt, c->sel));
+        HIPCHK(c, pf::launch_post({.ps = c->ps, .pool = Q.pool, .img_off = Q.img_off + q0, .var_lds = vmax, .nq = q1 - q0,
+                                   .blk_begin = c->wb_begin, .blk_end = c->wb_end, .k = k, .blocks = blocks,
+                                   .parts = c->d_part.as<uint64_t>() + (size_t)q0 * (blocks + 8) * k, .out = d_keys,
+                                   .sync = Q.sync + q0, .out_rows = Q.out_rows + q0, .claimed = false, .mode = post_mode(false),
+                                   .e0 = (timed && q0 == 0) ? e0 : nullptr, .e1 = (timed && q1 == nq) ? e1 : nullptr, .s = s,
+                                   .qconst = nullptr, .filt = c->filt, .sel = c->sel}));
         q0 = q1;
     }
-    if (ln) {  // the caller's stream: wait for the lane's launch (its stop event), copy its row out
-        rc = lane_end(c, lu, (timed ? e1 : ln->done), caller, d_keys + (size_t)out_row0 * k, k);
-        if (rc != PF_OK) return rc;
-    }
-    if (timed) {
-        c->last_ev0 = e0;
-        c->last_ev1 = e1;
-    }
+    if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
     return PF_OK;
 }
 
@@ -520,41 +547,16 @@ bool resident_ok(const pf_ctx* c, int32_t i) {
 
 int scan_post_resident(pf_ctx* c, int32_t i, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
     auto& R = c->rp;
-    const uint32_t vl = R.var_lds[i];
-    const int per_cu = pf::post_blocks_per_cu(vl, true, c->filt.fields != 0u, c->sel.on != 0u);
-    const int nwb = c->wb_end - c->wb_begin;
-    LaneUse lu;
-    int rc = lane_begin(c, s, lu);
-    if (rc != PF_OK) return rc;
-    pf_ctx::ScanLane* ln = lu.ln;
-    const int blocks = std::max(1, std::min(nwb, one_query_wgs(c->num_cus * per_cu, ln != nullptr)));
-    const hipStream_t ls = ln ? ln->st : s;
-    DBuf& part_buf = ln ? ln->part : c->d_part;
-    DBuf& sync_buf = ln ? ln->sync : R.d_sync;
-    if (!sync_buf.p) {  // once: every launch leaves it zeroed
-        HIPCHK(c, sync_buf.ensure(sizeof(pf::ScanSync)));
-        HIPCHK(c, hipMemsetAsync(sync_buf.p, 0, sizeof(pf::ScanSync), ls));
-    }
-    HIPCHK(c, part_buf.ensure((size_t)(blocks + 8) * k * sizeof(uint64_t)));  // + 8 group lists (post_tail)
-    hipEvent_t e0, e1;
-    rc = scan_events(c, timed, e0, e1);
-    if (rc != PF_OK) return rc;
-    hipEvent_t stop = timed ? e1 : (ln ? ln->done : nullptr);
-    uint64_t* out = ln ? lu.keys : d_keys + (size_t)row * k;
-    const uint8_t* img = R.d_pool.as<uint8_t>() + R.off[i] - sizeof(pf::QConst);
-    const uint8_t* qc = c->jb.d_pimg.as<uint8_t>() + c->jb.pimg_off[i];
-    HIPCHK(c, pf::launch_post(c->ps, img, R.d_zero.as<uint32_t>(), vl, 1, c->wb_begin, c->wb_end, k, blocks,
-                              part_buf.as<uint64_t>(), sync_buf.as<pf::ScanSync>(), out, R.d_zero.as<int32_t>(),
-                              true, post_mode(true), timed ? e0 : nullptr, stop, ls, qc, c->filt, c->sel));
-    if (ln) {
-        rc = lane_end(c, lu, stop, s, d_keys + (size_t)row * k, k);
-        if (rc != PF_OK) return rc;
-    }
-    if (timed) {
-        c->last_ev0 = e0;
-        c->last_ev1 = e1;
-    }
-    return PF_OK;
+    return scan_post_one(c, R.var_lds[i], row, k, d_keys, s, timed, [&](pf_ctx::ScanLane* ln, hipStream_t ls, PostQueries& Q) {
+        DBuf& sync_buf = ln ? ln->sync : R.d_sync;
+        if (!sync_buf.p) {  // once: every launch leaves it zeroed
+            HIPCHK(c, sync_buf.ensure(sizeof(pf::ScanSync)));
+            HIPCHK(c, hipMemsetAsync(sync_buf.p, 0, sizeof(pf::ScanSync), ls));
+        }
+        Q = PostQueries{R.d_pool.as<uint8_t>() + R.off[i] - sizeof(pf::QConst), c->jb.d_pimg.as<uint8_t>() + c->jb.pimg_off[i],
+                        R.d_zero.as<uint32_t>(), sync_buf.as<pf::ScanSync>(), R.d_zero.as<int32_t>()};
+        return (int)PF_OK;
+    });
 }
 
 // Every user's K5 image part (ResidentPost) built once at open: host threads write the parts of a
@@ -693,8 +695,10 @@ int scan_stream(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<in
     int rc = scan_events(c, timed, e0, e1);
     if (rc != PF_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(e0, s));
-    HIPCHK(c, pf::launch_scan(c->ds, d_images, d_refs, im.max_lds, im.gtab, nq, c->tile_begin, c->tile_end, k, blocks,
-                              c->d_part.as<uint64_t>(), d_sync, d_keys, d_rows, s, c->filt, c->sel));
+    HIPCHK(c, pf::launch_scan({.st = c->ds, .pool = d_images, .refs_dev = d_refs, .lds = im.max_lds, .gtab = im.gtab, .nq = nq,
+                               .tile_begin = c->tile_begin, .tile_end = c->tile_end, .k = k, .blocks = blocks,
+                               .parts = c->d_part.as<uint64_t>(), .out = d_keys, .sync = d_sync, .out_rows = d_rows, .s = s,
+                               .filt = c->filt, .sel = c->sel}));
     if (timed) {
         HIPCHK(c, hipEventRecord(e1, s));
         c->last_ev0 = e0;
@@ -1422,7 +1426,7 @@ int pf_scan_bytes(pf_ctx* c, const int32_t* q, int32_t nq, int64_t* out) {
     }
     // workgroups that stage a query's image, as scan_post launches the fitting queries
     const int nwb = c->wb_end - c->wb_begin;
-    const int wgs = nfit == 1 ? one_query_wgs(c->num_cus * pf::post_blocks_per_cu(pf::post_var_lds(max_tok, max_lists), true, false, false), true)
+    const int wgs = nfit == 1 ? one_query_grid(c, pf::post_var_lds(max_tok, max_lists), false, false, true)
                               : (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg();
     par_jobs((size_t)nq, [&](size_t i) {
         out[i] = kind[i] == 0 ? 0 : (kind[i] == 2 ? k1 : post_query_bytes(c, imgs[i], wgs));

@@ -56,6 +56,36 @@ static __device__ __attribute__((noinline)) double ratio_term(const QConst& q, i
     return term_of(q, slot, (double)lo / (double)hi);
 }
 
+// The reference's seven fixed terms (recommender_similarity.cpp:38-91) and its final score, once: every
+// kernel unpacks its own header format and runs this text.  The five header terms of a candidate with public /
+// gender codes pb, gb, completion cb, age ab and regions r0..r2, in the reference's order; used counts them.
+__device__ __forceinline__ void header_terms(const QConst& q, uint32_t pb, uint32_t gb, int cb, int ab, int r0, int r1,
+                                             int r2, double& sum, int& used) {
+    if (q.pubcode != kCodeMissing && pb != kCodeMissing) { sum += q.sig_pub[pb == q.pubcode]; ++used; }
+    if (q.gencode != kCodeMissing && gb != kCodeMissing) { sum += q.sig_gen[gb == q.gencode]; ++used; }
+    if (q.comp > 0 && cb > 0) { sum += cb <= kValTab ? q.sig_comp[cb] : ratio_term(q, PF_F_COMPLETION, q.comp, cb); ++used; }
+    if (q.age > 0 && ab > 0) { sum += ab <= kValTab ? q.sig_age[ab] : ratio_term(q, PF_F_AGE, q.age, ab); ++used; }
+    const int bcnt = (r0 >= 0) + (r1 >= 0) + (r2 >= 0);
+    if (q.a_regcnt > 0 && bcnt > 0) {
+        const int m = (r0 >= 0 && r0 == q.reg[0]) + (r1 >= 0 && r1 == q.reg[1]) + (r2 >= 0 && r2 == q.reg[2]);
+        sum += q.sig_reg[bcnt][m];
+        ++used;
+    }
+}
+// The two set terms after them: the candidate's nc clubs and nf friends, ic / ifr of them the query's
+// (the pair epilogue computes these two through its item queue and keeps only the bookkeeping).
+__device__ __forceinline__ void set_terms(const QConst& q, int ic, uint32_t nc, int ifr, uint32_t nf, double& sum, int& used) {
+    if (q.n_clubs > 0 && nc > 0) { sum += ic == 0 ? q.sig0_clubs : set_term(q, PF_F_CLUBS, ic, (int)nc, q.sqrt_clubs); ++used; }
+    if (q.n_friends > 0 && nf > 0) { sum += ifr == 0 ? q.sig0_friends : set_term(q, PF_F_FRIENDS, ifr, (int)nf, q.sqrt_friends); ++used; }
+}
+// recommender_similarity.cpp:114-123; F = used / (kNumFixed + the query's columns), divided or looked up by the caller
+__device__ __forceinline__ float fas_score(double sum, int used, double F) {
+    if (used == 0) return 0.0f;
+    const double S = sum / (double)used;
+    if (S <= 0.0 && F <= 0.0) return 0.0f;
+    return (float)((2.0 * S * F) / (S + F));
+}
+
 // ---------------------------------------------------------------- query hash (cuckoo)
 struct QView {
     const QConst* q;

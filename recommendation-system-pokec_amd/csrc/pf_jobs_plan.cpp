@@ -1075,8 +1075,9 @@ int enqueue_chunk(pf_ctx* c, const ChunkPlan& cp, const PlanLayout& L, JobsState
         HIPCHK(c, hipEventRecord(pe0, st.sp));
     }
     for (int k = 0, o = 0; k < 3; o += cp.nb_c[k++]) {  // the pair-scoring stage (timed)
-        HIPCHK(c, launch_pairs(c->ds, ipl, L.refs.at(d), cp.lds_c[k], k == 2, d_blk + o, cp.nb_c[k], d_ord + o, slots, fl,
-                               st.sp, cp.sel));
+        HIPCHK(c, launch_pairs({.st = c->ds, .pool = ipl, .refs_dev = L.refs.at(d), .max_lds = cp.lds_c[k], .gtab = k == 2,
+                                .blocks = d_blk + o, .nblocks = cp.nb_c[k], .order = d_ord + o, .slots = slots, .out = fl,
+                                .s = st.sp, .sel = cp.sel}));
         J.n_dispatch += cp.nb_c[k] > 0;
     }
     if (pe1) {

@@ -26,46 +26,72 @@ struct PairGen {
     int32_t nf, nch, cap, cand, fl, stride, out, first;
 };
 
-
-// lds: dynamic LDS bytes per block = max over the batch of
-//   sizeof(QConst) + staged keys/vals + n_hits_max * threads + 2048
-// gtab: at least one image of the batch probes its table in global memory (lds_bytes == 0);
-// the whole launch then uses the global-table variant.
-// sel (by value in the launch's arguments; on == 0: none): the context's field selection
-// (pf_select.h), applied to each block's staged copy of its query's constants.
-hipError_t launch_scan(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t lds, bool gtab,
-                       int nq, int tile_begin, int tile_end, int k, int blocks, uint64_t* parts, ScanSync* sync,
-                       uint64_t* out, const int32_t* out_rows, hipStream_t s, const CandFilter& filt,
-                       const FieldSel& sel);
+// Each launcher takes one descriptor, filled with named members at the call; no member has a default,
+// and a call that leaves out a reference does not compile.  A kernel's run-time choice of instantiation
+// is made by one function in pf_kernels.hip, which its launch and its occupancy query both go through.
+// K1, the record-stream scan of tiles [tile_begin, tile_end) for nq query images
+struct ScanLaunch {
+    const DevStore& st;  // st.packed and gtab are the instantiation
+    const uint8_t* pool;
+    const QImageRef* refs_dev;
+    // dynamic LDS bytes per block = max over the batch of sizeof(QConst) + staged keys/vals + n_hits_max * threads + 2048
+    uint32_t lds;
+    // at least one image of the batch probes its table in global memory (lds_bytes == 0); the whole
+    // launch then uses the global-table variant
+    bool gtab;
+    int nq, tile_begin, tile_end, k, blocks;
+    uint64_t *parts, *out;
+    ScanSync* sync;
+    const int32_t* out_rows;
+    hipStream_t s;
+    const CandFilter& filt;  // by value in the launch's arguments (fields == 0: none): pf_filter.h
+    // by value likewise (on == 0: none): the context's field selection (pf_select.h), applied to
+    // each block's staged copy of its query's constants
+    const FieldSel& sel;
+};
+hipError_t launch_scan(const ScanLaunch& L);
 // resident scan blocks per CU at this dynamic LDS size (HIP occupancy API)
 int scan_blocks_per_cu(bool packed, bool gtab, uint32_t lds);
 // K5 postings scan over candidate blocks [blk_begin, blk_end) for nq query images (byte
 // offsets img_off[] into pool); var_lds = post_var_lds(max n_tok, max lists of an image)
 uint32_t post_var_lds(int n_tok, int n_lists);
 uint32_t post_lds(uint32_t var_lds);
-// claimed: the block hand-out, which is the instantiation.  true (nq == 1 only): the grid's workgroups
-// claim every block per XCD group; false: workgroup x of query y takes every blocks-th block of the
-// range, in XCD-contiguous order (the batches, a class of one query of a batch included).
-// qconst: nullptr (each image starts with its QConst) or, for a one-query launch from the resident
-// images, the user's QConst elsewhere (its K1' resident image); img = the resident part's start
-// minus sizeof(QConst).  The launch leaves each query's ScanSync zeroed (post_tail).
-// mode: flags (pf_api.cpp post_mode).  Claimed launches only: kPostPrune = drop candidates below the
+// mode flags (pf_api.cpp post_mode).  Claimed launches only: kPostPrune = drop candidates below the
 // query's shared score threshold (pf_prune.h), kPostPruneBlockOnly = at block starts only,
 // kPostPruneStats = count them.  kPostFiltKeepBlocks (filtered launches, A/B): a block in which no
 // candidate passes the filter runs to its end instead of leaving after its first barrier.
-// filt (by value in the launch's arguments; fields == 0: none): the context's candidate filter
-// (pf_filter.h); a filtered launch takes the FILT instantiation of its hand-out.
-// sel (by value likewise; on == 0: none): the context's field selection (pf_select.h); a selected
-// launch takes the SEL instantiation, which patches its staged copy of the query's constants and
-// leaves the deselected columns and set lists out of its tables.  It needs no LDS of its own.
 constexpr uint32_t kPostPrune = 1u << 16, kPostPruneStats = 1u << 17, kPostPruneBlockOnly = 1u << 18;
 constexpr uint32_t kPostFiltKeepBlocks = 1u << 19;
 // dynamic LDS a filtered launch takes on top of post_lds(var_lds): the filter, parked past the query's tables
 constexpr uint32_t kFiltLds = (uint32_t)sizeof(CandFilter);
-hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t* img_off, uint32_t var_lds, int nq,
-                       int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
-                       const int32_t* out_rows, bool claimed, uint32_t mode, hipEvent_t e0, hipEvent_t e1,
-                       hipStream_t s, const uint8_t* qconst, const CandFilter& filt, const FieldSel& sel);
+struct PostLaunch {
+    const PostStore& ps;
+    const uint8_t* pool;
+    const uint32_t* img_off;
+    uint32_t var_lds;
+    int nq, blk_begin, blk_end, k, blocks;
+    uint64_t *parts, *out;
+    ScanSync* sync;  // the launch leaves each query's ScanSync zeroed (post_tail)
+    const int32_t* out_rows;
+    // the block hand-out, which is the instantiation.  true (nq == 1 only): the grid's workgroups
+    // claim every block per XCD group; false: workgroup x of query y takes every blocks-th block of
+    // the range, in XCD-contiguous order (the batches, a class of one query of a batch included)
+    bool claimed;
+    uint32_t mode;
+    // timed launches (both given): the kernel's own start and end timestamps, taken from its dispatch
+    hipEvent_t e0, e1;
+    hipStream_t s;
+    // nullptr (each image starts with its QConst) or, for a one-query launch from the resident images, the
+    // user's QConst elsewhere (its K1' resident image); the image = the resident part's start minus sizeof(QConst)
+    const uint8_t* qconst;
+    // by value in the launch's arguments (fields == 0: none): the context's candidate filter (pf_filter.h)
+    const CandFilter& filt;
+    // by value likewise (on == 0: none): the context's field selection (pf_select.h); a selected
+    // launch takes the SEL instantiation, which patches its staged copy of the query's constants and
+    // leaves the deselected columns and set lists out of its tables.  It needs no LDS of its own.
+    const FieldSel& sel;
+};
+hipError_t launch_post(const PostLaunch& L);
 // workgroups per CU of the instantiation launch_post takes for `claimed`, `filtered` (a filter is
 // set) and `selected` (a field selection is set)
 int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered, bool selected);
@@ -80,11 +106,21 @@ hipError_t k5_prune_stats_read(unsigned long long* out, bool reset);
 // plain merge of key lists (cross-shard merge after the all-gather)
 hipError_t launch_merge(const uint64_t* in, int nparts, int64_t part_stride, int64_t query_stride, int nq, int k,
                         uint64_t* out, hipStream_t s);
-// order (nullable): the dispatch order, block blockIdx.x scores blocks[order[blockIdx.x]]
-// sel (on == 0: none): a field selection applied to every block's staged constants (pf_fas_pairs_select,
-// the pair stage of an all-candidates job chunk)
-hipError_t launch_pairs(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t max_lds,
-                        bool gtab, const PairBlock* blocks, int nblocks, const int32_t* order, const int32_t* slots,
-                        float* out, hipStream_t s, const FieldSel& sel = FieldSel{});
+// K1', one workgroup per PairBlock
+struct PairsLaunch {
+    const DevStore& st;  // st.packed and gtab are the instantiation
+    const uint8_t* pool;
+    const QImageRef* refs_dev;
+    uint32_t max_lds;
+    bool gtab;
+    const PairBlock* blocks;
+    int nblocks;
+    const int32_t *order, *slots;  // order (nullable): the dispatch order, block blockIdx.x scores blocks[order[blockIdx.x]]
+    float* out;
+    hipStream_t s;
+    // on == 0: none; applied to every block's staged constants (pf_fas_pairs_select, the pair stage of a job chunk)
+    const FieldSel& sel;
+};
+hipError_t launch_pairs(const PairsLaunch& L);
 
 }  // namespace pf

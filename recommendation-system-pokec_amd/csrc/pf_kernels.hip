@@ -340,28 +340,8 @@ __device__ __forceinline__ float fas_epilogue(const QView& v, const Rec& rec, co
 
     double sum = 0.0;
     int used = 0;
-    const uint32_t pb = h2.x & 0xFFu, gb = (h2.x >> 8) & 0xFFu;
-    if (q.pubcode != kCodeMissing && pb != kCodeMissing) { sum += q.sig_pub[pb == q.pubcode]; ++used; }
-    if (q.gencode != kCodeMissing && gb != kCodeMissing) { sum += q.sig_gen[gb == q.gencode]; ++used; }
-    const int cb = (int)h0.z, ab = (int)h0.w;
-    if (q.comp > 0 && cb > 0) { sum += cb <= kValTab ? q.sig_comp[cb] : ratio_term(q, PF_F_COMPLETION, q.comp, cb); ++used; }
-    if (q.age > 0 && ab > 0) { sum += ab <= kValTab ? q.sig_age[ab] : ratio_term(q, PF_F_AGE, q.age, ab); ++used; }
-    const int r0 = (int)h1.x, r1 = (int)h1.y, r2 = (int)h1.z;
-    const int bcnt = (r0 >= 0) + (r1 >= 0) + (r2 >= 0);
-    if (q.a_regcnt > 0 && bcnt > 0) {
-        const int m = (r0 >= 0 && r0 == q.reg[0]) + (r1 >= 0 && r1 == q.reg[1]) + (r2 >= 0 && r2 == q.reg[2]);
-        sum += q.sig_reg[bcnt][m];
-        ++used;
-    }
-    const int ic = (int)(cnt & 0xFFFFu), ifr = (int)(cnt >> 16);
-    if (q.n_clubs > 0 && nc > 0) {
-        sum += ic == 0 ? q.sig0_clubs : set_term(q, PF_F_CLUBS, ic, (int)nc, q.sqrt_clubs);
-        ++used;
-    }
-    if (q.n_friends > 0 && nf > 0) {
-        sum += ifr == 0 ? q.sig0_friends : set_term(q, PF_F_FRIENDS, ifr, (int)nf, q.sqrt_friends);
-        ++used;
-    }
+    header_terms(q, h2.x & 0xFFu, (h2.x >> 8) & 0xFFu, (int)h0.z, (int)h0.w, (int)h1.x, (int)h1.y, (int)h1.z, sum, used);
+    set_terms(q, (int)(cnt & 0xFFFFu), nc, (int)(cnt >> 16), nf, sum, used);
     used += __popcll(common);
     if (tep) tep[0] = clock64();
     if (!overflow) {
@@ -402,12 +382,7 @@ __device__ __forceinline__ float fas_epilogue(const QView& v, const Rec& rec, co
         sum = text_terms_slow<PACKED>(v, rec, nc + nf, record_words(h2, PACKED), cmask, sum);
     }
     if (tep) tep[1] = clock64();
-    if (used == 0) return 0.0f;
-    // recommender_similarity.cpp:114-123
-    const double S = sum / (double)used;
-    const double F = (double)used / (double)(kNumFixed + q.n_cols);
-    if (S <= 0.0 && F <= 0.0) return 0.0f;
-    return (float)((2.0 * S * F) / (S + F));
+    return fas_score(sum, used, (double)used / (double)(kNumFixed + q.n_cols));
 }
 
 // ---------------------------------------------------------------- K1' record walk (packed)
@@ -570,19 +545,7 @@ __device__ __forceinline__ float pair_epilogue(const QView& v, const DevStore& s
     // every active lane: the fixed terms (an overflowed lane computes its set terms itself)
     double sum = 0.0;
     int used = 0;
-    const uint32_t pb = h2.x & 0xFFu, gb = (h2.x >> 8) & 0xFFu;
-    if (q.pubcode != kCodeMissing && pb != kCodeMissing) { sum += q.sig_pub[pb == q.pubcode]; ++used; }
-    if (q.gencode != kCodeMissing && gb != kCodeMissing) { sum += q.sig_gen[gb == q.gencode]; ++used; }
-    const int cb = (int)h0.z, ab = (int)h0.w;
-    if (q.comp > 0 && cb > 0) { sum += cb <= kValTab ? q.sig_comp[cb] : ratio_term(q, PF_F_COMPLETION, q.comp, cb); ++used; }
-    if (q.age > 0 && ab > 0) { sum += ab <= kValTab ? q.sig_age[ab] : ratio_term(q, PF_F_AGE, q.age, ab); ++used; }
-    const int r0 = (int)h1.x, r1 = (int)h1.y, r2 = (int)h1.z;
-    const int bcnt = (r0 >= 0) + (r1 >= 0) + (r2 >= 0);
-    if (q.a_regcnt > 0 && bcnt > 0) {
-        const int m = (r0 >= 0 && r0 == q.reg[0]) + (r1 >= 0 && r1 == q.reg[1]) + (r2 >= 0 && r2 == q.reg[2]);
-        sum += q.sig_reg[bcnt][m];
-        ++used;
-    }
+    header_terms(q, h2.x & 0xFFu, (h2.x >> 8) & 0xFFu, (int)h0.z, (int)h0.w, (int)h1.x, (int)h1.y, (int)h1.z, sum, used);
     const bool has_clubs = q.n_clubs > 0 && nc > 0, has_friends = q.n_friends > 0 && nf > 0;
     used += (has_clubs ? 1 : 0) + (has_friends ? 1 : 0);
     uint64_t common = q.colmask & cmask;
@@ -710,12 +673,8 @@ __device__ __forceinline__ float pair_epilogue(const QView& v, const DevStore& s
         if (lane == l) sum = sl;
     }
     if (tep) tep[2] = clock64();
-    if (!active || used == 0) return 0.0f;
-    // recommender_similarity.cpp:114-123
-    const double S = sum / (double)used;
-    const double F = (double)used / (double)(kNumFixed + q.n_cols);
-    if (S <= 0.0 && F <= 0.0) return 0.0f;
-    return (float)((2.0 * S * F) / (S + F));
+    if (!active) return 0.0f;
+    return fas_score(sum, used, (double)used / (double)(kNumFixed + q.n_cols));
 }
 
 // FAS of slot p by one lane alone (pairs kernel): the lane walks the slot's record in the row
@@ -1710,23 +1669,9 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
             pend[kk] = cm & q.colmask;
             double s = 0.0;
             int u = 0;
-            const uint32_t pb = (ha[kk].y >> 16) & 0xFFu, gb = ha[kk].y >> 24;
-            if (q.pubcode != kCodeMissing && pb != kCodeMissing) { s += q.sig_pub[pb == q.pubcode]; ++u; }
-            if (q.gencode != kCodeMissing && gb != kCodeMissing) { s += q.sig_gen[gb == q.gencode]; ++u; }
-            const int cb = (int)(int16_t)(ha[kk].z & 0xFFFFu), ab = (int)(int16_t)(ha[kk].z >> 16);
-            if (q.comp > 0 && cb > 0) { s += cb <= kValTab ? q.sig_comp[cb] : ratio_term(q, PF_F_COMPLETION, q.comp, cb); ++u; }
-            if (q.age > 0 && ab > 0) { s += ab <= kValTab ? q.sig_age[ab] : ratio_term(q, PF_F_AGE, q.age, ab); ++u; }
-            const int r0 = (int)hb[kk].x, r1 = (int)hb[kk].y, r2 = (int)hb[kk].z;
-            const int bcnt = (r0 >= 0) + (r1 >= 0) + (r2 >= 0);
-            if (q.a_regcnt > 0 && bcnt > 0) {
-                const int m = (r0 >= 0 && r0 == q.reg[0]) + (r1 >= 0 && r1 == q.reg[1]) + (r2 >= 0 && r2 == q.reg[2]);
-                s += q.sig_reg[bcnt][m];
-                ++u;
-            }
-            const uint32_t nc = ha[kk].w & 0xFFFFu, nf = ha[kk].w >> 16;
-            const int ic = (int)(ct & 0xFFFFu), ifr = (int)(ct >> 16);
-            if (q.n_clubs > 0 && nc > 0) { s += ic == 0 ? q.sig0_clubs : set_term(q, PF_F_CLUBS, ic, (int)nc, q.sqrt_clubs); ++u; }
-            if (q.n_friends > 0 && nf > 0) { s += ifr == 0 ? q.sig0_friends : set_term(q, PF_F_FRIENDS, ifr, (int)nf, q.sqrt_friends); ++u; }
+            header_terms(q, (ha[kk].y >> 16) & 0xFFu, ha[kk].y >> 24, (int)(int16_t)(ha[kk].z & 0xFFFFu),
+                         (int)(int16_t)(ha[kk].z >> 16), (int)hb[kk].x, (int)hb[kk].y, (int)hb[kk].z, s, u);
+            set_terms(q, (int)(ct & 0xFFFFu), ha[kk].w & 0xFFFFu, (int)(ct >> 16), ha[kk].w >> 16, s, u);
             sum[kk] = s;
             used |= (uint32_t)(u + __popcll(pend[kk])) << (8 * kk);
         }
@@ -2043,13 +1988,8 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         for (int kk = 0; kk < kCandsPerThread; ++kk) {
             uint64_t key = ~0ull;
             if (!((skip >> kk) & 1u)) {
-                float f = 0.0f;
                 const int uk = (int)((used >> (8 * kk)) & 0xFFu);
-                if (uk > 0) {
-                    const double S = sum[kk] / (double)uk;
-                    const double Fv = ftab[uk];  // (double)uk / (double)(kNumFixed + q.n_cols)
-                    f = (S <= 0.0 && Fv <= 0.0) ? 0.0f : (float)((2.0 * S * Fv) / (S + Fv));
-                }
+                const float f = fas_score(sum[kk], uk, ftab[uk]);  // (double)uk / (double)(kNumFixed + q.n_cols)
                 // keyed by idx (idx order = uid order); uids are filled in before the merge
                 key = score_key(f, (int32_t)(c0 + kk * kPostThreads + tid));
             }
@@ -2242,16 +2182,34 @@ hipError_t launch_filter_count(const PostStore& ps, const DevStore& st, int32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_scan(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t lds, bool gtab,
-                       int nq, int tile_begin, int tile_end, int k, int blocks, uint64_t* parts, ScanSync* sync,
-                       uint64_t* out, const int32_t* out_rows, hipStream_t s, const CandFilter& filt, const FieldSel& sel) {
-    if (nq <= 0) return hipSuccess;
-    dim3 grid(blocks, nq), block(kScanThreads);
-#define PF_SCAN(P, G) hipLaunchKernelGGL((fas_scan_kernel<P, G>), grid, block, lds, s, st, pool, refs_dev, tile_begin, \
-                                         tile_end, k, parts, sync, out, out_rows, filt, sel)
-    if (st.packed) { if (gtab) PF_SCAN(true, true); else PF_SCAN(true, false); }
-    else { if (gtab) PF_SCAN(false, true); else PF_SCAN(false, false); }
-#undef PF_SCAN
+// The instantiation a launch's run-time choice names, one function per kernel template: the launch
+// and the occupancy query both ask it, so they cannot disagree, and a new template parameter is one
+// more dimension of its table.
+using ScanKernel = decltype(&fas_scan_kernel<false, false>);
+static ScanKernel scan_kernel(bool packed, bool gtab) {
+    static constexpr ScanKernel tab[2][2] = {{fas_scan_kernel<false, false>, fas_scan_kernel<false, true>},
+                                             {fas_scan_kernel<true, false>, fas_scan_kernel<true, true>}};
+    return tab[packed][gtab];
+}
+using PairsKernel = decltype(&fas_pairs_kernel<false, false>);
+static PairsKernel pairs_kernel(bool packed, bool gtab) {
+    static constexpr PairsKernel tab[2][2] = {{fas_pairs_kernel<false, false>, fas_pairs_kernel<false, true>},
+                                              {fas_pairs_kernel<true, false>, fas_pairs_kernel<true, true>}};
+    return tab[packed][gtab];
+}
+using PostKernel = decltype(&fas_post_kernel<false, false, false>);
+static PostKernel post_kernel(bool claimed, bool filtered, bool selected) {
+    static constexpr PostKernel tab[2][2][2] = {{{fas_post_kernel<false, false, false>, fas_post_kernel<false, false, true>},
+                                                 {fas_post_kernel<false, true, false>, fas_post_kernel<false, true, true>}},
+                                                {{fas_post_kernel<true, false, false>, fas_post_kernel<true, false, true>},
+                                                 {fas_post_kernel<true, true, false>, fas_post_kernel<true, true, true>}}};
+    return tab[claimed][filtered][selected];
+}
+
+hipError_t launch_scan(const ScanLaunch& L) {
+    if (L.nq <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scan_kernel(L.st.packed, L.gtab), dim3(L.blocks, L.nq), dim3(kScanThreads), L.lds, L.s, L.st, L.pool,
+                       L.refs_dev, L.tile_begin, L.tile_end, L.k, L.parts, L.sync, L.out, L.out_rows, L.filt, L.sel);
     return hipGetLastError();
 }
 
@@ -2262,11 +2220,7 @@ int scan_blocks_per_cu(bool packed, bool gtab, uint32_t lds) {
     const uint64_t key = ((uint64_t)lds << 2) | ((uint64_t)packed << 1) | (uint64_t)gtab;
     if (key == last_key) return last_nb;
     int nb = 0;
-    hipError_t e;
-    if (packed) e = gtab ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_scan_kernel<true, true>, kScanThreads, lds)
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_scan_kernel<true, false>, kScanThreads, lds);
-    else e = gtab ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_scan_kernel<false, true>, kScanThreads, lds)
-                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_scan_kernel<false, false>, kScanThreads, lds);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, scan_kernel(packed, gtab), kScanThreads, lds);
     last_key = key;
     last_nb = (e == hipSuccess && nb > 0) ? nb : 1;
     return last_nb;
@@ -2325,34 +2279,22 @@ static void blog_report(int nbx) {
 }
 #endif
 
-hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t* img_off, uint32_t var_lds, int nq,
-                       int blk_begin, int blk_end, int k, int blocks, uint64_t* parts, ScanSync* sync, uint64_t* out,
-                       const int32_t* out_rows, bool claimed, uint32_t mode, hipEvent_t e0, hipEvent_t e1,
-                       hipStream_t s, const uint8_t* qconst, const CandFilter& filt, const FieldSel& sel) {
-    if (nq <= 0) return hipSuccess;
+hipError_t launch_post(const PostLaunch& L) {
+    if (L.nq <= 0) return hipSuccess;
     // the claimed hand-out is the one-query instantiation's and nobody else's
-    if (claimed && nq != 1) return hipErrorInvalidValue;
+    if (L.claimed && L.nq != 1) return hipErrorInvalidValue;
+    const uint32_t lds = post_lds(L.var_lds) + (L.filt.fields ? kFiltLds : 0u);  // + the filter's words (fas_post_kernel)
     // timed launches (e0, e1 given): the kernel's own start and end timestamps, taken from its
-    // dispatch (hipExtLaunchKernelGGL), instead of two marker packets around it
-    const dim3 grid(blocks, nq);
-#define PF_POST(XD, FILT, SEL) hipExtLaunchKernelGGL((fas_post_kernel<XD, FILT, SEL>), grid, dim3(kPostThreads), lds, s, e0, e1, 0u, ps, \
-                                                     pool, img_off, blk_begin, blk_end, k, parts, sync, out, out_rows, mode, qconst, filt, sel)
-    const uint32_t lds = post_lds(var_lds) + (filt.fields ? kFiltLds : 0u);  // + the filter's words (fas_post_kernel)
-    // the filter travels in the launch's own arguments: a later pf_set_scan_filter does not reach it
-    // and so does the field selection (pf_set_scan_select)
-    if (sel.on) {
-        if (filt.fields) { if (claimed) PF_POST(true, true, true); else PF_POST(false, true, true); }
-        else { if (claimed) PF_POST(true, false, true); else PF_POST(false, false, true); }
-    } else {
-        if (filt.fields) { if (claimed) PF_POST(true, true, false); else PF_POST(false, true, false); }
-        else { if (claimed) PF_POST(true, false, false); else PF_POST(false, false, false); }
-    }
-#undef PF_POST
+    // dispatch (hipExtLaunchKernelGGL), instead of two marker packets around it.  The filter and the field
+    // selection travel in the launch's own arguments: a later pf_set_scan_filter / _select does not reach them
+    hipExtLaunchKernelGGL(post_kernel(L.claimed, L.filt.fields != 0u, L.sel.on != 0u), dim3(L.blocks, L.nq), dim3(kPostThreads),
+                          lds, L.s, L.e0, L.e1, 0u, L.ps, L.pool, L.img_off, L.blk_begin, L.blk_end, L.k, L.parts, L.sync, L.out,
+                          L.out_rows, L.mode, L.qconst, L.filt, L.sel);
 #ifdef PF_K5_BLOCKLOG
     {
         static int calls = 0;
-        hipStreamSynchronize(s);
-        if (++calls % 10 == 0 && nq == 1) blog_report(blocks);
+        hipStreamSynchronize(L.s);
+        if (++calls % 10 == 0 && L.nq == 1) blog_report(L.blocks);
         const unsigned zero = 0;
         hipMemcpyToSymbol(HIP_SYMBOL(g_blog_n), &zero, sizeof zero);
     }
@@ -2361,7 +2303,7 @@ hipError_t launch_post(const PostStore& ps, const uint8_t* pool, const uint32_t*
     {
         static int calls = 0;
         unsigned long long t[16];
-        hipStreamSynchronize(s);
+        hipStreamSynchronize(L.s);
         hipMemcpyFromSymbol(t, HIP_SYMBOL(g_k5t), sizeof(t));
         static const char* nm[14] = {"ranges+hdr", "barriers", "excl+sets", "fixed", "walk", "walk-bar",
                                      "slots", "place", "place-bar", "terms", "owner-add", "rounds-end", "fas+topk",
@@ -2397,17 +2339,8 @@ int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered, bool selec
     if (it != memo.end()) return it->second;
     int nb = 0;
     const size_t lds = post_lds(var_lds) + (filtered ? kFiltLds : 0u);
-    hipError_t e;
-#define PF_OCC(XD, FILT, SEL) hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fas_post_kernel<XD, FILT, SEL>, kPostThreads, lds)
-    if (selected) {
-        if (filtered) e = claimed ? PF_OCC(true, true, true) : PF_OCC(false, true, true);
-        else e = claimed ? PF_OCC(true, false, true) : PF_OCC(false, false, true);
-    } else {
-        if (filtered) e = claimed ? PF_OCC(true, true, false) : PF_OCC(false, true, false);
-        else e = claimed ? PF_OCC(true, false, false) : PF_OCC(false, false, false);
-    }
-#undef PF_OCC
-    nb = (e == hipSuccess && nb > 0) ? nb : 1;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, post_kernel(claimed, filtered, selected), kPostThreads, lds);
+    nb =(e == hipSuccess && nb > 0) ? nb : 1;
     if (memo.size() > 4096) memo.clear();
     memo.emplace(var_lds, nb);
     return nb;
@@ -2421,20 +2354,15 @@ hipError_t launch_merge(const uint64_t* in, int nparts, int64_t part_stride, int
     return hipGetLastError();
 }
 
-hipError_t launch_pairs(const DevStore& st, const uint8_t* pool, const QImageRef* refs_dev, uint32_t max_lds,
-                        bool gtab, const PairBlock* blocks, int nblocks, const int32_t* order, const int32_t* slots,
-                        float* out, hipStream_t s, const FieldSel& sel) {
-    if (nblocks <= 0) return hipSuccess;
-#define PF_PAIRS(P, G) hipLaunchKernelGGL((fas_pairs_kernel<P, G>), dim3(nblocks), dim3(kPairThreads), max_lds, s, st, pool, \
-                                          refs_dev, blocks, order, slots, out, sel)
-    if (st.packed) { if (gtab) PF_PAIRS(true, true); else PF_PAIRS(true, false); }
-    else { if (gtab) PF_PAIRS(false, true); else PF_PAIRS(false, false); }
-#undef PF_PAIRS
+hipError_t launch_pairs(const PairsLaunch& L) {
+    if (L.nblocks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pairs_kernel(L.st.packed, L.gtab), dim3(L.nblocks), dim3(kPairThreads), L.max_lds, L.s, L.st, L.pool,
+                       L.refs_dev, L.blocks, L.order, L.slots, L.out, L.sel);
 #ifdef PF_K5_TIMERS
     {
         static int calls = 0;
         unsigned long long t[12];
-        hipStreamSynchronize(s);
+        hipStreamSynchronize(L.s);
         hipMemcpyFromSymbol(t, HIP_SYMBOL(g_k1t), sizeof(t));
         if (++calls % 10 == 0 && t[7] && t[11])
             fprintf(stderr, "k1pt epilogue: fallback waves %.3f, items per lane %.2f\n", (double)t[9] / t[11],
@@ -2444,7 +2372,7 @@ hipError_t launch_pairs(const DevStore& st, const uint8_t* pool, const QImageRef
                     "k1pt per wave (clock64): staging=%.0f walk=%.0f epilogue=%.0f (dense=%.0f assembly=%.0f "
                     "overflow=%.0f fas=%.0f) total=%.0f waves=%llu blocks=%d\n",
                     (double)t[0] / t[7], (double)t[1] / t[7], (double)t[2] / t[7], (double)t[4] / t[7],
-                    (double)t[5] / t[7], (double)t[6] / t[7], (double)t[8] / t[7], (double)t[3] / t[7], t[7], nblocks);
+                    (double)t[5] / t[7], (double)t[6] / t[7], (double)t[8] / t[7], (double)t[3] / t[7], t[7], L.nblocks);
         const unsigned long long z[12] = {0};
         hipMemcpyToSymbol(HIP_SYMBOL(g_k1t), z, sizeof(z));
     }

@@ -13,9 +13,9 @@ import edge_corpus as ec
 import pokec_testlib as tl
 
 # the kernels' limits, as their sources state them
-ROUND_TOKS = 64     # pf_types.h:219 kRoundToks; pf_kernels.hip:1055 "ROUNDS of <= 64 query tokens"
+ROUND_TOKS = 64     # pf_types.h:219 kRoundToks; pf_kernels.hip, K5: "ROUNDS of <= 64 query tokens"
 ROUND_CAP = 1536    # pf_types.h:220 kRoundCap = PF_K5_RCAP (6, :217) * kPostThreads (4 waves * 64, :209-210)
-ITEM_RUN_MAX = 31   # pf_kernels.hip:1206 kItemRunMax
+ITEM_RUN_MAX = 31   # pf_kernels.hip kItemRunMax
 HIT_CAP = 20        # pf_types.h:20-22 PF_HIT_CAP / kHitCap
 HIT_SLOTS = 24      # pf_types.h:28 kHitSlots = kHitCap + 4
 VAL_TAB = 128       # pf_types.h:16 kValTab

@@ -23,8 +23,7 @@ for what in os.environ.get("SKIP", "").split(","):
     elif what == "items":  # no item compaction and terms at all
         rep("for (uint32_t r0 = wb; r0 < wb + wn; r0 += 64) {", "for (uint32_t r0 = wb; r0 < wb; r0 += 64) {")
     elif what == "fas":  # no FAS divisions
-        rep("f = (S <= 0.0 && Fv <= 0.0) ? 0.0f : (float)((2.0 * S * Fv) / (S + Fv));", "f = (float)(S + Fv);")
-        rep("const double S = sum[kk] / (double)uk;", "const double S = sum[kk];")
+        rep("const float f = fas_score(sum[kk], uk, ftab[uk]);", "const float f = (float)(sum[kk] + ftab[uk]);")
     elif what == "owner":  # no owner sums
         rep("for (uint64_t pr = pend[kk] & rtm; pr; pr &= pr - 1) {", "for (uint64_t pr = 0; pr; pr &= pr - 1) {")
     elif what == "place":  # no hit placing

@@ -27,8 +27,9 @@ c = """                            atomicOr(reinterpret_cast<unsigned long long*
 assert s.count(c) == 1
 s = s.replace(c, c + "                K5T(17);\n", 1)
 # the host report: 20 slots
-s = s.replace("        unsigned long long t[16];\n        hipStreamSynchronize(s);\n        hipMemcpyFromSymbol(t, HIP_SYMBOL(g_k5t), sizeof(t));",
-              "        unsigned long long t[20];\n        hipStreamSynchronize(s);\n        hipMemcpyFromSymbol(t, HIP_SYMBOL(g_k5t), sizeof(t));", 1)
+d = "        unsigned long long t[16];\n        hipStreamSynchronize(L.s);\n        hipMemcpyFromSymbol(t, HIP_SYMBOL(g_k5t), sizeof(t));"
+assert s.count(d) == 1
+s = s.replace(d, d.replace("t[16]", "t[20]"), 1)
 i = s.index('static const char* nm[14] = {"ranges+hdr"')
 j = s.index("const unsigned long long z[16] = {0};", i)
 seg = s[i:j]
