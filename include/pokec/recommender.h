@@ -131,6 +131,18 @@ struct FieldSelect {
     }
 };
 
+// The breakdown of a pair's FAS (pokec_fas.h pf_fas_pairs_terms): the per-field sigmoid terms the
+// reference adds to sum_Si.  terms has 7 + (set_text_columns' list) doubles, slot k < 7 the fixed
+// field PF_F_*, slot 7 + t column t; a slot is present where its mask bit is set (`fixed` bit k,
+// `cols` bit t) and holds 0.0 otherwise.  score is profile_similarity's float.  For a profile that
+// is not of the map the score is NaN, the masks are 0 and terms is empty.
+struct ScoreTerms {
+    float score = NAN;
+    uint32_t fixed = 0;
+    uint64_t cols = 0;
+    std::vector<double> terms;
+};
+
 namespace detail {
 
 // One engine context and the adjacency rows it currently holds.
@@ -315,6 +327,16 @@ public:
         return pair_(engine_(), A.user_id, B.user_id, &s);
     }
 
+    // profile_similarity(A, B) with its per-field terms, for two profiles of the map; the overload
+    // over the selected fields only (a deselected slot is not present)
+    ScoreTerms profile_similarity_terms(const Profile& A, const Profile& B) const {
+        return pair_terms_(engine_(), A.user_id, B.user_id, nullptr);
+    }
+    ScoreTerms profile_similarity_terms(const Profile& A, const Profile& B, const FieldSelect& select) const {
+        const pf_field_select s = select.c_form();
+        return pair_terms_(engine_(), A.user_id, B.user_id, &s);
+    }
+
     // Push adj_list row `uid` to the engine now.  Never needed for correctness (every call
     // re-reads the rows it uses); kept for callers of the earlier facade.
     int sync_adjacency(int uid) const {
@@ -394,6 +416,25 @@ private:
         float out = NAN;
         const int rc = select ? pf_fas_pairs_select(e->ctx, &x, &y, 1, select, &out) : pf_fas_pairs(e->ctx, &x, &y, 1, &out);
         return rc == PF_OK ? out : NAN;
+    }
+
+    ScoreTerms pair_terms_(const std::shared_ptr<detail::Engine>& e, int a, int b, const pf_field_select* select) const {
+        ScoreTerms out;
+        if (!e) return out;
+        try {
+            std::lock_guard<std::mutex> g(e->mu);
+            const int32_t x = a, y = b;
+            pf_pair_terms_head h{};
+            std::vector<double> row((size_t)(PF_NUM_FIXED + pf_num_cols(e->ctx)));
+            if (pf_fas_pairs_terms(e->ctx, &x, &y, 1, select, &h, row.data()) != PF_OK || h.score != h.score) return out;
+            out.score = h.score;
+            out.fixed = h.fixed;
+            out.cols = h.cols;
+            out.terms = std::move(row);
+        } catch (...) {  // an allocation failure: the empty result
+            return ScoreTerms{};
+        }
+        return out;
     }
 
     Ranked fail_(pf_ctx* c, Ranked& out) const {

@@ -286,6 +286,43 @@ int pf_fas_pairs_select(pf_ctx* ctx, const int32_t* a_uid, const int32_t* b_uid,
                         const pf_field_select* select, float* out);
 
 /*
+ * Score breakdown: "similar because of what".  FAS is the harmonic mean of S, the average of the
+ * per-field sigmoid terms profile_similarity adds to sum_Si (recommender_similarity.cpp:38-114),
+ * and F, the share of the 7 + T fields both profiles filled in.  These calls return the terms.
+ * A pair's row has PF_NUM_FIXED + T doubles, T = pf_num_cols(ctx): slot k < 7 is the fixed field
+ * PF_F_*, slot 7 + t text column t of the engine's list.  A slot is present when the reference adds
+ * its term (the field is filled in on both sides); the head's masks say which: bit k of `fixed` =
+ * slot k, bit t of `cols` = slot 7 + t, the layout of pf_field_select.  A slot that is not present
+ * holds 0.0.  score is the pair's FAS, formed from the row as the reference forms it: used = the
+ * masks' popcount, S = (the present terms summed in ascending slot order) / used, F = used / (7 + T),
+ * (float)(2SF / (S + F)); used == 0 scores 0.
+ * Under a field selection a deselected slot is not present, T in F is the selected columns' count,
+ * the row keeps the engine's width (slots do not move), and the term of a slot that stays selected
+ * is the same double as with no selection.
+ */
+typedef struct pf_pair_terms_head {
+    float    score;
+    uint32_t fixed;
+    uint64_t cols;
+} pf_pair_terms_head; /* 16 B */
+/* T, the engine's text columns (0 for a NULL context) */
+int32_t pf_num_cols(const pf_ctx* ctx);
+/* pf_fas_pairs_select with the breakdown: head[n], terms[n * (PF_NUM_FIXED + T)].  A pair with an
+ * unknown uid gets score NaN, both masks 0 and a row of 0.0.  select NULL = none; the context's scan
+ * selection plays no part. */
+int pf_fas_pairs_terms(pf_ctx* ctx, const int32_t* a_uid, const int32_t* b_uid, int64_t n,
+                       const pf_field_select* select, pf_pair_terms_head* head, double* terms);
+/* pf_recommend_interest(ctx, query_uid, nq, topk, PF_MODE_ALL, 0, ...) with the breakdown of every
+ * result: the same scan (the context's filter, selection, kernel choice and shard; the job pipeline
+ * for topk > 64), whose ids and scores are returned as they are, then one more launch over the
+ * (query, result) pairs under the context's selection.  Result j of query i has head[i * topk + j]
+ * and the row terms[(i * topk + j) * (PF_NUM_FIXED + T)]; entries at or past out_count[i] are not
+ * written. */
+int pf_recommend_interest_all_terms(pf_ctx* ctx, const int32_t* query_uid, int32_t nq, int32_t topk,
+                                    int32_t* out_uid, float* out_score, int32_t* out_count,
+                                    pf_pair_terms_head* head, double* terms);
+
+/*
  * Device-resident all-candidates scan for the multi-GPU bench: scores the
  * queries against this context's shard and writes, per query, `topk` packed
  * 64-bit keys to DEVICE memory d_keys[nq*topk] on `stream` (a hipStream_t).

@@ -11,6 +11,10 @@ routes are kept, with the same paths, parameters and JSON:
     GET /api/recommend/{kind}/{uid}?topk=20, kind in graph|collab|interest|clubs:
                                         recommendations[kind][:topk]                 (app.py:122-144)
 
+and one route of the engine's own:
+
+    GET /api/explain/{a}/{b}            the api_cli JSON line for "EXPLAIN a b": the breakdown of FAS(a, b)
+
 What differs, because the reference's file cannot run as written:
   * it has unresolved merge-conflict markers (app.py:38-42, 147-159); the start-up wait here
     is the HEAD side's 120 s;
@@ -160,6 +164,7 @@ def create_app(root, cli_cmd=None, load_users=None, ready_timeout=120.0, request
         return ("<!doctype html><html><head><title>Pokec recommender</title></head><body>"
                 f"<h1>Pokec recommender</h1><p>Loaded users: {n}</p>"
                 "<p>GET /api/user/{uid}, /api/recommend/{graph|collab|interest|clubs}/{uid}?topk=20</p>"
+                "<p>GET /api/explain/{a}/{b}: the per-field terms of the similarity of users a and b</p>"
                 "</body></html>")
 
     @app.get("/health")
@@ -167,8 +172,11 @@ def create_app(root, cli_cmd=None, load_users=None, ready_timeout=120.0, request
         return {"status": "ok", "load_users": n}
 
     def user_json(uid):
+        return cli_json(f"USER {uid}")
+
+    def cli_json(cmd):
         try:
-            out = cli.send(f"USER {uid}", request_timeout)
+            out = cli.send(cmd, request_timeout)
         except Exception as e:
             raise HTTPException(status_code=500, detail=str(e))
         try:
@@ -181,6 +189,10 @@ def create_app(root, cli_cmd=None, load_users=None, ready_timeout=120.0, request
     @app.get("/api/user/{uid}")
     def api_user(uid: int):
         return JSONResponse(user_json(uid))
+
+    @app.get("/api/explain/{a}/{b}")
+    def api_explain(a: int, b: int):
+        return JSONResponse(cli_json(f"EXPLAIN {a} {b}"))
 
     def recommend(kind):
         def route(uid: int, topk: int = 20):

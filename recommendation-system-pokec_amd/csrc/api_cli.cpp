@@ -2,6 +2,9 @@
 // MI355X engine.  Same files (cwd-relative data/ + config/), same stdout protocol:
 // loader progress lines, READY, then one JSON line per input line.  The four
 // recommenders run through the C ABI (pokec_fas.h); start-up uses pokec_io.h.
+// One command is the engine's own: EXPLAIN <a> <b> prints the breakdown of FAS(a, b)
+// (pf_fas_pairs_terms): {"a":A,"b":B,"score":S,"used":U,"possible":7+T,"terms":{name:term,...}},
+// the present slots in slot order, doubles with max_digits10 digits (a JSON parse gives them back).
 //
 //   pokec_api_cli [load_users] [--root DIR] [--device N] [--no-cap] [--cache PATH]
 //
@@ -16,6 +19,7 @@
 #include <fstream>
 #include <iomanip>
 #include <iostream>
+#include <limits>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -137,11 +141,12 @@ int main(int argc, char** argv) {
             continue;
         }
         std::string cmd;
-        int uid = -1;
+        int uid = -1, xa = -1, xb = -1;
         {
             std::istringstream iss(line);
             iss >> cmd;
             if (cmd == "USER") iss >> uid;
+            if (cmd == "EXPLAIN" && !(iss >> xa >> xb)) xa = xb = -1;
         }
         if (cmd == "PING") {
             std::cout << "{\"ok\":true}" << std::endl;
@@ -181,6 +186,42 @@ int main(int argc, char** argv) {
             write_list(os, "interest", g, nullptr);  // recommend_by_interest == graph (recommender_graph.cpp:224-227)
             os << ",";
             write_list(os, "clubs", cl, ds);
+            os << "}}";
+            std::cout << os.str() << std::endl;
+            continue;
+        }
+        if (cmd == "EXPLAIN" && xa >= 0 && xb >= 0) {
+            static const char* const kFixedNames[PF_NUM_FIXED] = {"public", "gender", "completion", "age", "region", "clubs", "friends"};
+            const int32_t a = xa, b = xb;
+            const int W = PF_NUM_FIXED + pf_num_cols(ctx);
+            pf_pair_terms_head h{};
+            std::vector<double> row((size_t)W);
+            if (pf_fas_pairs_terms(ctx, &a, &b, 1, nullptr, &h, row.data()) != PF_OK) {
+                std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
+                std::cout << "{\"error\":\"engine failure\",\"user_id\":" << xa << "}" << std::endl;
+                continue;
+            }
+            if (h.score != h.score) {  // NaN: one of the two has no profile
+                int64_t len = 0;
+                const bool a_known = pf_dataset_profile_json(ds, xa, nullptr, 0, &len) != PF_ENOTFOUND;
+                std::cout << "{\"error\":\"not found\",\"user_id\":" << (a_known ? xb : xa) << "}" << std::endl;
+                continue;
+            }
+            std::ostringstream os;
+            int used = 0;
+            for (int s = 0; s < W; ++s)
+                used += s < PF_NUM_FIXED ? (int)((h.fixed >> s) & 1u) : (int)((h.cols >> (s - PF_NUM_FIXED)) & 1ull);
+            os << "{\"a\":" << xa << ",\"b\":" << xb << ",\"score\":" << std::setprecision(std::numeric_limits<float>::max_digits10)
+               << h.score << ",\"used\":" << used << ",\"possible\":" << W << ",\"terms\":{"
+               << std::setprecision(std::numeric_limits<double>::max_digits10);
+            bool first = true;
+            for (int s = 0; s < W; ++s) {
+                const bool on = s < PF_NUM_FIXED ? ((h.fixed >> s) & 1u) != 0 : ((h.cols >> (s - PF_NUM_FIXED)) & 1ull) != 0;
+                if (!on) continue;
+                const char* nm = s < PF_NUM_FIXED ? kFixedNames[s] : pf_dataset_column(ds, s - PF_NUM_FIXED);
+                os << (first ? "" : ",") << "\"" << json_escape(nm ? nm : "") << "\":" << row[(size_t)s];
+                first = false;
+            }
             os << "}}";
             std::cout << os.str() << std::endl;
             continue;

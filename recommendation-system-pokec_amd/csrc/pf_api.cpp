@@ -51,6 +51,7 @@ struct Images {
     std::vector<pf::QImageRef> refs;
     uint32_t max_lds = 0;  // dynamic LDS a 256-thread block needs for the largest image
     bool gtab = false;     // some image probes its table in global memory
+    uint32_t max_img = 0;  // the largest staged keys + vals (plan_images): K1t's LDS past the QConst
 };
 
 constexpr uint32_t kStageLimit = 48 * 1024;   // keys+vals above this are probed in global memory
@@ -107,6 +108,7 @@ size_t plan_images(Images& im, const std::vector<pf::QImageHost>& qs) {
                               4u * kPairThreads + 2048u;
         im.max_lds = std::max(im.max_lds, need);
         im.refs.push_back(r);
+        im.max_img = std::max(im.max_img, r.lds_bytes);
     }
     return o;
 }
@@ -133,26 +135,26 @@ pf::AdjView plain_view(const pf_ctx* c) {
     return v;
 }
 
-// FAS(A = qidx[g], B = slots[g][j]) for every group g, on the GPU.
-// Groups go to the GPU in chunks (<= 4096 distinct queries, <= 8M pairs per launch); each
-// distinct query's image is built once per chunk, on host threads.
-// keep (optional): every chunk's scores stay on the device in one buffer, group g at
-// (*goff)[g] (the collaborative sums read their matrix rows there)
-// sel (on == 0: none): a field selection every pair is scored under (pf_fas_pairs_select)
-int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
-              std::vector<std::vector<float>>& out, DBuf* keep = nullptr, std::vector<int64_t>* goff = nullptr,
-              const pf::FieldSel& sel = pf::FieldSel{}) {
-    out.assign(qidx.size(), {});
-    if (keep) {
-        size_t tot = 0;
-        goff->assign(qidx.size(), 0);
-        for (size_t g = 0; g < qidx.size(); ++g) {
-            (*goff)[g] = (int64_t)tot;
-            tot += slots[g].size();
-        }
-        HIPCHK(c, keep->ensure(std::max<size_t>(tot, 1) * sizeof(float)));
-    }
-    for (size_t g = 0; g < qidx.size(); ++g) out[g].assign(slots[g].size(), 0.f);
+// One chunk of pair groups as its kernel finds it: the images in c->d_pool / d_refs, the candidate
+// slots in c->d_slots (group g0 + i's from gf[i]; gf[g1 - g0] = npairs) and the pair blocks in
+// c->d_blocks, all queued on the context's stream.
+struct PairChunk {
+    size_t g0, g1;
+    const std::vector<size_t>& gf;
+    size_t npairs;
+    const Images& im;
+    int nblocks;
+    pf::HpLap& hl;
+};
+
+// Pairs (A = qidx[g], B = slots[g][j]) of every group g, to the GPU in chunks (<= 4096 distinct
+// queries, <= max_pairs pairs per launch); each distinct query's image is built once per chunk, on host
+// threads.  A group's pairs are cut into blocks of block_pairs (a PairBlock's count).  run(chunk)
+// launches the chunk's kernel, fetches its results and synchronises the stream before it returns
+// (the pinned buffers are reused by the next chunk).
+template <class Run>
+int pair_chunks(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
+                uint32_t block_pairs, size_t max_pairs, Run&& run) {
     size_t g0 = 0;
     while (g0 < qidx.size()) {
         // chunk [g0, g1)
@@ -162,7 +164,7 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
         for (; g1 < qidx.size(); ++g1) {
             if (slots[g1].empty()) continue;
             const bool fresh = !img_of.count(qidx[g1]);
-            if (g1 > g0 && ((fresh && uq.size() >= 4096) || pairs + slots[g1].size() > (8u << 20))) break;
+            if (g1 > g0 && ((fresh && uq.size() >= 4096) || pairs + slots[g1].size() > max_pairs)) break;
             if (fresh) {
                 img_of.emplace(qidx[g1], (int32_t)uq.size());
                 uq.push_back(qidx[g1]);
@@ -192,13 +194,12 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
         // per group: first block and first pair (serial, O(groups)); then the copies on threads
         std::vector<size_t> gb(g1 - g0 + 1), gf(g1 - g0 + 1);
         for (size_t g = g0; g < g1; ++g) {
-            gb[g - g0 + 1] = gb[g - g0] + (slots[g].size() + kPairThreads - 1) / kPairThreads;
+            gb[g - g0 + 1] = gb[g - g0] + (slots[g].size() + block_pairs - 1) / block_pairs;
             gf[g - g0 + 1] = gf[g - g0] + slots[g].size();
         }
         const size_t npairs = gf.back();
         HIPCHK(c, c->h_pool.ensure(pool_bytes));
         HIPCHK(c, c->h_slots.ensure(npairs * sizeof(int32_t)));
-        HIPCHK(c, c->h_scores.ensure(npairs * sizeof(float)));
         fill_images(im, qi, c->h_pool.as<uint8_t>(), pool_bytes);
         blocks.resize(gb.back());
         int32_t* flat = c->h_slots.as<int32_t>();
@@ -207,8 +208,8 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
             if (slots[g].empty()) return;
             const int32_t img = img_of.at(qidx[g]);
             std::memcpy(flat + gf[i], slots[g].data(), slots[g].size() * sizeof(int32_t));
-            for (size_t b = 0, x = gb[i]; b < slots[g].size(); b += kPairThreads, ++x)
-                blocks[x] = pf::PairBlock{img, (int32_t)(gf[i] + b), (int32_t)std::min<size_t>(kPairThreads, slots[g].size() - b),
+            for (size_t b = 0, x = gb[i]; b < slots[g].size(); b += block_pairs, ++x)
+                blocks[x] = pf::PairBlock{img, (int32_t)(gf[i] + b), (int32_t)std::min<size_t>(block_pairs, slots[g].size() - b),
                                            (int32_t)(gf[i] + b)};
         }, 256);
         hl.lap(pf::kHpPack);
@@ -219,30 +220,93 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
         HIPCHK(c, upload(c, c->d_blocks, blocks));
         HIPCHK(c, c->d_slots.ensure(npairs * sizeof(int32_t)));
         HIPCHK(c, hipMemcpyAsync(c->d_slots.p, flat, npairs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        float* dsc = nullptr;
-        if (keep) {
-            dsc = keep->as<float>() + (*goff)[g0];  // groups are laid out in order, chunk after chunk
-        } else {
-            HIPCHK(c, c->d_scores.ensure(npairs * sizeof(float)));
-            dsc = c->d_scores.as<float>();
-        }
-        HIPCHK(c, pf::launch_pairs({.st = c->ds, .pool = c->d_pool.as<uint8_t>(), .refs_dev = c->d_refs.as<pf::QImageRef>(),
-                                    .max_lds = im.max_lds, .gtab = im.gtab, .blocks = c->d_blocks.as<pf::PairBlock>(),
-                                    .nblocks = (int)blocks.size(), .order = nullptr, .slots = c->d_slots.as<int32_t>(),
-                                    .out = dsc, .s = c->stream, .sel = sel}));
-        c->jb.n_dispatch += !blocks.empty();  // pf_jobs_stats.pair_dispatches counts every K1' dispatch
-        const float* res = c->h_scores.as<float>();
-        HIPCHK(c, hipMemcpyAsync(c->h_scores.p, dsc, npairs * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hl.lap(pf::kHpGpu);
-        par_jobs(g1 - g0, [&](size_t i) {
-            const size_t g = g0 + i;
-            if (!slots[g].empty()) std::memcpy(out[g].data(), res + gf[i], slots[g].size() * sizeof(float));
-        }, 256);
-        hl.lap(pf::kHpUnpack);
+        const int rc = run(PairChunk{g0, g1, gf, npairs, im, (int)blocks.size(), hl});
+        if (rc != PF_OK) return rc;
         g0 = g1;
     }
     return PF_OK;
+}
+
+// FAS(A = qidx[g], B = slots[g][j]) for every group g, on the GPU (K1').
+// keep (optional): every chunk's scores stay on the device in one buffer, group g at
+// (*goff)[g] (the collaborative sums read their matrix rows there)
+// sel (on == 0: none): a field selection every pair is scored under (pf_fas_pairs_select)
+int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
+              std::vector<std::vector<float>>& out, DBuf* keep = nullptr, std::vector<int64_t>* goff = nullptr,
+              const pf::FieldSel& sel = pf::FieldSel{}) {
+    out.assign(qidx.size(), {});
+    if (keep) {
+        size_t tot = 0;
+        goff->assign(qidx.size(), 0);
+        for (size_t g = 0; g < qidx.size(); ++g) {
+            (*goff)[g] = (int64_t)tot;
+            tot += slots[g].size();
+        }
+        HIPCHK(c, keep->ensure(std::max<size_t>(tot, 1) * sizeof(float)));
+    }
+    for (size_t g = 0; g < qidx.size(); ++g) out[g].assign(slots[g].size(), 0.f);
+    return pair_chunks(c, qidx, slots, kPairThreads, (size_t)8u << 20, [&](const PairChunk& k) -> int {
+        HIPCHK(c, c->h_scores.ensure(k.npairs * sizeof(float)));
+        float* dsc = nullptr;
+        if (keep) {
+            dsc = keep->as<float>() + (*goff)[k.g0];  // groups are laid out in order, chunk after chunk
+        } else {
+            HIPCHK(c, c->d_scores.ensure(k.npairs * sizeof(float)));
+            dsc = c->d_scores.as<float>();
+        }
+        HIPCHK(c, pf::launch_pairs({.st = c->ds, .pool = c->d_pool.as<uint8_t>(), .refs_dev = c->d_refs.as<pf::QImageRef>(),
+                                    .max_lds = k.im.max_lds, .gtab = k.im.gtab, .blocks = c->d_blocks.as<pf::PairBlock>(),
+                                    .nblocks = k.nblocks, .order = nullptr, .slots = c->d_slots.as<int32_t>(),
+                                    .out = dsc, .s = c->stream, .sel = sel}));
+        c->jb.n_dispatch += k.nblocks != 0;  // pf_jobs_stats.pair_dispatches counts every K1' dispatch
+        const float* res = c->h_scores.as<float>();
+        HIPCHK(c, hipMemcpyAsync(c->h_scores.p, dsc, k.npairs * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        k.hl.lap(pf::kHpGpu);
+        par_jobs(k.g1 - k.g0, [&](size_t i) {
+            const size_t g = k.g0 + i;
+            if (!slots[g].empty()) std::memcpy(out[g].data(), res + k.gf[i], slots[g].size() * sizeof(float));
+        }, 256);
+        k.hl.lap(pf::kHpUnpack);
+        return PF_OK;
+    });
+}
+
+// The breakdown of the same pairs (K1t, pf_terms.hip): pair j of group g writes head[dest[g][j]] and
+// the row (W = 7 + T doubles) terms + dest[g][j] * W.  sel as in run_pairs.  A launch's rows are kept
+// to 256 MB (a row is up to 71 doubles where a score is one float).
+int run_pair_terms(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
+                   const std::vector<std::vector<int64_t>>& dest, pf_pair_terms_head* head, double* terms,
+                   const pf::FieldSel& sel) {
+    const size_t W = (size_t)(pf::kNumFixed + c->hc.T);
+    const size_t max_pairs = ((size_t)256u << 20) / (W * sizeof(double));
+    return pair_chunks(c, qidx, slots, (uint32_t)pf::kTermsPairs, max_pairs, [&](const PairChunk& k) -> int {
+        const size_t hb = k.npairs * sizeof(pf_pair_terms_head), tb = k.npairs * W * sizeof(double);
+        HIPCHK(c, c->d_thead.ensure(hb));
+        HIPCHK(c, c->d_terms.ensure(tb));
+        HIPCHK(c, c->h_thead.ensure(hb));
+        HIPCHK(c, c->h_terms.ensure(tb));
+        HIPCHK(c, pf::launch_terms({.st = c->ds, .pool = c->d_pool.as<uint8_t>(), .refs_dev = c->d_refs.as<pf::QImageRef>(),
+                                    .lds = (uint32_t)sizeof(pf::QConst) + k.im.max_img, .gtab = k.im.gtab,
+                                    .blocks = c->d_blocks.as<pf::PairBlock>(), .nblocks = k.nblocks,
+                                    .slots = c->d_slots.as<int32_t>(), .head = c->d_thead.as<pf_pair_terms_head>(),
+                                    .terms = c->d_terms.as<double>(), .s = c->stream, .sel = sel}));
+        HIPCHK(c, hipMemcpyAsync(c->h_thead.p, c->d_thead.p, hb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_terms.p, c->d_terms.p, tb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        k.hl.lap(pf::kHpGpu);
+        const pf_pair_terms_head* rh = c->h_thead.as<pf_pair_terms_head>();
+        const double* rt = c->h_terms.as<double>();
+        par_jobs(k.g1 - k.g0, [&](size_t i) {
+            const size_t g = k.g0 + i;
+            for (size_t j = 0; j < slots[g].size(); ++j) {
+                head[dest[g][j]] = rh[k.gf[i] + j];
+                std::memcpy(terms + (size_t)dest[g][j] * W, rt + (k.gf[i] + j) * W, W * sizeof(double));
+            }
+        }, 256);
+        k.hl.lap(pf::kHpUnpack);
+        return PF_OK;
+    });
 }
 
 // K5 mode word (pf_kernels.h): flags only; the block hand-out is launch_post's `claimed`, true for
@@ -1095,6 +1159,69 @@ static int fas_pairs(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, f
     for (int64_t i = 0; i < n; ++i)
         if (where[i].first >= 0) out[i] = res[where[i].first][where[i].second];
     return PF_OK;
+}
+
+static_assert(sizeof(pf_pair_terms_head) == 16, "pf_pair_terms_head is 16 B");
+
+int32_t pf_num_cols(const pf_ctx* c) { return c ? c->hc.T : 0; }
+
+// pairs grouped by their query, each remembering where its head and row go
+struct TermGroups {
+    std::unordered_map<int32_t, int32_t> group;  // query idx -> group
+    std::vector<int32_t> qidx;
+    std::vector<std::vector<int32_t>> slots;
+    std::vector<std::vector<int64_t>> dest;
+    void add(int32_t ia, int32_t slot, int64_t to) {
+        auto it = group.find(ia);
+        if (it == group.end()) {
+            it = group.emplace(ia, (int32_t)qidx.size()).first;
+            qidx.push_back(ia);
+            slots.emplace_back();
+            dest.emplace_back();
+        }
+        slots[it->second].push_back(slot);
+        dest[it->second].push_back(to);
+    }
+};
+
+int pf_fas_pairs_terms(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, const pf_field_select* s,
+                       pf_pair_terms_head* head, double* terms) {
+    if (!c || n < 0 || (n && (!a || !b || !head || !terms))) return PF_EINVAL;
+    pf::FieldSel d;
+    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "pairs terms: unknown bits in fixed / flags");
+    (void)hipSetDevice(c->device);
+    const size_t W = (size_t)(PF_NUM_FIXED + c->hc.T);
+    TermGroups tg;
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t ia = c->hc.idx_of(a[i]), ib = c->hc.idx_of(b[i]);
+        if (ia < 0 || ib < 0) {  // an unknown uid: NaN, nothing present, the row all 0.0
+            head[i] = pf_pair_terms_head{NAN, 0u, 0ull};
+            std::fill(terms + (size_t)i * W, terms + (size_t)(i + 1) * W, 0.0);
+            continue;
+        }
+        tg.add(ia, c->hs.slot_of_idx[ib], i);
+    }
+    return run_pair_terms(c, tg.qidx, tg.slots, tg.dest, head, terms, d);
+}
+
+int pf_recommend_interest_all_terms(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, int32_t* ou, float* os,
+                                    int32_t* oc, pf_pair_terms_head* head, double* terms) {
+    if (!c || nq < 0 || topk < 0 || (nq && (!q || !oc)) || (nq && topk && (!ou || !os || !head || !terms))) return PF_EINVAL;
+    // the scan itself, whatever path it takes; its ids and scores are the caller's results as they are
+    const int rc = pf_recommend_interest(c, q, nq, topk, PF_MODE_ALL, 0, ou, os, oc);
+    if (rc != PF_OK) return rc;
+    // the (query, winner) pairs, formed on the host from the list the scan returned
+    TermGroups tg;
+    for (int32_t i = 0; i < nq; ++i) {
+        if (oc[i] <= 0) continue;
+        const int32_t ia = c->hc.idx_of(q[i]);
+        for (int32_t j = 0; j < oc[i]; ++j) {
+            const int32_t ib = c->hc.idx_of(ou[(size_t)i * topk + j]);
+            if (ia < 0 || ib < 0) return c->fail(PF_EINTERNAL, "scan result without a profile");
+            tg.add(ia, c->hs.slot_of_idx[ib], (int64_t)i * topk + j);
+        }
+    }
+    return run_pair_terms(c, tg.qidx, tg.slots, tg.dest, head, terms, c->sel);
 }
 
 int pf_recommend_interest(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, int32_t mode, int32_t limit,

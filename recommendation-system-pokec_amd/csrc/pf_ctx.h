@@ -217,6 +217,8 @@ struct pf_ctx {
     // workspaces
     DBuf d_pool, d_refs, d_out, d_slots, d_blocks, d_scores, d_part;
     PinBuf h_pool, h_slots, h_scores;  // pf_fas_pairs batches: images, candidate slots, scores
+    DBuf d_thead, d_terms;             // pf_fas_pairs_terms batches: heads and term rows (K1t)
+    PinBuf h_thead, h_terms;
     int32_t tile_begin = 0, tile_end = 0;
     // postings store (K5); wave blocks [wb_begin, wb_end) are this context's shard
     pf::HostPost hp;

@@ -1,6 +1,6 @@
 // pf_device.h — device helpers shared by the gfx950 kernel files (pf_kernels.hip,
-// pf_jobs.hip): the reference's FAS arithmetic, query-table probes, tile-store record
-// access and the wave top-k.
+// pf_jobs.hip, pf_terms.hip): the reference's FAS arithmetic, query-table probes, tile-store
+// record access, the wave top-k, and the copies that stage a query image into LDS.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,24 +59,34 @@ static __device__ __attribute__((noinline)) double ratio_term(const QConst& q, i
 // The reference's seven fixed terms (recommender_similarity.cpp:38-91) and its final score, once: every
 // kernel unpacks its own header format and runs this text.  The five header terms of a candidate with public /
 // gender codes pb, gb, completion cb, age ab and regions r0..r2, in the reference's order; used counts them.
-__device__ __forceinline__ void header_terms(const QConst& q, uint32_t pb, uint32_t gb, int cb, int ab, int r0, int r1,
-                                             int r2, double& sum, int& used) {
-    if (q.pubcode != kCodeMissing && pb != kCodeMissing) { sum += q.sig_pub[pb == q.pubcode]; ++used; }
-    if (q.gencode != kCodeMissing && gb != kCodeMissing) { sum += q.sig_gen[gb == q.gencode]; ++used; }
-    if (q.comp > 0 && cb > 0) { sum += cb <= kValTab ? q.sig_comp[cb] : ratio_term(q, PF_F_COMPLETION, q.comp, cb); ++used; }
-    if (q.age > 0 && ab > 0) { sum += ab <= kValTab ? q.sig_age[ab] : ratio_term(q, PF_F_AGE, q.age, ab); ++used; }
+// Each present term goes to put(slot, term), slot = PF_F_*: the scoring kernels add it to their sum, the
+// terms kernel (pf_terms.hip) also keeps it.
+template <class Put>
+__device__ __forceinline__ void header_terms_each(const QConst& q, uint32_t pb, uint32_t gb, int cb, int ab, int r0, int r1,
+                                                  int r2, Put&& put) {
+    if (q.pubcode != kCodeMissing && pb != kCodeMissing) put(PF_F_PUBLIC, q.sig_pub[pb == q.pubcode]);
+    if (q.gencode != kCodeMissing && gb != kCodeMissing) put(PF_F_GENDER, q.sig_gen[gb == q.gencode]);
+    if (q.comp > 0 && cb > 0) put(PF_F_COMPLETION, cb <= kValTab ? q.sig_comp[cb] : ratio_term(q, PF_F_COMPLETION, q.comp, cb));
+    if (q.age > 0 && ab > 0) put(PF_F_AGE, ab <= kValTab ? q.sig_age[ab] : ratio_term(q, PF_F_AGE, q.age, ab));
     const int bcnt = (r0 >= 0) + (r1 >= 0) + (r2 >= 0);
     if (q.a_regcnt > 0 && bcnt > 0) {
         const int m = (r0 >= 0 && r0 == q.reg[0]) + (r1 >= 0 && r1 == q.reg[1]) + (r2 >= 0 && r2 == q.reg[2]);
-        sum += q.sig_reg[bcnt][m];
-        ++used;
+        put(PF_F_REGION, q.sig_reg[bcnt][m]);
     }
+}
+__device__ __forceinline__ void header_terms(const QConst& q, uint32_t pb, uint32_t gb, int cb, int ab, int r0, int r1,
+                                             int r2, double& sum, int& used) {
+    header_terms_each(q, pb, gb, cb, ab, r0, r1, r2, [&](int, double term) { sum += term; ++used; });
 }
 // The two set terms after them: the candidate's nc clubs and nf friends, ic / ifr of them the query's
 // (the pair epilogue computes these two through its item queue and keeps only the bookkeeping).
+template <class Put>
+__device__ __forceinline__ void set_terms_each(const QConst& q, int ic, uint32_t nc, int ifr, uint32_t nf, Put&& put) {
+    if (q.n_clubs > 0 && nc > 0) put(PF_F_CLUBS, ic == 0 ? q.sig0_clubs : set_term(q, PF_F_CLUBS, ic, (int)nc, q.sqrt_clubs));
+    if (q.n_friends > 0 && nf > 0) put(PF_F_FRIENDS, ifr == 0 ? q.sig0_friends : set_term(q, PF_F_FRIENDS, ifr, (int)nf, q.sqrt_friends));
+}
 __device__ __forceinline__ void set_terms(const QConst& q, int ic, uint32_t nc, int ifr, uint32_t nf, double& sum, int& used) {
-    if (q.n_clubs > 0 && nc > 0) { sum += ic == 0 ? q.sig0_clubs : set_term(q, PF_F_CLUBS, ic, (int)nc, q.sqrt_clubs); ++used; }
-    if (q.n_friends > 0 && nf > 0) { sum += ifr == 0 ? q.sig0_friends : set_term(q, PF_F_FRIENDS, ifr, (int)nf, q.sqrt_friends); ++used; }
+    set_terms_each(q, ic, nc, ifr, nf, [&](int, double term) { sum += term; ++used; });
 }
 // recommender_similarity.cpp:114-123; F = used / (kNumFixed + the query's columns), divided or looked up by the caller
 __device__ __forceinline__ float fas_score(double sum, int used, double F) {
@@ -318,6 +328,32 @@ __device__ __forceinline__ void topk_push(uint64_t& list, uint64_t x, int k, int
     const uint64_t thr = rdlane64(list, k - 1);
     const uint64_t m = __ballot(x < thr);
     if (m) list = topk_insert(list, x, thr, m, k, lane);
+}
+
+// ---------------------------------------------------------------- LDS staging
+__device__ __forceinline__ void stage(void* dst, const void* src, uint32_t bytes) {
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    const uint4* s = reinterpret_cast<const uint4*>(src);
+    for (uint32_t i = threadIdx.x; i < bytes / 16; i += blockDim.x) d[i] = s[i];
+}
+
+// The same with every thread's loads of a round (4 per thread) issued before its stores, so a
+// round costs one memory round trip (the pair kernel stages a 5-20 KB image per block)
+__device__ __forceinline__ void stage4(void* dst, const void* src, uint32_t bytes) {
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    const uint4* s = reinterpret_cast<const uint4*>(src);
+    const uint32_t n = bytes / 16;
+    if (n == 0) return;
+    const uint32_t bd = blockDim.x;
+    for (uint32_t base = threadIdx.x; base < n; base += 4 * bd) {
+        // clamped loads (always in range), guarded stores: four in flight per thread
+        const uint32_t i1 = base + bd, i2 = base + 2 * bd, i3 = base + 3 * bd;
+        const uint4 r0 = s[base], r1 = s[min(i1, n - 1)], r2 = s[min(i2, n - 1)], r3 = s[min(i3, n - 1)];
+        d[base] = r0;
+        if (i1 < n) d[i1] = r1;
+        if (i2 < n) d[i2] = r2;
+        if (i3 < n) d[i3] = r3;
+    }
 }
 
 }  // namespace pf

@@ -122,5 +122,29 @@ struct PairsLaunch {
     const FieldSel& sel;
 };
 hipError_t launch_pairs(const PairsLaunch& L);
+// K1t (pf_terms.hip), the score breakdown: one workgroup of kTermsThreads per PairBlock of count <=
+// kTermsPairs pairs, one wave per pair, the block's waves taking its pairs in turn against the one
+// staged image.  Pair i of a block writes head[out + i] and the row terms[(out + i) * (PF_NUM_FIXED +
+// st.n_cols)]; a slot < 0 writes score NaN, both masks 0 and the row 0.0, so every output is defined.
+constexpr int kTermsThreads = 256;
+constexpr int kTermsPairs = 32;
+struct TermsLaunch {
+    const DevStore& st;  // st.packed and gtab are the instantiation
+    const uint8_t* pool;
+    const QImageRef* refs_dev;
+    // dynamic LDS bytes per block = sizeof(QConst) + the largest staged keys/vals of the launch's images
+    // (the kernel keeps no hit list)
+    uint32_t lds;
+    bool gtab;
+    const PairBlock* blocks;
+    int nblocks;
+    const int32_t* slots;
+    pf_pair_terms_head* head;
+    double* terms;
+    hipStream_t s;
+    // on == 0: none; applied to every block's staged constants, as in PairsLaunch
+    const FieldSel& sel;
+};
+hipError_t launch_terms(const TermsLaunch& L);
 
 }  // namespace pf

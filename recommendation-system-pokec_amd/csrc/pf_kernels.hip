@@ -728,31 +728,7 @@ __device__ __forceinline__ float fas_slot(const DevStore& st, const QView& v, co
 }
 
 // ---------------------------------------------------------------- LDS staging
-__device__ __forceinline__ void stage(void* dst, const void* src, uint32_t bytes) {
-    uint4* d = reinterpret_cast<uint4*>(dst);
-    const uint4* s = reinterpret_cast<const uint4*>(src);
-    for (uint32_t i = threadIdx.x; i < bytes / 16; i += blockDim.x) d[i] = s[i];
-}
-
-// The same with every thread's loads of a round (4 per thread) issued before its stores, so a
-// round costs one memory round trip (the pair kernel stages a 5-20 KB image per block)
-__device__ __forceinline__ void stage4(void* dst, const void* src, uint32_t bytes) {
-    uint4* d = reinterpret_cast<uint4*>(dst);
-    const uint4* s = reinterpret_cast<const uint4*>(src);
-    const uint32_t n = bytes / 16;
-    if (n == 0) return;
-    const uint32_t bd = blockDim.x;
-    for (uint32_t base = threadIdx.x; base < n; base += 4 * bd) {
-        // clamped loads (always in range), guarded stores: four in flight per thread
-        const uint32_t i1 = base + bd, i2 = base + 2 * bd, i3 = base + 3 * bd;
-        const uint4 r0 = s[base], r1 = s[min(i1, n - 1)], r2 = s[min(i2, n - 1)], r3 = s[min(i3, n - 1)];
-        d[base] = r0;
-        if (i1 < n) d[i1] = r1;
-        if (i2 < n) d[i2] = r2;
-        if (i3 < n) d[i3] = r3;
-    }
-}
-
+// (the copies: stage, stage4 in pf_device.h)
 // LDS carve: [QConst][tables][vals][hit lists kHitCap x blockDim][merge scratch 2 KiB].
 // GTAB = false: the cuckoo table and the token values are staged in LDS, so every probe
 // is a ds_read (pointer provenance is the LDS symbol only, never merged with a global

@@ -36,7 +36,8 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_last_scan_ms", "pf_profile_reset", "pf_profile_read", "pf_profile_sample", "pf_set_scan_kernel",
            "pf_scan_bytes", "pf_scan_prune_stats", "pf_jobs_stats_reset", "pf_jobs_stats_read", "pf_recommend_interest_async",
            "pf_recommend_collab_async", "pf_recommend_clubs_async", "pf_wait", "pf_completed_ticket",
-           "pf_set_scan_filter", "pf_scan_filter_count", "pf_set_scan_select", "pf_fas_pairs_select"]
+           "pf_set_scan_filter", "pf_scan_filter_count", "pf_set_scan_select", "pf_fas_pairs_select",
+           "pf_num_cols", "pf_fas_pairs_terms", "pf_recommend_interest_all_terms"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
               "pf_dataset_profile_order", "pf_dataset_adj_order", "pf_dataset_profile_json", "pf_dataset_club_name",
@@ -134,6 +135,47 @@ class FieldSelect(ctypes.Structure):
         return g
 
 
+class PairTermsHead(ctypes.Structure):
+    """pf_pair_terms_head: a pair's score and the masks of its present slots."""
+    _fields_ = [("score", ctypes.c_float), ("fixed", ctypes.c_uint32), ("cols", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(PairTermsHead) == 16
+_HEAD_DTYPE = np.dtype([("score", np.float32), ("fixed", np.uint32), ("cols", np.uint64)])
+assert _HEAD_DTYPE.itemsize == ctypes.sizeof(PairTermsHead)
+
+
+class PairTerms:
+    """The breakdown of n pairs' FAS (pf_fas_pairs_terms): score f32[n], fixed u32[n] and cols u64[n]
+    (the masks of the slots the reference added: bit k of fixed = PF_F_*, bit t of cols = column t)
+    and terms f64[n, 7 + T], the per-slot sigmoid terms, 0.0 where the slot is not present."""
+
+    def __init__(self, head, terms):
+        self.score = np.ascontiguousarray(head["score"])
+        self.fixed = np.ascontiguousarray(head["fixed"])
+        self.cols = np.ascontiguousarray(head["cols"])
+        self.terms = terms
+
+    def __len__(self):
+        return len(self.score)
+
+    @property
+    def present(self):
+        """bool[n, 7 + T]: which slots were added to the reference's sum."""
+        T = self.terms.shape[1] - 7
+        fx = (self.fixed[:, None] >> np.arange(7, dtype=np.uint32)[None, :]) & np.uint32(1)
+        cl = (self.cols[:, None] >> np.arange(T, dtype=np.uint64)[None, :]) & np.uint64(1)
+        return np.concatenate([fx.astype(bool), cl.astype(bool)], axis=1)
+
+    @property
+    def used(self):
+        return self.present.sum(axis=1)
+
+    @staticmethod
+    def slot_names(ds_columns):
+        return list(FIXED_FIELD_NAMES) + list(ds_columns)
+
+
 class PfJobsStats(ctypes.Structure):
     _fields_ = [("jobs", ctypes.c_int64), ("candidates", ctypes.c_int64), ("pairs", ctypes.c_int64),
                 ("pair_alg_bytes", ctypes.c_int64), ("pair_record_bytes", ctypes.c_int64),
@@ -197,6 +239,10 @@ def lib():
         L.pf_scan_filter_count.argtypes = [V, ctypes.POINTER(I64)]
         L.pf_set_scan_select.argtypes = [V, ctypes.POINTER(FieldSelect)]
         L.pf_fas_pairs_select.argtypes = [V, V, V, I64, ctypes.POINTER(FieldSelect), V]
+        L.pf_num_cols.argtypes = [V]
+        L.pf_num_cols.restype = I32
+        L.pf_fas_pairs_terms.argtypes = [V, V, V, I64, ctypes.POINTER(FieldSelect), V, V]
+        L.pf_recommend_interest_all_terms.argtypes = [V, V, I32, I32, V, V, V, V, V]
         L.pf_scan_keys_async.argtypes = [V, V, I32, I32, V, V]
         L.pf_merge_keys_async.argtypes = [V, V, I32, I32, I32, V, V]
         L.pf_decode_keys.argtypes = [V, I32, V, V, V]
@@ -303,6 +349,38 @@ class FasEngine:
                     "pf_fas_pairs")
         return out
 
+    @property
+    def num_cols(self):
+        return self._L.pf_num_cols(self.h)
+
+    def fas_pairs_terms(self, a_uid, b_uid, select=None):
+        """The pairs' FAS with its per-field terms (a PairTerms), under select (a FieldSelect) or
+        none; the scan selection in force plays no part.  A pair with an unknown uid scores NaN
+        with nothing present."""
+        a, b = _i32(a_uid), _i32(b_uid)
+        n, W = len(a), 7 + self.num_cols
+        head = np.zeros(n, _HEAD_DTYPE)
+        terms = np.zeros((n, W), np.float64)
+        self._check(self._L.pf_fas_pairs_terms(self.h, a.ctypes.data, b.ctypes.data, n,
+                                               None if select is None else ctypes.byref(select),
+                                               head.ctypes.data, terms.ctypes.data), "pf_fas_pairs_terms")
+        return PairTerms(head, terms)
+
+    def _topk_terms(self, users, topk):
+        q = _i32(users)
+        k, W = max(int(topk), 0), 7 + self.num_cols
+        ou = np.zeros(max(len(q) * k, 1), np.int32)
+        os_ = np.zeros(max(len(q) * k, 1), np.float32)
+        oc = np.zeros(max(len(q), 1), np.int32)
+        head = np.zeros(max(len(q) * k, 1), _HEAD_DTYPE)
+        terms = np.zeros((max(len(q) * k, 1), W), np.float64)
+        self._check(self._L.pf_recommend_interest_all_terms(self.h, q.ctypes.data, len(q), k, ou.ctypes.data,
+                                                            os_.ctypes.data, oc.ctypes.data, head.ctypes.data,
+                                                            terms.ctypes.data), "pf_recommend_interest_all_terms")
+        self._prune_inflight()
+        return [(ou[i * k:i * k + oc[i]].copy(), os_[i * k:i * k + oc[i]].copy(),
+                 PairTerms(head[i * k:i * k + oc[i]], terms[i * k:i * k + oc[i]].copy())) for i in range(len(q))]
+
     def _topk(self, fn, users, topk, *extra):
         q = _i32(users)
         k = max(int(topk), 0)
@@ -375,10 +453,24 @@ class FasEngine:
     recommend_friends_by_interest = recommend_graph_registration
     recommend_friends_collab = recommend_collaborative
 
-    def recommend_interest_all(self, users, topk, filter=None, select=None):
+    def recommend_interest_all(self, users, topk, filter=None, select=None, explain=False):
         """All-candidates interest scan.  filter (a CandFilter): rank only the candidates
         that pass it; select (a FieldSelect): score over the selected fields only.  The filter and the
-        selection in force before the call are restored afterwards."""
+        selection in force before the call are restored afterwards.  explain: each result is
+        (ids, scores, PairTerms), the breakdown of every listed score (one more launch and copy)."""
+        if explain:
+            prev, prev_sel = self._filter, self._select
+            try:
+                if filter is not None:
+                    self.set_scan_filter(filter)
+                if select is not None:
+                    self.set_scan_select(select)
+                return self._topk_terms(users, topk)
+            finally:
+                if filter is not None:
+                    self.set_scan_filter(prev)
+                if select is not None:
+                    self.set_scan_select(prev_sel)
         if filter is None and select is None:
             return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
         prev, prev_sel = self._filter, self._select
