@@ -42,6 +42,11 @@
 //     is how every reference caller uses it.  It returns NaN otherwise.  A text_columns list other
 //     than set_text_columns' uses the engine for that list; a proper prefix of set_text_columns'
 //     list is scored on the one engine through a field selection (no second engine is opened).
+//     A profile that is NOT of the map (a visitor, an edited copy) is scored by value through
+//     profile_similarity_adhoc(A, B) / profile_similarity_terms_adhoc(A, B), with B of the map, and
+//     ranked against every profile of the map by recommend_by_profile(A, topk, exclude): the
+//     reference's profile_similarity(A, B) for a corpus that also held A, under this engine's idf
+//     and normalisers (pokec_fas.h "Query by profile").
 //   - The legacy user_feats constructor and recommend_from_supernodes
 //     (recommender_clubs.cpp:75-...) are not provided: no live caller uses them
 //     (SURVEY.md §8 A12).
@@ -337,6 +342,40 @@ public:
         return pair_terms_(engine_(), A.user_id, B.user_id, &s);
     }
 
+    // Query by profile (pokec_fas.h pf_query_profile): A is taken by value and need not be of the
+    // map; its user_id plays no part.  The all-candidates top-k over every profile of the map but
+    // those in `exclude` (nothing is excluded implicitly: pass A's own id and friends to leave them out).
+    Ranked recommend_by_profile(const Profile& A, int topk, const std::vector<int>& exclude = {}) const {
+        Ranked out;
+        if (!profiles || topk <= 0) return out;
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return out;
+        std::lock_guard<std::mutex> g(e->mu);
+        QueryHold h;
+        const pf_query_profile q = query_of_(e->ctx, A, exclude, h);
+        topk = (int)std::min<int64_t>(topk, e->n_users + 1);
+        std::vector<int32_t> ids((size_t)topk);
+        std::vector<float> sc((size_t)topk);
+        int32_t n = 0;
+        if (pf_recommend_interest_profile(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n) != PF_OK) return fail_(e->ctx, out);
+        for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
+        return out;
+    }
+    // profile_similarity(A, B) with A by value and B of the map (NaN when B is not); the overload over
+    // the selected fields only
+    float profile_similarity_adhoc(const Profile& A, const Profile& B) const { return adhoc_(A, B.user_id, nullptr); }
+    float profile_similarity_adhoc(const Profile& A, const Profile& B, const FieldSelect& select) const {
+        const pf_field_select s = select.c_form();
+        return adhoc_(A, B.user_id, &s);
+    }
+    ScoreTerms profile_similarity_terms_adhoc(const Profile& A, const Profile& B) const {
+        return adhoc_terms_(A, B.user_id, nullptr);
+    }
+    ScoreTerms profile_similarity_terms_adhoc(const Profile& A, const Profile& B, const FieldSelect& select) const {
+        const pf_field_select s = select.c_form();
+        return adhoc_terms_(A, B.user_id, &s);
+    }
+
     // Push adj_list row `uid` to the engine now.  Never needed for correctness (every call
     // re-reads the rows it uses); kept for callers of the earlier facade.
     int sync_adjacency(int uid) const {
@@ -432,6 +471,78 @@ private:
             out.cols = h.cols;
             out.terms = std::move(row);
         } catch (...) {  // an allocation failure: the empty result
+            return ScoreTerms{};
+        }
+        return out;
+    }
+
+    // the arrays behind a pf_query_profile built from a Profile
+    struct QueryHold {
+        std::vector<int64_t> off;
+        std::vector<int32_t> tid, tf, excl;
+    };
+    pf_query_profile query_of_(pf_ctx* c, const Profile& A, const std::vector<int>& exclude, QueryHold& h) const {
+        const int T = pf_num_cols(c);
+        h.off.assign(1, 0);
+        for (int t = 0; t < T; ++t) {
+            if ((size_t)t < A.token_cols.size())
+                for (const auto& kv : A.token_cols[(size_t)t]) {
+                    h.tid.push_back(kv.first);
+                    h.tf.push_back(kv.second);
+                }
+            h.off.push_back((int64_t)h.tid.size());
+        }
+        h.excl.assign(exclude.begin(), exclude.end());
+        pf_query_profile q{};
+        q.public_flag = A.public_flag;
+        q.gender = A.gender;
+        q.completion = A.completion_percentage;
+        q.age = A.age;
+        for (int k = 0; k < 3; ++k) q.region[k] = A.region_parts[(size_t)k];
+        q.club_ids = A.clubs.data();
+        q.n_clubs = (int32_t)A.clubs.size();
+        q.friend_ids = A.friends.data();
+        q.n_friends = (int32_t)A.friends.size();
+        q.tok_off = h.off.data();
+        q.tok_tid = h.tid.data();
+        q.tok_tf = h.tf.data();
+        q.exclude_uid = h.excl.data();
+        q.n_exclude = (int32_t)h.excl.size();
+        return q;
+    }
+
+    float adhoc_(const Profile& A, int b, const pf_field_select* select) const {
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return NAN;
+        try {
+            std::lock_guard<std::mutex> g(e->mu);
+            QueryHold h;
+            const pf_query_profile q = query_of_(e->ctx, A, {}, h);
+            const int32_t y = b;
+            float out = NAN;
+            return pf_fas_profile_pairs(e->ctx, &q, &y, 1, select, &out) == PF_OK ? out : NAN;
+        } catch (...) {
+            return NAN;
+        }
+    }
+
+    ScoreTerms adhoc_terms_(const Profile& A, int b, const pf_field_select* select) const {
+        ScoreTerms out;
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return out;
+        try {
+            std::lock_guard<std::mutex> g(e->mu);
+            QueryHold hold;
+            const pf_query_profile q = query_of_(e->ctx, A, {}, hold);
+            const int32_t y = b;
+            pf_pair_terms_head h{};
+            std::vector<double> row((size_t)(PF_NUM_FIXED + pf_num_cols(e->ctx)));
+            if (pf_fas_profile_pairs_terms(e->ctx, &q, &y, 1, select, &h, row.data()) != PF_OK || h.score != h.score) return out;
+            out.score = h.score;
+            out.fixed = h.fixed;
+            out.cols = h.cols;
+            out.terms = std::move(row);
+        } catch (...) {
             return ScoreTerms{};
         }
         return out;

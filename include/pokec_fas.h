@@ -323,6 +323,68 @@ int pf_recommend_interest_all_terms(pf_ctx* ctx, const int32_t* query_uid, int32
                                     pf_pair_terms_head* head, double* terms);
 
 /*
+ * Query by profile: "for whom", when that person is not a user of the corpus given to pf_open (a
+ * sign-up form, a profile being edited, an anonymous search, a record of another dataset).  The
+ * profile is given by value; nothing of it is stored.
+ *   Definition   The score of candidate B is profile_similarity(A, B) of the reference with A the given
+ *                profile: bit for bit what the reference returns for a corpus that also holds A, under
+ *                the same idf map and normalisers.
+ *   idf          The engine's, fixed at open: the visitor counts in neither N nor df.  A token id the
+ *                column's idf map does not hold gets 1.0 (pf_idf's rule, recommender.cpp:78), ids above
+ *                every id the engine has seen included; a column with no idf map uses raw counts.  A
+ *                query token no candidate holds meets nobody, but adds to the column's norm and keeps
+ *                the column non-empty: a candidate with that column filled gets the s = 0 term there.
+ *   Norm         Per column sqrt(sum ((double)tf * idf)^2) over the row in ascending token-id order, the
+ *                order and the arithmetic of the stored users' rows.
+ *   Codes        A public_flag / gender value no corpus user has is present and equal to nobody (not
+ *                missing: the term is added, at s = 0).  An age / completion no user has gets its
+ *                sigmoid row computed on the host like any stored value; values past 128 behave as
+ *                they do for stored users.
+ *   Exclusions   Exactly exclude_uid: no implicit self, no adjacency.  Unknown uids are ignored.
+ *   State        The context's filter, field selection, shard and scan-kernel choice apply exactly as
+ *                to pf_recommend_interest(PF_MODE_ALL); the `select` argument of the pair calls behaves
+ *                as in pf_fas_pairs_select / pf_fas_pairs_terms.
+ *   Batches      The nq profiles are one call: nq == 1 runs the one-query scan (its image uploaded with
+ *                the launch), nq > 1 the batch scan over the staged images.
+ *   Limits       topk > 64 returns PF_EUNSUPP (the job pipeline serves stored users only).  A row
+ *                pf_open would not accept for a user is refused, never scored wrongly: PF_EUNSUPP for a
+ *                club / friend id repeated more than 255 times, more than 65535 clubs or friends, a tf
+ *                outside the record encoding (0..255 in the packed layout); PF_EINVAL for a negative
+ *                token id, an id repeated within a column, a non-monotone tok_off, non-zero flags, a
+ *                NULL profile array with nq > 0.  pf_last_error names the reason.
+ *   No change    Nothing in the context changes: no resident image, store or idf is touched, and the
+ *                by-uid calls before and after are identical.
+ */
+typedef struct pf_query_profile {
+    int32_t public_flag, gender;      /* -1 = missing                                  */
+    int32_t completion, age;          /* used when > 0; age in the corpus's domain     */
+    int32_t region[3];                /* -1 = missing part                             */
+    uint32_t flags;                   /* must be 0                                     */
+    const uint32_t* club_ids;   int32_t n_clubs;    /* profile order, duplicates kept  */
+    const uint32_t* friend_ids; int32_t n_friends;  /* the profile's `friends` column  */
+    const int64_t* tok_off;           /* [T + 1], T = pf_num_cols(ctx); NULL = no text */
+    const int32_t* tok_tid;           /* distinct within a column, >= 0                */
+    const int32_t* tok_tf;
+    const int32_t* exclude_uid; int32_t n_exclude;  /* never returned; unknown uids ignored */
+} pf_query_profile;
+
+/* The all-candidates top-k of each of the nq profiles; outputs as pf_recommend_interest.  nq = 0
+ * returns PF_OK and writes nothing. */
+int pf_recommend_interest_profile(pf_ctx* ctx, const pf_query_profile* q, int32_t nq, int32_t topk,
+                                  int32_t* out_uid, float* out_score, int32_t* out_count);
+/* FAS(A = the profile, B = b_uid[i]) for n stored users; an unknown b_uid scores NaN. */
+int pf_fas_profile_pairs(pf_ctx* ctx, const pf_query_profile* a, const int32_t* b_uid, int64_t n,
+                         const pf_field_select* select, float* out);
+/* ... with the breakdown, laid out as pf_fas_pairs_terms */
+int pf_fas_profile_pairs_terms(pf_ctx* ctx, const pf_query_profile* a, const int32_t* b_uid, int64_t n,
+                               const pf_field_select* select, pf_pair_terms_head* head, double* terms);
+/* pf_recommend_interest_profile with the breakdown of every result, laid out as
+ * pf_recommend_interest_all_terms (the context's selection) */
+int pf_recommend_interest_profile_terms(pf_ctx* ctx, const pf_query_profile* q, int32_t nq, int32_t topk,
+                                        int32_t* out_uid, float* out_score, int32_t* out_count,
+                                        pf_pair_terms_head* head, double* terms);
+
+/*
  * Device-resident all-candidates scan for the multi-GPU bench: scores the
  * queries against this context's shard and writes, per query, `topk` packed
  * 64-bit keys to DEVICE memory d_keys[nq*topk] on `stream` (a hipStream_t).

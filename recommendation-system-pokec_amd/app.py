@@ -14,6 +14,13 @@ routes are kept, with the same paths, parameters and JSON:
 and one route of the engine's own:
 
     GET /api/explain/{a}/{b}            the api_cli JSON line for "EXPLAIN a b": the breakdown of FAS(a, b)
+    POST /api/match                     the api_cli JSON line for "MATCH ...": the most similar users for a
+                                        profile given in the body, for a person who is not a user of the corpus:
+                                        {"topk": 20, "public": 1, "gender": 0, "completion": 80, "age": 25,
+                                         "region": [3, null, 27], "clubs": [ids], "friends": [ids], "exclude": [uids],
+                                         "tokens": {"<column index>": [[tid, tf], ...]}}, every field optional.
+                                        Text columns are token ids: callers that ran the reference's encoder, or
+                                        that match on the fixed fields and clubs only (no text -> id ETL here).
 
 What differs, because the reference's file cannot run as written:
   * it has unresolved merge-conflict markers (app.py:38-42, 147-159); the start-up wait here
@@ -42,6 +49,42 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_CLI = os.path.join(HERE, "pokec_api_cli")
 KINDS = {"graph": "graph", "collab": "collaborative", "interest": "interest", "clubs": "clubs"}
+
+
+def match_line(body):
+    """The api_cli "MATCH ..." line of a POST /api/match body (csrc/match_line.h); ValueError on a
+    field of the wrong shape."""
+    if not isinstance(body, dict):
+        raise ValueError("the body must be a JSON object")
+    unknown = set(body) - {"topk", "public", "gender", "completion", "age", "region", "clubs", "friends", "exclude", "tokens"}
+    if unknown:
+        raise ValueError("unknown field: " + sorted(unknown)[0])
+
+    def ints(name, v):
+        if not isinstance(v, (list, tuple)) or any(isinstance(x, bool) or not isinstance(x, int) for x in v):
+            raise ValueError(name + " must be a list of integers")
+        return ",".join(str(x) for x in v)
+
+    words = ["MATCH", str(int(body.get("topk", 20)))]
+    for key in ("public", "gender", "completion", "age"):
+        if body.get(key) is not None:
+            if isinstance(body[key], bool) or not isinstance(body[key], int):
+                raise ValueError(key + " must be an integer")
+            words.append(f"{key}={body[key]}")
+    if body.get("region") is not None:
+        reg = list(body["region"])
+        if len(reg) > 3 or any(x is not None and (isinstance(x, bool) or not isinstance(x, int)) for x in reg):
+            raise ValueError("region must be up to three integers or nulls")
+        words.append("region=" + ",".join("" if x is None or x < 0 else str(x) for x in reg))
+    for key in ("clubs", "friends", "exclude"):
+        if body.get(key):
+            words.append(f"{key}=" + ints(key, body[key]))
+    for t, row in sorted((int(t), row) for t, row in (body.get("tokens") or {}).items()):
+        if t < 0 or any(not isinstance(p, (list, tuple)) or len(p) != 2 for p in row):
+            raise ValueError("tokens must map a column index to [[tid, tf], ...]")
+        if row:
+            words.append(f"c{t}=" + ",".join(ints("tokens", p).replace(",", ":") for p in row))
+    return " ".join(words)
 
 
 def load_config(root):
@@ -165,6 +208,7 @@ def create_app(root, cli_cmd=None, load_users=None, ready_timeout=120.0, request
                 f"<h1>Pokec recommender</h1><p>Loaded users: {n}</p>"
                 "<p>GET /api/user/{uid}, /api/recommend/{graph|collab|interest|clubs}/{uid}?topk=20</p>"
                 "<p>GET /api/explain/{a}/{b}: the per-field terms of the similarity of users a and b</p>"
+                "<p>POST /api/match: the most similar users for a profile given in the body</p>"
                 "</body></html>")
 
     @app.get("/health")
@@ -193,6 +237,14 @@ def create_app(root, cli_cmd=None, load_users=None, ready_timeout=120.0, request
     @app.get("/api/explain/{a}/{b}")
     def api_explain(a: int, b: int):
         return JSONResponse(cli_json(f"EXPLAIN {a} {b}"))
+
+    @app.post("/api/match")
+    def api_match(body: dict):
+        try:
+            line = match_line(body)
+        except (ValueError, TypeError) as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        return JSONResponse(cli_json(line))
 
     def recommend(kind):
         def route(uid: int, topk: int = 20):

@@ -5,6 +5,10 @@
 // One command is the engine's own: EXPLAIN <a> <b> prints the breakdown of FAS(a, b)
 // (pf_fas_pairs_terms): {"a":A,"b":B,"score":S,"used":U,"possible":7+T,"terms":{name:term,...}},
 // the present slots in slot order, doubles with max_digits10 digits (a JSON parse gives them back).
+// Another is MATCH <topk> [key=value]... (csrc/match_line.h): the all-candidates top-k for a profile
+// given on the line, for a person who is not a user of the corpus (pf_recommend_interest_profile).
+// It answers {"recommendations":{"interest":[{"id":..,"score":..},..]}}, USER's list format, or
+// {"error":"bad request","detail":..} / {"error":"engine failure","detail":..}.
 //
 //   pokec_api_cli [load_users] [--root DIR] [--device N] [--no-cap] [--cache PATH]
 //
@@ -24,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "match_line.h"
 #include "pokec_io.h"
 
 namespace {
@@ -186,6 +191,27 @@ int main(int argc, char** argv) {
             write_list(os, "interest", g, nullptr);  // recommend_by_interest == graph (recommender_graph.cpp:224-227)
             os << ",";
             write_list(os, "clubs", cl, ds);
+            os << "}}";
+            std::cout << os.str() << std::endl;
+            continue;
+        }
+        if (cmd == "MATCH") {
+            pokec::MatchLine m;
+            std::string why;
+            if (!pokec::parse_match_line(line.substr(line.find("MATCH") + 5), pf_num_cols(ctx), m, why)) {
+                std::cout << "{\"error\":\"bad request\",\"detail\":\"" << json_escape(why) << "\"}" << std::endl;
+                continue;
+            }
+            const pf_query_profile q = m.profile();
+            List r(m.topk > 0 ? m.topk : 1);
+            if (pf_recommend_interest_profile(ctx, &q, 1, m.topk, r.id.data(), r.score.data(), &r.n) != PF_OK) {
+                std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
+                std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
+                continue;
+            }
+            std::ostringstream os;
+            os << "{\"recommendations\":{";
+            write_list(os, "interest", r, nullptr);
             os << "}}";
             std::cout << os.str() << std::endl;
             continue;

@@ -152,9 +152,11 @@ struct PairChunk {
 // threads.  A group's pairs are cut into blocks of block_pairs (a PairBlock's count).  run(chunk)
 // launches the chunk's kernel, fetches its results and synchronises the stream before it returns
 // (the pinned buffers are reused by the next chunk).
+// pv (optional): the A side of every group is this by-value profile, not a stored user (qidx then
+// only groups the pairs); its image is built by the same builder and staged in the same pool.
 template <class Run>
 int pair_chunks(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
-                uint32_t block_pairs, size_t max_pairs, Run&& run) {
+                uint32_t block_pairs, size_t max_pairs, const pf::ProfileView* pv, Run&& run) {
     size_t g0 = 0;
     while (g0 < qidx.size()) {
         // chunk [g0, g1)
@@ -181,7 +183,8 @@ int pair_chunks(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<s
             for (int w = 0; w < th; ++w)
                 ts.emplace_back([&, w]() {
                     for (size_t i = (size_t)w; i < uq.size(); i += (size_t)th)
-                        ok[i] = pf::build_query(c->hc, c->hs.packed, uq[i], nullptr, qi[i]) ? 1 : 0;
+                        ok[i] = (pv ? pf::build_query(c->hc, c->hs.packed, *pv, nullptr, qi[i])
+                                    : pf::build_query(c->hc, c->hs.packed, uq[i], nullptr, qi[i])) ? 1 : 0;
                 });
             for (auto& t : ts) t.join();
         }
@@ -233,7 +236,7 @@ int pair_chunks(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<s
 // sel (on == 0: none): a field selection every pair is scored under (pf_fas_pairs_select)
 int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
               std::vector<std::vector<float>>& out, DBuf* keep = nullptr, std::vector<int64_t>* goff = nullptr,
-              const pf::FieldSel& sel = pf::FieldSel{}) {
+              const pf::FieldSel& sel = pf::FieldSel{}, const pf::ProfileView* pv = nullptr) {
     out.assign(qidx.size(), {});
     if (keep) {
         size_t tot = 0;
@@ -245,7 +248,7 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
         HIPCHK(c, keep->ensure(std::max<size_t>(tot, 1) * sizeof(float)));
     }
     for (size_t g = 0; g < qidx.size(); ++g) out[g].assign(slots[g].size(), 0.f);
-    return pair_chunks(c, qidx, slots, kPairThreads, (size_t)8u << 20, [&](const PairChunk& k) -> int {
+    return pair_chunks(c, qidx, slots, kPairThreads, (size_t)8u << 20, pv, [&](const PairChunk& k) -> int {
         HIPCHK(c, c->h_scores.ensure(k.npairs * sizeof(float)));
         float* dsc = nullptr;
         if (keep) {
@@ -277,10 +280,10 @@ int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std
 // to 256 MB (a row is up to 71 doubles where a score is one float).
 int run_pair_terms(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
                    const std::vector<std::vector<int64_t>>& dest, pf_pair_terms_head* head, double* terms,
-                   const pf::FieldSel& sel) {
+                   const pf::FieldSel& sel, const pf::ProfileView* pv = nullptr) {
     const size_t W = (size_t)(pf::kNumFixed + c->hc.T);
     const size_t max_pairs = ((size_t)256u << 20) / (W * sizeof(double));
-    return pair_chunks(c, qidx, slots, (uint32_t)pf::kTermsPairs, max_pairs, [&](const PairChunk& k) -> int {
+    return pair_chunks(c, qidx, slots, (uint32_t)pf::kTermsPairs, max_pairs, pv, [&](const PairChunk& k) -> int {
         const size_t hb = k.npairs * sizeof(pf_pair_terms_head), tb = k.npairs * W * sizeof(double);
         HIPCHK(c, c->d_thead.ensure(hb));
         HIPCHK(c, c->d_terms.ensure(tb));
@@ -715,22 +718,17 @@ int build_resident_post(pf_ctx* c) {
 
 // K1: the record-stream scan for `idx` (valid query indices) into d_keys rows `rows`.
 // One pinned staging buffer [refs | rows | sync | image pool] goes up in a single async copy.
-int scan_stream(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<int32_t>& rows, int k, uint64_t* d_keys,
-                hipStream_t s, bool timed) {
-    if (idx.empty()) return PF_OK;
+// build(q, qi) makes query q's K1 image (false: its hash table cannot be built).
+template <class Build>
+int scan_stream_images(pf_ctx* c, int nq, const std::vector<int32_t>& rows, int k, uint64_t* d_keys, hipStream_t s,
+                       bool timed, Build build) {
+    if (nq == 0) return PF_OK;
     Images im;
     pf::QImageHost qi;
-    std::vector<int32_t> excl;
-    for (int32_t i : idx) {
-        const int32_t u = c->hc.uid[i];
-        excl.clear();
-        auto it = c->hc.adj.find(u);
-        if (it != c->hc.adj.end()) excl = it->second;
-        excl.push_back(u);
-        if (!pf::build_query(c->hc, c->hs.packed, i, &excl, qi)) return c->fail(PF_EUNSUPP, "query hash table too large");
+    for (int q = 0; q < nq; ++q) {
+        if (!build(q, qi)) return c->fail(PF_EUNSUPP, "query hash table too large");
         add_image(im, qi);
     }
-    const int nq = (int)idx.size();
     const int tiles = c->tile_end - c->tile_begin;
     // one resident round of blocks over the batch: tiles come from a per-query queue, so
     // the waves that exist balance the work themselves
@@ -769,6 +767,51 @@ int scan_stream(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<in
         c->last_ev1 = e1;
     }
     return PF_OK;
+}
+
+int scan_stream(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<int32_t>& rows, int k, uint64_t* d_keys,
+                hipStream_t s, bool timed) {
+    std::vector<int32_t> excl;
+    return scan_stream_images(c, (int)idx.size(), rows, k, d_keys, s, timed, [&](int q, pf::QImageHost& qi) {
+        const int32_t i = idx[q], u = c->hc.uid[i];
+        excl.clear();
+        auto it = c->hc.adj.find(u);
+        if (it != c->hc.adj.end()) excl = it->second;
+        excl.push_back(u);
+        return pf::build_query(c->hc, c->hs.packed, i, &excl, qi);
+    });
+}
+
+// The all-candidates scan of by-value profiles (pf_recommend_interest_profile) into d_keys rows 0 ..:
+// scan_all's routing with the images built from the views and the call's exclusion lists; there is
+// no resident image to launch from, so one profile takes the upload path (stage_post, scan_post_one).
+int scan_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
+    const size_t nq = ps.size();
+    std::vector<int32_t> all_rows(nq);
+    for (size_t q = 0; q < nq; ++q) all_rows[q] = (int32_t)q;
+    auto stream = [&](const std::vector<int32_t>& which, bool tm) {
+        return scan_stream_images(c, (int)which.size(), which, k, d_keys, s, tm, [&](int q, pf::QImageHost& qi) {
+            const pf::ProfileOwned& p = ps[(size_t)which[q]];
+            return pf::build_query(c->hc, c->hs.packed, p.v, &p.excl, qi);
+        });
+    };
+    if (!c->use_post()) return stream(all_rows, timed);
+    std::vector<std::vector<uint8_t>> imgs(nq);
+    std::vector<uint8_t> fits(nq, 1);
+    par_jobs(nq, [&](size_t q) {
+        pf::build_query_post(c->hc, c->hp, ps[q].v, ps[q].excl, imgs[q]);
+        const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q].data() + sizeof(pf::QConst));
+        fits[q] = post_image_lds(h) + filt_lds(c) <= kK5LdsCap;
+    });
+    std::vector<const std::vector<uint8_t>*> pi;
+    std::vector<int32_t> prow, sidx;
+    for (size_t q = 0; q < nq; ++q) {
+        if (fits[q]) { pi.push_back(&imgs[q]); prow.push_back((int32_t)q); }
+        else sidx.push_back((int32_t)q);
+    }
+    const int rc = scan_post(c, pi, prow, k, d_keys, s, timed);
+    if (rc != PF_OK) return rc;
+    return stream(sidx, timed && pi.empty());
 }
 
 // All-candidates scan for `idx` (valid query indices) into d_keys rows `rows`.  The postings
@@ -1222,6 +1265,145 @@ int pf_recommend_interest_all_terms(pf_ctx* c, const int32_t* q, int32_t nq, int
         }
     }
     return run_pair_terms(c, tg.qidx, tg.slots, tg.dest, head, terms, c->sel);
+}
+
+// the by-value profiles of a call, checked and resolved against the engine's corpus
+static int resolve_profiles(pf_ctx* c, const pf_query_profile* q, int32_t nq, std::vector<pf::ProfileOwned>& ps) {
+    ps.clear();
+    ps.resize((size_t)nq);  // sized once: the views point into their own elements
+    for (int32_t i = 0; i < nq; ++i) {
+        std::string why;
+        const int rc = pf::make_profile_view(c->hc, c->hs.packed, q[i], ps[(size_t)i], why);
+        if (rc != PF_OK) return c->fail(rc, why);
+    }
+    return PF_OK;
+}
+
+static int recommend_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps, int32_t topk, int32_t* ou, float* os,
+                              int32_t* oc) {
+    const int32_t nq = (int32_t)ps.size();
+    HIPCHK(c, c->d_out.ensure((size_t)nq * topk * sizeof(uint64_t)));
+    const size_t chunk = 256;
+    for (size_t b = 0; b < ps.size(); b += chunk) {
+        // a launch's share of a longer call: views of the same arrays
+        std::vector<pf::ProfileOwned> part;
+        const std::vector<pf::ProfileOwned>* use = &ps;
+        if (ps.size() > chunk) {
+            part.resize(std::min(ps.size(), b + chunk) - b);
+            for (size_t i = 0; i < part.size(); ++i) {
+                part[i].v = ps[b + i].v;
+                part[i].excl = ps[b + i].excl;
+            }
+            use = &part;
+        }
+        const int rc = scan_profiles(c, *use, topk, c->d_out.as<uint64_t>() + b * (size_t)topk, c->stream, b == 0);
+        if (rc != PF_OK) return rc;
+    }
+    std::vector<uint64_t> keys((size_t)nq * topk);
+    HIPCHK(c, hipMemcpyAsync(keys.data(), c->d_out.p, keys.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
+    for (int i = 0; i < nq; ++i) pf_decode_keys(&keys[(size_t)i * topk], topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
+    return PF_OK;
+}
+
+static int profile_args(pf_ctx* c, const pf_query_profile* q, int32_t nq, int32_t topk, int32_t* ou, float* os, int32_t* oc) {
+    if (!c) return PF_EINVAL;
+    if (nq < 0 || topk < 0) return c->fail(PF_EINVAL, "query profile: negative nq / topk");
+    if (nq && (!q || !oc || (topk && (!ou || !os)))) return c->fail(PF_EINVAL, "query profile: null argument with nq > 0");
+    if (topk > pf::kMaxTopK) return c->fail(PF_EUNSUPP, "query profile: topk above the scan kernels' bound (64)");
+    return PF_OK;
+}
+
+int pf_recommend_interest_profile(pf_ctx* c, const pf_query_profile* q, int32_t nq, int32_t topk, int32_t* ou, float* os,
+                                  int32_t* oc) {
+    int rc = profile_args(c, q, nq, topk, ou, os, oc);
+    if (rc != PF_OK || nq == 0) return rc;
+    (void)hipSetDevice(c->device);
+    std::vector<pf::ProfileOwned> ps;
+    if ((rc = resolve_profiles(c, q, nq, ps)) != PF_OK) return rc;
+    for (int i = 0; i < nq; ++i) oc[i] = 0;
+    if (topk == 0) return PF_OK;
+    return recommend_profiles(c, ps, topk, ou, os, oc);
+}
+
+// the slots of the stored B side of a profile's pairs (one group: the profile); unknown uids are left out
+static void profile_pair_slots(const pf_ctx* c, const int32_t* b, int64_t n, std::vector<int32_t>& slots,
+                               std::vector<int64_t>& dest) {
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t ib = c->hc.idx_of(b[i]);
+        if (ib < 0) continue;
+        slots.push_back(c->hs.slot_of_idx[ib]);
+        dest.push_back(i);
+    }
+}
+
+int pf_fas_profile_pairs(pf_ctx* c, const pf_query_profile* a, const int32_t* b, int64_t n, const pf_field_select* s,
+                         float* out) {
+    if (!c) return PF_EINVAL;
+    if (n < 0 || !a || (n && (!b || !out))) return c->fail(PF_EINVAL, "profile pairs: null argument");
+    pf::FieldSel d;
+    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "profile pairs: unknown bits in fixed / flags");
+    (void)hipSetDevice(c->device);
+    std::vector<pf::ProfileOwned> ps;
+    int rc = resolve_profiles(c, a, 1, ps);
+    if (rc != PF_OK) return rc;
+    std::vector<std::vector<int32_t>> slots(1);
+    std::vector<int64_t> dest;
+    profile_pair_slots(c, b, n, slots[0], dest);
+    for (int64_t i = 0; i < n; ++i) out[i] = NAN;
+    std::vector<std::vector<float>> res;
+    if ((rc = run_pairs(c, {0}, slots, res, nullptr, nullptr, d, &ps[0].v)) != PF_OK) return rc;
+    for (size_t j = 0; j < dest.size(); ++j) out[dest[j]] = res[0][j];
+    return PF_OK;
+}
+
+int pf_fas_profile_pairs_terms(pf_ctx* c, const pf_query_profile* a, const int32_t* b, int64_t n, const pf_field_select* s,
+                               pf_pair_terms_head* head, double* terms) {
+    if (!c) return PF_EINVAL;
+    if (n < 0 || !a || (n && (!b || !head || !terms))) return c->fail(PF_EINVAL, "profile pairs terms: null argument");
+    pf::FieldSel d;
+    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "profile pairs terms: unknown bits in fixed / flags");
+    (void)hipSetDevice(c->device);
+    std::vector<pf::ProfileOwned> ps;
+    const int rc = resolve_profiles(c, a, 1, ps);
+    if (rc != PF_OK) return rc;
+    const size_t W = (size_t)(PF_NUM_FIXED + c->hc.T);
+    std::vector<std::vector<int32_t>> slots(1);
+    std::vector<std::vector<int64_t>> dest(1);
+    profile_pair_slots(c, b, n, slots[0], dest[0]);
+    for (int64_t i = 0; i < n; ++i) {  // an unknown uid keeps this: NaN, nothing present, the row all 0.0
+        head[i] = pf_pair_terms_head{NAN, 0u, 0ull};
+        std::fill(terms + (size_t)i * W, terms + (size_t)(i + 1) * W, 0.0);
+    }
+    return run_pair_terms(c, {0}, slots, dest, head, terms, d, &ps[0].v);
+}
+
+int pf_recommend_interest_profile_terms(pf_ctx* c, const pf_query_profile* q, int32_t nq, int32_t topk, int32_t* ou,
+                                        float* os, int32_t* oc, pf_pair_terms_head* head, double* terms) {
+    int rc = profile_args(c, q, nq, topk, ou, os, oc);
+    if (rc != PF_OK || nq == 0) return rc;
+    if (topk && (!head || !terms)) return c->fail(PF_EINVAL, "query profile: null argument with nq > 0");
+    (void)hipSetDevice(c->device);
+    std::vector<pf::ProfileOwned> ps;
+    if ((rc = resolve_profiles(c, q, nq, ps)) != PF_OK) return rc;
+    for (int i = 0; i < nq; ++i) oc[i] = 0;
+    if (topk == 0) return PF_OK;
+    if ((rc = recommend_profiles(c, ps, topk, ou, os, oc)) != PF_OK) return rc;
+    // the (profile, winner) pairs, profile by profile: each has an image of its own
+    for (int32_t i = 0; i < nq; ++i) {
+        if (oc[i] <= 0) continue;
+        std::vector<std::vector<int32_t>> slots(1);
+        std::vector<std::vector<int64_t>> dest(1);
+        for (int32_t j = 0; j < oc[i]; ++j) {
+            const int32_t ib = c->hc.idx_of(ou[(size_t)i * topk + j]);
+            if (ib < 0) return c->fail(PF_EINTERNAL, "scan result without a profile");
+            slots[0].push_back(c->hs.slot_of_idx[ib]);
+            dest[0].push_back((int64_t)i * topk + j);
+        }
+        if ((rc = run_pair_terms(c, {0}, slots, dest, head, terms, c->sel, &ps[(size_t)i].v)) != PF_OK) return rc;
+    }
+    return PF_OK;
 }
 
 int pf_recommend_interest(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, int32_t mode, int32_t limit,

@@ -81,9 +81,7 @@ __global__ __launch_bounds__(kIdfThreads) void idf_norms_kernel(const int64_t* _
                 else up = mid;
             }
             tid[k] = (int32_t)(lo - s0);
-            const double idf = hi ? (double)tab_idf[lo] : 1.0;
-            const double w = (double)tf[k] * idf;
-            nb += w * w;
+            norm_add(nb, tf[k], hi ? (double)tab_idf[lo] : 1.0);
         }
         sqrt_nb[r] = sqrt(nb);
     }

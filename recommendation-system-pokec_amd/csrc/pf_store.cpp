@@ -5,6 +5,7 @@
 #include "pf_store.h"
 
 #include "pf_debug.h"
+#include "pf_filter.h"
 
 #include <algorithm>
 #include <atomic>
@@ -511,17 +512,48 @@ void qconst_ratio_row(const HostCorpus& hc, int slot, int a, double* out) {
         out[v] = a > 0 ? term(hc, slot, (double)std::min(a, v) / (double)std::max(a, v)) : 0.0;
 }
 
-static void fill_qconst(const HostCorpus& hc, bool packed, int32_t i, QConst& c) {
+ProfileView view_of(const HostCorpus& hc, int32_t i) {
+    ProfileView a;
+    a.pub = hc.pub[i]; a.gen = hc.gen[i]; a.comp = hc.comp[i]; a.age = hc.age[i];
+    for (int k = 0; k < 3; ++k) a.reg[k] = hc.reg[3 * (size_t)i + k];
+    a.clubs = hc.clubs.data() + hc.club_off[i];
+    a.n_clubs = hc.club_off[i + 1] - hc.club_off[i];
+    a.friends = hc.friends.data() + hc.friend_off[i];
+    a.n_friends = hc.friend_off[i + 1] - hc.friend_off[i];
+    a.tok_off = hc.tok_off.data() + (size_t)i * hc.T;  // the corpus's own offsets: rank / tf are its arrays
+    a.rank = hc.tid.data();
+    a.tf = hc.tf.data();
+    a.sqrt_na = hc.sqrt_nb.data() + (size_t)i * hc.T;
+    return a;
+}
+
+namespace {
+// A token's idf as its image carries it: 1.0 for a column without an idf map (recommender.cpp:78, A7)
+double view_idf(const HostCorpus& hc, const ProfileView& a, int t, int64_t k) {
+    if (!hc.has_idf[t]) return 1.0;
+    return a.idf ? (double)a.idf[k] : (double)hc.idf_of(t, a.rank[k]);
+}
+// Equality code of a public / gender value: a stored user's is in the map; a by-value profile's
+// value no user has is present and equal to nobody (the code pf_filter.h reserves for that)
+uint32_t view_code(const std::unordered_map<int32_t, uint32_t>& m, int32_t v, bool by_value) {
+    if (v < 0) return kCodeMissing;
+    if (!by_value) return m.at(v);
+    const auto it = m.find(v);
+    return it == m.end() ? kFiltCodeNobody : it->second;
+}
+}  // namespace
+
+static void fill_qconst(const HostCorpus& hc, bool packed, const ProfileView& a, QConst& c) {
     const int T = hc.T;
     qconst_template(hc, packed, c);
-    c.pubcode = hc.pub[i] < 0 ? kCodeMissing : hc.pub_code.at(hc.pub[i]);
-    c.gencode = hc.gen[i] < 0 ? kCodeMissing : hc.gen_code.at(hc.gen[i]);
-    c.comp = hc.comp[i];
-    c.age = hc.age[i];
-    for (int k = 0; k < 3; ++k) c.reg[k] = hc.reg[3 * (size_t)i + k];
+    c.pubcode = view_code(hc.pub_code, a.pub, a.by_value);
+    c.gencode = view_code(hc.gen_code, a.gen, a.by_value);
+    c.comp = a.comp;
+    c.age = a.age;
+    for (int k = 0; k < 3; ++k) c.reg[k] = a.reg[k];
     c.a_regcnt = (c.reg[0] >= 0) + (c.reg[1] >= 0) + (c.reg[2] >= 0);
-    c.n_clubs = (int32_t)(hc.club_off[i + 1] - hc.club_off[i]);
-    c.n_friends = (int32_t)(hc.friend_off[i + 1] - hc.friend_off[i]);
+    c.n_clubs = (int32_t)a.n_clubs;
+    c.n_friends = (int32_t)a.n_friends;
     c.sqrt_clubs = std::sqrt((double)c.n_clubs);
     c.sqrt_friends = std::sqrt((double)c.n_friends);
     qconst_sig_reg(hc, c.a_regcnt, c.sig_reg);
@@ -529,41 +561,118 @@ static void fill_qconst(const HostCorpus& hc, bool packed, int32_t i, QConst& c)
     qconst_ratio_row(hc, PF_F_AGE, c.age, c.sig_age);
     c.colmask = 0;
     for (int t = 0; t < T; ++t) {
-        const size_t r = (size_t)i * T + t;
-        c.sqrt_na[t] = hc.sqrt_nb[r];
-        if (hc.tok_off[r + 1] != hc.tok_off[r]) c.colmask |= 1ull << t;
+        c.sqrt_na[t] = a.sqrt_na[t];
+        if (a.tok_off[t + 1] != a.tok_off[t]) c.colmask |= 1ull << t;
     }
 }
 
+int make_profile_view(const HostCorpus& hc, bool packed, const pf_query_profile& q, ProfileOwned& out, std::string& err) {
+    const int T = hc.T;
+    auto bad = [&](int rc, const char* w) { err = std::string("query profile: ") + w; return rc; };
+    if (q.flags != 0u) return bad(PF_EINVAL, "flags must be 0");
+    if (q.n_clubs < 0 || q.n_friends < 0 || q.n_exclude < 0) return bad(PF_EINVAL, "negative count");
+    if ((q.n_clubs && !q.club_ids) || (q.n_friends && !q.friend_ids) || (q.n_exclude && !q.exclude_uid))
+        return bad(PF_EINVAL, "null array with a non-zero count");
+    // what pf_open refuses for a user (build_store, build_postings)
+    if (q.n_clubs > 0xFFFF || q.n_friends > 0xFFFF) return bad(PF_EUNSUPP, "more than 65535 clubs or friends");
+    auto repeats = [](const uint32_t* ids, int32_t n) {
+        std::vector<uint32_t> v(ids, ids + n);
+        std::sort(v.begin(), v.end());
+        for (size_t a = 0, b = 0; a < v.size(); a = b) {
+            while (b < v.size() && v[b] == v[a]) ++b;
+            if (b - a > 255) return true;
+        }
+        return false;
+    };
+    if (repeats(q.club_ids, q.n_clubs) || repeats(q.friend_ids, q.n_friends))
+        return bad(PF_EUNSUPP, "a club / friend id repeats more than 255 times");
+    ProfileView& v = out.v;
+    v = ProfileView{};
+    v.by_value = true;
+    v.pub = q.public_flag; v.gen = q.gender; v.comp = q.completion; v.age = q.age;
+    for (int k = 0; k < 3; ++k) v.reg[k] = q.region[k];
+    v.clubs = q.club_ids; v.n_clubs = q.n_clubs;
+    v.friends = q.friend_ids; v.n_friends = q.n_friends;
+    out.tok_off.assign((size_t)T + 1, 0);
+    out.rank.clear(); out.tf.clear(); out.idf.clear();
+    out.sqrt_na.assign((size_t)std::max(T, 1), 0.0);
+    std::vector<std::pair<int32_t, int32_t>> row;
+    for (int t = 0; t < T && q.tok_off; ++t) {
+        const int64_t b = q.tok_off[t], e = q.tok_off[t + 1];
+        if (b < 0 || e < b) return bad(PF_EINVAL, "tok_off is not monotone");
+        if (e > b && (!q.tok_tid || !q.tok_tf)) return bad(PF_EINVAL, "null token arrays");
+        row.clear();
+        for (int64_t k = b; k < e; ++k) {
+            if (q.tok_tid[k] < 0) return bad(PF_EINVAL, "negative token id");
+            const int32_t tf = q.tok_tf[k];
+            if (packed ? (tf < 0 || tf > 255) : (tf < -(1 << 23) || tf >= (1 << 23)))
+                return bad(PF_EUNSUPP, "token count outside the record encoding");
+            row.emplace_back(q.tok_tid[k], tf);
+        }
+        std::sort(row.begin(), row.end());  // rows are kept in ascending id order (build_host_corpus)
+        for (size_t k = 1; k < row.size(); ++k)
+            if (row[k].first == row[k - 1].first) return bad(PF_EINVAL, "token id repeated within a column");
+        const auto& ids = hc.tid_of_rank[t];
+        double nb = 0.0;
+        for (const auto& tk : row) {
+            const auto it = std::lower_bound(ids.begin(), ids.end(), tk.first);
+            out.rank.push_back(it != ids.end() && *it == tk.first ? (int32_t)(it - ids.begin()) : -1);
+            out.tf.push_back(tk.second);
+            const float idf = hc.has_idf[t] ? hc.idf_of_tid(t, tk.first) : 1.0f;  // pf_idf's rule; raw counts (A7)
+            out.idf.push_back(idf);
+            norm_add(nb, tk.second, (double)idf);
+        }
+        out.sqrt_na[t] = std::sqrt(nb);
+        out.tok_off[t + 1] = (int64_t)out.rank.size();
+    }
+    if (out.rank.empty()) { out.rank.push_back(-1); out.tf.push_back(0); out.idf.push_back(1.0f); }  // valid pointers
+    v.tok_off = out.tok_off.data();
+    v.rank = out.rank.data();
+    v.tf = out.tf.data();
+    v.idf = out.idf.data();
+    v.sqrt_na = out.sqrt_na.data();
+    out.excl.assign(q.exclude_uid, q.exclude_uid + q.n_exclude);
+    return PF_OK;
+}
+
 bool build_query(const HostCorpus& hc, bool packed, int32_t i, const std::vector<int32_t>* excl, QImageHost& out) {
+    return build_query(hc, packed, view_of(hc, i), excl, out);
+}
+
+bool build_query(const HostCorpus& hc, bool packed, const ProfileView& a, const std::vector<int32_t>* excl, QImageHost& out) {
     const int T = hc.T;
     QConst& c = out.c;
-    fill_qconst(hc, packed, i, c);
+    fill_qconst(hc, packed, a, c);
     // hash items: distinct clubs (T0), distinct friends (T1), (column, token) weights (T2),
     // exclusions (T3); packed corpora merge T0..T2 into one tagged table (pf_types.h)
     std::vector<uint64_t> items[4];
-    std::vector<uint32_t> tmp(hc.clubs.begin() + hc.club_off[i], hc.clubs.begin() + hc.club_off[i + 1]);
+    // a by-value profile's id that no record word can equal (a packed store holds ids below
+    // kIdLimit only) has no entry: it still counts in n_clubs / n_friends (fill_qconst)
+    const auto held = [&](uint32_t x) { return !(a.by_value && packed && x >= kIdLimit); };
+    std::vector<uint32_t> tmp(a.clubs, a.clubs + a.n_clubs);
     std::sort(tmp.begin(), tmp.end());
     tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-    for (uint32_t x : tmp) items[0].push_back(packed ? make_entry(x | kTagClub, 1u) : make_entry(x, 0));
-    tmp.assign(hc.friends.begin() + hc.friend_off[i], hc.friends.begin() + hc.friend_off[i + 1]);
+    for (uint32_t x : tmp)
+        if (held(x)) items[0].push_back(packed ? make_entry(x | kTagClub, 1u) : make_entry(x, 0));
+    tmp.assign(a.friends, a.friends + a.n_friends);
     std::sort(tmp.begin(), tmp.end());
     tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-    for (uint32_t x : tmp) items[1].push_back(packed ? make_entry(x, 0x10000u) : make_entry(x, 0));
+    for (uint32_t x : tmp)
+        if (held(x)) items[1].push_back(packed ? make_entry(x, 0x10000u) : make_entry(x, 0));
     out.vals.clear();
     for (int t = 0; t < T; ++t) {
-        const size_t r = (size_t)i * T + t;
-        if (hc.tok_off[r + 1] == hc.tok_off[r]) continue;
-        for (int64_t k = hc.tok_off[r]; k < hc.tok_off[r + 1]; ++k) {
-            const double idf = hc.has_idf[t] ? (double)hc.idf_of(t, hc.tid[k]) : 1.0;  // recommender.cpp:78 (A7)
+        if (a.tok_off[t + 1] == a.tok_off[t]) continue;
+        for (int64_t k = a.tok_off[t]; k < a.tok_off[t + 1]; ++k) {
+            if (a.rank[k] < 0) continue;  // an id no record holds: in the row's norm only
+            const double idf = view_idf(hc, a, t, k);
             QVal v;
-            v.wq = (double)hc.tf[k] * idf;
+            v.wq = (double)a.tf[k] * idf;
             v.idf = idf;
             const uint32_t vi = (uint32_t)out.vals.size();
             if (packed)
-                items[2].push_back(make_entry(kTagTok | ((uint32_t)t << kTidBits) | (uint32_t)hc.tid[k],
+                items[2].push_back(make_entry(kTagTok | ((uint32_t)t << kTidBits) | (uint32_t)a.rank[k],
                                               kTokVal | vi | ((uint32_t)t << kTidBits)));
-            else items[2].push_back(make_entry((uint32_t)hc.tid[k] | ((uint32_t)t << kWideTidBits), (uint32_t)t | (vi << 8)));
+            else items[2].push_back(make_entry((uint32_t)a.rank[k] | ((uint32_t)t << kWideTidBits), (uint32_t)t | (vi << 8)));
             out.vals.push_back(v);
         }
     }
@@ -894,37 +1003,54 @@ void build_postings(const HostCorpus& hc, HostPost& hp) {
 // Returns the part's size, or 0 when it exceeds out_cap.
 size_t build_query_post_part(const HostCorpus& hc, const HostPost& hp, int32_t i, const std::vector<int32_t>& excl,
                              uint8_t* out, size_t out_cap) {
+    return build_query_post_part(hc, hp, view_of(hc, i), excl, out, out_cap);
+}
+
+size_t build_query_post_part(const HostCorpus& hc, const HostPost& hp, const ProfileView& a,
+                             const std::vector<int32_t>& excl, uint8_t* out, size_t out_cap) {
     const int T = hc.T;
     std::vector<QTok> toks;
     std::vector<QCol> cols;
     for (int t = 0; t < T; ++t) {
-        const size_t r = (size_t)i * T + t;
         const int32_t j0 = (int32_t)toks.size();
-        for (int64_t k = hc.tok_off[r]; k < hc.tok_off[r + 1]; ++k) {
-            const double idf = hc.has_idf[t] ? (double)hc.idf_of(t, hc.tid[k]) : 1.0;  // recommender.cpp:78
-            const double wq = (double)hc.tf[k] * idf;
+        for (int64_t k = a.tok_off[t]; k < a.tok_off[t + 1]; ++k) {
+            const double idf = view_idf(hc, a, t, k);  // recommender.cpp:78
+            const double wq = (double)a.tf[k] * idf;
             if (wq == 0.0) continue;  // adds +-0 to every dot it meets
+            // a stored user's token (tf > 0) is on its own list; a by-value profile's may have none
+            // (an id the corpus does not hold, past the table's end, or held with tf 0 only): it
+            // meets nobody, and stays in the row's norm and in its column's presence
+            const int32_t rk = a.rank[k];
+            const int32_t li = rk >= 0 && (size_t)rk < hp.tok_list[t].size() ? hp.tok_list[t][rk] : -1;
+            if (li < 0) continue;
             QTok q;
-            q.l = hp.lists[hp.tok_list[t][hc.tid[k]]];  // tf > 0: the query itself is on the list
+            q.l = hp.lists[li];
             q.wq = wq;
             q.idf = idf;
             toks.push_back(q);
         }
         // every non-empty query column is listed (none of its tokens may carry weight: then
         // it has no passes), so the kernel adds every common column's term at its column
-        if (hc.tok_off[r + 1] != hc.tok_off[r]) cols.push_back(QCol{t, j0, (int32_t)toks.size(), 0});
+        if (a.tok_off[t + 1] != a.tok_off[t]) cols.push_back(QCol{t, j0, (int32_t)toks.size(), 0});
     }
     std::vector<PList> sets;
-    auto add_sets = [&](const std::vector<int64_t>& o, const std::vector<uint32_t>& ids,
-                        const std::unordered_map<uint32_t, int32_t>& m) -> int32_t {
-        std::vector<uint32_t> v(ids.begin() + o[i], ids.begin() + o[i + 1]);
+    // the distinct ids that have a list (a by-value profile's id nobody holds has none; it counts in
+    // the image's QConst n_clubs / n_friends and their square roots all the same, recommender.cpp:119-128)
+    auto add_sets = [&](const uint32_t* ids, int64_t n, const std::unordered_map<uint32_t, int32_t>& m) -> int32_t {
+        std::vector<uint32_t> v(ids, ids + n);
         std::sort(v.begin(), v.end());
         v.erase(std::unique(v.begin(), v.end()), v.end());
-        for (uint32_t x : v) sets.push_back(hp.lists[m.at(x)]);
-        return (int32_t)v.size();
+        int32_t held = 0;
+        for (uint32_t x : v) {
+            const auto it = m.find(x);
+            if (it == m.end()) continue;
+            sets.push_back(hp.lists[it->second]);
+            ++held;
+        }
+        return held;
     };
-    const int32_t ncl = add_sets(hc.club_off, hc.clubs, hp.club_list);
-    const int32_t nfr = add_sets(hc.friend_off, hc.friends, hp.friend_list);
+    const int32_t ncl = add_sets(a.clubs, a.n_clubs, hp.club_list);
+    const int32_t nfr = add_sets(a.friends, a.n_friends, hp.friend_list);
     std::vector<uint32_t> ex;
     for (int32_t u : excl) {
         const int32_t x = hc.idx_of(u);
@@ -960,25 +1086,32 @@ size_t build_query_post_part(const HostCorpus& hc, const HostPost& hp, int32_t i
     return part;
 }
 
-size_t post_part_bound(const HostCorpus& hc, int32_t i, size_t n_excl) {
+size_t post_part_bound(const HostCorpus& hc, int32_t i, size_t n_excl) { return post_part_bound(hc, view_of(hc, i), n_excl); }
+
+size_t post_part_bound(const HostCorpus& hc, const ProfileView& a, size_t n_excl) {
     auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const int T = hc.T;
-    const size_t ntok = (size_t)(hc.tok_off[(size_t)(i + 1) * T] - hc.tok_off[(size_t)i * T]);
+    const size_t ntok = (size_t)(a.tok_off[T] - a.tok_off[0]);
     size_t nact = 0;
-    for (int t = 0; t < T; ++t) nact += hc.tok_off[(size_t)i * T + t + 1] != hc.tok_off[(size_t)i * T + t];
-    const size_t nset = (size_t)(hc.club_off[i + 1] - hc.club_off[i]) + (size_t)(hc.friend_off[i + 1] - hc.friend_off[i]);
+    for (int t = 0; t < T; ++t) nact += a.tok_off[t + 1] != a.tok_off[t];
+    const size_t nset = (size_t)a.n_clubs + (size_t)a.n_friends;
     return a16(sizeof(QPostHead)) + a16(ntok * sizeof(QTok)) + a16(nact * sizeof(QCol)) + a16(nset * sizeof(PList)) +
            a16(n_excl * 4);
 }
 
 void build_query_post(const HostCorpus& hc, const HostPost& hp, int32_t i, const std::vector<int32_t>& excl,
                       std::vector<uint8_t>& img) {
+    build_query_post(hc, hp, view_of(hc, i), excl, img);
+}
+
+void build_query_post(const HostCorpus& hc, const HostPost& hp, const ProfileView& a, const std::vector<int32_t>& excl,
+                      std::vector<uint8_t>& img) {
     QConst c;
-    fill_qconst(hc, true, i, c);
-    const size_t cap = post_part_bound(hc, i, excl.size());
+    fill_qconst(hc, true, a, c);
+    const size_t cap = post_part_bound(hc, a, excl.size());
     img.assign(sizeof(QConst) + cap, 0);
     std::memcpy(img.data(), &c, sizeof c);
-    const size_t part = build_query_post_part(hc, hp, i, excl, img.data() + sizeof(QConst), cap);
+    const size_t part = build_query_post_part(hc, hp, a, excl, img.data() + sizeof(QConst), cap);
     img.resize(sizeof(QConst) + part);
 }
 

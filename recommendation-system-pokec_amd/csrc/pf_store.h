@@ -141,7 +141,49 @@ struct HostPost {
     int64_t tok_entries = 0;
 };
 
+// One step of a (user, column) row's norm, sqrt(sum ((double)tf * idf)^2) (recommender.cpp:74-90):
+// the stored rows' norms (idf_norms_kernel, pf_idf.hip) and a by-value profile's (make_profile_view)
+// add their tokens through this, in the row's ascending-tid order.  Both sides are built with
+// -ffp-contract=off, so the product and the sum round separately on the device as on the host.
+__host__ __device__ inline void norm_add(double& nb, int32_t tf, double idf) {
+    const double w = (double)tf * idf;
+    nb += w * w;
+}
+
+// The A side of a per-call query image, as the image builders read it: a stored user's rows (views
+// into HostCorpus, view_of) or a profile given by value that no store holds (pf_query_profile,
+// make_profile_view).  Row (column) t's tokens are [tok_off[t], tok_off[t + 1]) of rank / tf / idf,
+// ascending by token id.
+struct ProfileView {
+    int32_t pub = -1, gen = -1, comp = 0, age = 0, reg[3] = {-1, -1, -1};
+    bool by_value = false;      // pub / gen may be values no user has; lists may miss
+    const uint32_t* clubs = nullptr;    // profile order, duplicates kept
+    const uint32_t* friends = nullptr;
+    int64_t n_clubs = 0, n_friends = 0;
+    const int64_t* tok_off = nullptr;   // [T + 1]
+    const int32_t* rank = nullptr;      // the token's column rank; < 0: an id the corpus does not hold
+    const int32_t* tf = nullptr;
+    const float* idf = nullptr;         // resolved per token; null: hc.idf_of(t, rank) (a stored user's row)
+    const double* sqrt_na = nullptr;    // [T] the rows' norms
+};
+
+// A by-value profile's arrays behind its view
+struct ProfileOwned {
+    ProfileView v;
+    std::vector<int64_t> tok_off;
+    std::vector<int32_t> rank, tf;
+    std::vector<float> idf;
+    std::vector<double> sqrt_na;
+    std::vector<int32_t> excl;          // the call's exclusions, as given
+};
+
 int build_host_corpus(const pf_corpus_desc* d, HostCorpus& hc, std::string& err);
+// the view of stored user idx
+ProfileView view_of(const HostCorpus& hc, int32_t idx);
+// Checks q against what pf_open accepts for a user (PF_EINVAL / PF_EUNSUPP with err) and resolves it
+// against the engine's corpus: token ids to column ranks (-1: not held), the engine's idf per token
+// (pf_idf's rule: 1.0 for an id the map does not hold), rows sorted by id, and their norms.
+int make_profile_view(const HostCorpus& hc, bool packed, const pf_query_profile& q, ProfileOwned& out, std::string& err);
 // F3 on the device (pf_idf.hip): the distinct (column, tid) pairs of the corpus (radix sort +
 // run-length encoding); hc.tid rewritten as column ranks, hc.tid_of_rank; hc.idf by rank (with
 // from_profiles: logf over df on the host; else from hc.idf_explicit, 1.0 for absent ids); then
@@ -158,6 +200,13 @@ void build_query_post(const HostCorpus& hc, const HostPost& hp, int32_t idx, con
 size_t build_query_post_part(const HostCorpus& hc, const HostPost& hp, int32_t idx, const std::vector<int32_t>& excl,
                              uint8_t* out, size_t out_cap);
 size_t post_part_bound(const HostCorpus& hc, int32_t idx, size_t n_excl);
+// The same builders for any profile view (the by-index forms above pass view_of(hc, idx): one body)
+void build_query_post(const HostCorpus& hc, const HostPost& hp, const ProfileView& a, const std::vector<int32_t>& excl,
+                      std::vector<uint8_t>& img);
+size_t build_query_post_part(const HostCorpus& hc, const HostPost& hp, const ProfileView& a,
+                             const std::vector<int32_t>& excl, uint8_t* out, size_t out_cap);
+size_t post_part_bound(const HostCorpus& hc, const ProfileView& a, size_t n_excl);
+bool build_query(const HostCorpus& hc, bool packed, const ProfileView& a, const std::vector<int32_t>* excl, QImageHost& out);
 int build_store(const HostCorpus& hc, HostStore& hs, std::string& err);
 // excl: uids to exclude (all-candidates mode), may be null
 // returns false when the cuckoo table cannot be built within kMaxHashLog2

@@ -37,7 +37,9 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_scan_bytes", "pf_scan_prune_stats", "pf_jobs_stats_reset", "pf_jobs_stats_read", "pf_recommend_interest_async",
            "pf_recommend_collab_async", "pf_recommend_clubs_async", "pf_wait", "pf_completed_ticket",
            "pf_set_scan_filter", "pf_scan_filter_count", "pf_set_scan_select", "pf_fas_pairs_select",
-           "pf_num_cols", "pf_fas_pairs_terms", "pf_recommend_interest_all_terms"]
+           "pf_num_cols", "pf_fas_pairs_terms", "pf_recommend_interest_all_terms",
+           "pf_recommend_interest_profile", "pf_fas_profile_pairs", "pf_fas_profile_pairs_terms",
+           "pf_recommend_interest_profile_terms"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
               "pf_dataset_profile_order", "pf_dataset_adj_order", "pf_dataset_profile_json", "pf_dataset_club_name",
@@ -176,6 +178,79 @@ class PairTerms:
         return list(FIXED_FIELD_NAMES) + list(ds_columns)
 
 
+class QueryProfile(ctypes.Structure):
+    """pf_query_profile: a profile given by value, for a person who is not a user of the corpus (the
+    engine's query-by-profile calls).  QueryProfile.make(...) builds one and keeps its arrays alive."""
+    _fields_ = [("public_flag", ctypes.c_int32), ("gender", ctypes.c_int32), ("completion", ctypes.c_int32),
+                ("age", ctypes.c_int32), ("region", ctypes.c_int32 * 3), ("flags", ctypes.c_uint32),
+                ("club_ids", ctypes.c_void_p), ("n_clubs", ctypes.c_int32),
+                ("friend_ids", ctypes.c_void_p), ("n_friends", ctypes.c_int32),
+                ("tok_off", ctypes.c_void_p), ("tok_tid", ctypes.c_void_p), ("tok_tf", ctypes.c_void_p),
+                ("exclude_uid", ctypes.c_void_p), ("n_exclude", ctypes.c_int32)]
+
+    @classmethod
+    def make(cls, public_flag=None, gender=None, completion=None, age=None, region=None, clubs=(), friends=(),
+             tokens=None, exclude=(), n_cols=None):
+        """public_flag / gender: None = missing; completion / age: None = not given; region: up to
+        three parts, None or -1 = missing; clubs / friends: ids in profile order, duplicates kept;
+        tokens: {column index: [(token id, tf), ...]}; exclude: uids never returned (no implicit
+        self, no adjacency).  n_cols: the engine's column count (the engine calls fit() itself)."""
+        p = cls()
+        p.public_flag = -1 if public_flag is None else int(public_flag)
+        p.gender = -1 if gender is None else int(gender)
+        p.completion = 0 if completion is None else int(completion)
+        p.age = 0 if age is None else int(age)
+        reg = list(region or ())[:3]
+        for i in range(3):
+            p.region[i] = -1 if i >= len(reg) or reg[i] is None else int(reg[i])
+        p._clubs = np.ascontiguousarray(np.asarray(list(clubs), dtype=np.uint32))
+        p._friends = np.ascontiguousarray(np.asarray(list(friends), dtype=np.uint32))
+        p._exclude = np.ascontiguousarray(np.asarray(list(exclude), dtype=np.int32))
+        p._tokens = {int(t): [(int(a), int(b)) for a, b in row] for t, row in (tokens or {}).items()}
+        p.club_ids, p.n_clubs = (p._clubs.ctypes.data if len(p._clubs) else None), len(p._clubs)
+        p.friend_ids, p.n_friends = (p._friends.ctypes.data if len(p._friends) else None), len(p._friends)
+        p.exclude_uid, p.n_exclude = (p._exclude.ctypes.data if len(p._exclude) else None), len(p._exclude)
+        p._n_cols = -1
+        return p.fit(max(p._tokens, default=-1) + 1 if n_cols is None else int(n_cols))
+
+    def fit(self, n_cols):
+        """Lay the token arrays out for an engine of n_cols text columns (tok_off has n_cols + 1 entries)."""
+        if getattr(self, "_tokens", None) is None or n_cols == self._n_cols:
+            return self  # as laid out (a struct filled in by hand is taken as it is)
+        if any(t < 0 or t >= n_cols for t in self._tokens):
+            raise ValueError(f"QueryProfile: a token column outside [0, {n_cols})")
+        off, tid, tf = [0], [], []
+        for t in range(n_cols):
+            for a, b in self._tokens.get(t, ()):
+                tid.append(a)
+                tf.append(b)
+            off.append(len(tid))
+        self._off = np.asarray(off, dtype=np.int64)
+        self._tid = np.asarray(tid if tid else [0], dtype=np.int32)
+        self._tf = np.asarray(tf if tf else [0], dtype=np.int32)
+        self.tok_off, self.tok_tid, self.tok_tf = self._off.ctypes.data, self._tid.ctypes.data, self._tf.ctypes.data
+        self._n_cols = n_cols
+        return self
+
+    def fields(self):
+        """The profile back as make()'s keyword arguments (read from the C struct's arrays)."""
+        def arr(ptr, n, ct):
+            return [] if not ptr or n <= 0 else list((ct * n).from_address(ptr))
+        off = arr(self.tok_off, self._n_cols + 1, ctypes.c_int64)
+        nt = off[-1] if off else 0
+        tid, tf = arr(self.tok_tid, nt, ctypes.c_int32), arr(self.tok_tf, nt, ctypes.c_int32)
+        tokens = {t: list(zip(tid[off[t]:off[t + 1]], tf[off[t]:off[t + 1]]))
+                  for t in range(self._n_cols) if off[t + 1] > off[t]}
+        return dict(public_flag=None if self.public_flag < 0 else self.public_flag,
+                    gender=None if self.gender < 0 else self.gender,
+                    completion=None if self.completion == 0 else self.completion,
+                    age=None if self.age == 0 else self.age,
+                    region=[None if r < 0 else r for r in self.region],
+                    clubs=arr(self.club_ids, self.n_clubs, ctypes.c_uint32),
+                    friends=arr(self.friend_ids, self.n_friends, ctypes.c_uint32),
+                    tokens=tokens, exclude=arr(self.exclude_uid, self.n_exclude, ctypes.c_int32))
+
+
 class PfJobsStats(ctypes.Structure):
     _fields_ = [("jobs", ctypes.c_int64), ("candidates", ctypes.c_int64), ("pairs", ctypes.c_int64),
                 ("pair_alg_bytes", ctypes.c_int64), ("pair_record_bytes", ctypes.c_int64),
@@ -191,7 +266,7 @@ class PfDatasetInfo(ctypes.Structure):
 
 
 class FasError(RuntimeError):
-    pass
+    code = None  # the C status code (PF_E*), where a call of the C ABI failed
 
 
 _lib = None
@@ -243,6 +318,10 @@ def lib():
         L.pf_num_cols.restype = I32
         L.pf_fas_pairs_terms.argtypes = [V, V, V, I64, ctypes.POINTER(FieldSelect), V, V]
         L.pf_recommend_interest_all_terms.argtypes = [V, V, I32, I32, V, V, V, V, V]
+        L.pf_recommend_interest_profile.argtypes = [V, V, I32, I32, V, V, V]
+        L.pf_fas_profile_pairs.argtypes = [V, V, V, I64, ctypes.POINTER(FieldSelect), V]
+        L.pf_fas_profile_pairs_terms.argtypes = [V, V, V, I64, ctypes.POINTER(FieldSelect), V, V]
+        L.pf_recommend_interest_profile_terms.argtypes = [V, V, I32, I32, V, V, V, V, V]
         L.pf_scan_keys_async.argtypes = [V, V, I32, I32, V, V]
         L.pf_merge_keys_async.argtypes = [V, V, I32, I32, I32, V, V]
         L.pf_decode_keys.argtypes = [V, I32, V, V, V]
@@ -321,7 +400,9 @@ class FasEngine:
 
     def _check(self, rc, what):
         if rc != PF_OK:
-            raise FasError(f"{what} failed ({rc}): {self._L.pf_last_error(self.h).decode()}")
+            e = FasError(f"{what} failed ({rc}): {self._L.pf_last_error(self.h).decode()}")
+            e.code = rc
+            raise e
 
     @property
     def num_users(self):
@@ -485,6 +566,74 @@ class FasEngine:
                 self.set_scan_filter(prev)
             if select is not None:
                 self.set_scan_select(prev_sel)
+
+    # -- query by profile (pf_query_profile): a person who is not a user of the corpus
+    def _profile_array(self, profiles):
+        ps = [profiles] if isinstance(profiles, QueryProfile) else list(profiles)
+        T = self.num_cols
+        arr = (QueryProfile * max(len(ps), 1))()
+        for i, p in enumerate(ps):
+            ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(p.fit(T)), ctypes.sizeof(QueryProfile))
+        return ps, arr  # ps keeps the profiles' arrays alive over the call
+
+    def _recommend_profile(self, profiles, topk, explain):
+        ps, arr = self._profile_array(profiles)
+        n, k, W = len(ps), max(int(topk), 0), 7 + self.num_cols
+        ou = np.zeros(max(n * k, 1), np.int32)
+        os_ = np.zeros(max(n * k, 1), np.float32)
+        oc = np.zeros(max(n, 1), np.int32)
+        if not explain:
+            self._check(self._L.pf_recommend_interest_profile(self.h, ctypes.byref(arr), n, k, ou.ctypes.data,
+                                                              os_.ctypes.data, oc.ctypes.data),
+                        "pf_recommend_interest_profile")
+            return [(ou[i * k:i * k + oc[i]].copy(), os_[i * k:i * k + oc[i]].copy()) for i in range(n)]
+        head = np.zeros(max(n * k, 1), _HEAD_DTYPE)
+        terms = np.zeros((max(n * k, 1), W), np.float64)
+        self._check(self._L.pf_recommend_interest_profile_terms(self.h, ctypes.byref(arr), n, k, ou.ctypes.data,
+                                                                os_.ctypes.data, oc.ctypes.data, head.ctypes.data,
+                                                                terms.ctypes.data), "pf_recommend_interest_profile_terms")
+        return [(ou[i * k:i * k + oc[i]].copy(), os_[i * k:i * k + oc[i]].copy(),
+                 PairTerms(head[i * k:i * k + oc[i]], terms[i * k:i * k + oc[i]].copy())) for i in range(n)]
+
+    def recommend_profile(self, profiles, k, filter=None, select=None, explain=False):
+        """The all-candidates top-k of each QueryProfile (one, or a list: one call), for people who are
+        not users of the corpus.  filter / select / explain as in recommend_interest_all: the filter and
+        selection in force before the call are restored afterwards.  A profile's exclusions are its own
+        `exclude` list and nothing else."""
+        prev, prev_sel = self._filter, self._select
+        try:
+            if filter is not None:
+                self.set_scan_filter(filter)
+            if select is not None:
+                self.set_scan_select(select)
+            return self._recommend_profile(profiles, k, explain)
+        finally:
+            if filter is not None:
+                self.set_scan_filter(prev)
+            if select is not None:
+                self.set_scan_select(prev_sel)
+
+    def fas_profile_pairs(self, profile, b_uid, select=None):
+        """FAS(A = the QueryProfile, B = each stored b_uid); NaN for an unknown b_uid."""
+        ps, arr = self._profile_array(profile)
+        b = _i32(b_uid)
+        out = np.empty(len(b), np.float32)
+        self._check(self._L.pf_fas_profile_pairs(self.h, ctypes.byref(arr), b.ctypes.data, len(b),
+                                                 None if select is None else ctypes.byref(select), out.ctypes.data),
+                    "pf_fas_profile_pairs")
+        return out
+
+    def fas_profile_pairs_terms(self, profile, b_uid, select=None):
+        """fas_profile_pairs with the per-field terms (a PairTerms)."""
+        ps, arr = self._profile_array(profile)
+        b = _i32(b_uid)
+        n, W = len(b), 7 + self.num_cols
+        head = np.zeros(n, _HEAD_DTYPE)
+        terms = np.zeros((n, W), np.float64)
+        self._check(self._L.pf_fas_profile_pairs_terms(self.h, ctypes.byref(arr), b.ctypes.data, n,
+                                                       None if select is None else ctypes.byref(select),
+                                                       head.ctypes.data, terms.ctypes.data), "pf_fas_profile_pairs_terms")
+        return PairTerms(head, terms)
 
     def fof_candidates(self, uid, limit, flavour=PF_FOF_GRAPH):
         cap = max(int(limit), 1) + 1

@@ -1,0 +1,115 @@
+"""Query by profile (pf_recommend_interest_profile, pf_fas_profile_pairs, their _terms forms): the
+all-candidates scan, the pair scores and the breakdown for a person who is not a user of the corpus,
+given by value (tests/gpu_query_profile_check.py, one fresh process per check).
+
+References.  A copy of a stored user X with exclude = adj[X] + {X} must give the by-uid call's ids
+and score bits (the per-call image is the same image): E's planted queries, the A sides of its
+planted pairs and the clones whose results tie, at k = 1, 10, 64, under both scan kernels, with the
+idf from the profiles and from the golden explicit map, under a filter (gender + age range), a
+selection (two fixed fields and one column off) and with explain=True.  Users E does not hold, Y and
+Z of tests/query_profile_cases.py, are checked bit for bit against the oracle opened on
+C+ = E + {Y, Z} under E's explicit idf map and normalisers, where both sides read the same idf: the
+top-k with Y and Z dropped from the oracle's list, and the pair score against every user of E.  The
+breakdown's head is fas_profile_pairs, its score the row's own sequential sum, a deselected slot
+absent and 0.0.  One call with four profiles equals four calls; two shards merged on the host equal
+the unsharded scan; by-uid results, scan_bytes and E's golden lists are the same before and after a
+run of ad-hoc calls; malformed and out-of-limit profiles are refused with the documented codes."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def run(mode):
+    env = {**os.environ, "PF_DEBUG": ""}
+    r = subprocess.run([sys.executable, os.path.join(HERE, "gpu_query_profile_check.py"), mode], env=env,
+                       capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+
+
+@pytest.mark.parametrize("idf", ["profiles", "explicit"])
+def test_clone_of_a_stored_user_equals_the_by_uid_call(idf):
+    run("clone_" + idf)
+
+
+def test_absent_users_against_the_oracle_terms_batch_shards():
+    run("absent")
+
+
+def test_nothing_sticks_and_errors():
+    run("state")
+
+
+def test_cpp_facade_by_profile(tmp_path):
+    """include/pokec/recommender.h: recommend_by_profile of a copy of a map profile gives
+    recommend_interest_all's list; profile_similarity_adhoc / _terms_adhoc the bits of
+    profile_similarity / _terms; a profile that is not of the map gives NaN from profile_similarity
+    and the same finite bits from profile_similarity_adhoc (tests/cpp/facade_profile_check.cpp)."""
+    import edge_corpus as ec
+    import pokec_testlib as tl
+    exe = str(tmp_path / "facade_profile_check")
+    pkg = os.path.join(tl.ROOT, "recommendation-system-pokec_amd")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I" + os.path.join(tl.ROOT, "include"),
+                    os.path.join(HERE, "cpp", "facade_profile_check.cpp"), "-L" + pkg, "-lpokec_fas",
+                    "-Wl,-rpath," + pkg, "-o", exe], check=True)
+    d = str(tmp_path / "E")
+    os.makedirs(d)
+    ec.write_reference_files(d)
+    uids = [ec.uid_of(i) for i in ec.PLANTED_QUERIES[::3] if i != ec.EMPTY_USER]
+    r = subprocess.run([exe, d], input="\n".join(str(u) for u in uids) + "\n", capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout[-2000:] + r.stderr
+    assert int(r.stdout.split()[1]) >= 10 * len(uids)
+
+
+def test_api_cli_match(tmp_path):
+    """pokec_api_cli: a MATCH line answers the engine's recommend_profile list in USER's list format
+    (ids, scores at the CLI's six decimals); a malformed line and a refused profile answer an error
+    object; the lines before and after are answered as ever."""
+    import json
+
+    import numpy as np
+
+    import edge_corpus as ec
+    import pokec_testlib as tl
+    import query_profile_cases as qc
+    pf = tl.product()
+    sys.path.insert(0, os.path.join(tl.ROOT, "recommendation-system-pokec_amd"))
+    import app as appmod
+    exe = os.path.join(tl.ROOT, "recommendation-system-pokec_amd", "pokec_api_cli")
+    assert os.path.exists(exe), "build with make -C recommendation-system-pokec_amd"
+    d = str(tmp_path)
+    ec.write_reference_files(d)
+    e = tl.read_reference_dir(d)
+    r = qc.y_record()
+    body = {"topk": 10, "public": r["pub"], "gender": r["gen"], "completion": r["comp"], "age": r["age"], "region": r["reg"],
+            "clubs": r["clubs"], "friends": r["friends"], "exclude": qc.ADJ_Y,
+            "tokens": {str(t): [list(kv) for kv in m.items()] for t, m in enumerate(r["toks"]) if m}}
+    clone = qc.record_of_user(e, int(np.nonzero(e.uid == ec.uid_of(ec.CLONE_QUERIES[0]))[0][0]))
+    eng = tl.engine(e)
+    try:
+        want = [eng.recommend_profile(qc.profile_of_record(pf, r, exclude=qc.ADJ_Y), 10)[0],
+                eng.recommend_profile(qc.profile_of_record(pf, clone), 3)[0]]
+    finally:
+        eng.close()
+    cbody = {"topk": 3, "public": clone["pub"], "gender": clone["gen"], "completion": clone["comp"], "age": clone["age"],
+             "region": clone["reg"], "clubs": clone["clubs"], "friends": clone["friends"],
+             "tokens": {str(t): [list(kv) for kv in m.items()] for t, m in enumerate(clone["toks"]) if m}}
+    lines = ["PING", appmod.match_line(body), appmod.match_line(cbody), "MATCH", "MATCH 5 colour=2", "MATCH 65",
+             "MATCH 5 clubs=" + ",".join(["9"] * 256), "PING", "EXIT"]
+    p = subprocess.run([exe], cwd=d, input=("\n".join(lines) + "\n").encode(), capture_output=True, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()
+    out = p.stdout.decode().splitlines()
+    out = out[out.index("READY") + 1:]
+    assert len(out) == len(lines) and out[0] == '{"ok":true}' and out[7] == '{"ok":true}'
+    for line, (ids, sc) in zip(out[1:3], want):
+        j = json.loads(line)
+        assert list(j) == ["recommendations"] and list(j["recommendations"]) == ["interest"]
+        got = j["recommendations"]["interest"]
+        assert [g["id"] for g in got] == [int(i) for i in ids]
+        assert ["%.6f" % g["score"] for g in got] == ["%.6f" % float(s) for s in sc]
+    assert [json.loads(x)["error"] for x in out[3:7]] == ["bad request", "bad request", "engine failure", "engine failure"]
