@@ -448,8 +448,8 @@ int pf_layout(const pf_ctx* ctx, pf_layout_stats* out);
  * (pf_set_scan_select) is ignored as well: the bytes are those of the unselected scan (a selected
  * one reads no entry of a deselected column's or set's lists). */
 int pf_scan_bytes(pf_ctx* ctx, const int32_t* query_uid, int32_t nq, int64_t* out_bytes);
-/* Counters of the postings scan's pruning, summed over the one-query scans of this process
- * since the last reset while PF_DEBUG k5_prune_stats=1 is set (zeros otherwise): out[5] =
+/* Counters of the postings scan's pruning, summed over the postings scans of this process
+ * (one-query launches and batches) since the last reset while PF_DEBUG k5_prune_stats=1 is set (zeros otherwise): out[5] =
  * candidates seen, candidates dropped at a block's start, dropped at a round's end, blocks,
  * blocks begun before the query had a threshold.  A candidate the scan filter drops counts as seen and
  * in neither dropped counter.  Synchronises the device. */

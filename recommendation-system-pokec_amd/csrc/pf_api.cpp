@@ -315,17 +315,19 @@ int run_pair_terms(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vecto
 // K5 mode word (pf_kernels.h): flags only; the block hand-out is launch_post's `claimed`, true for
 // the one-query launches (scan_post with a batch of one, scan_post_resident) and false for batches.
 uint32_t post_mode(bool claimed) {
-    // the one-query instantiation drops candidates that cannot reach the query's shared score
-    // threshold (pf_prune.h): k5_prune=0 off, 1 at block starts only, 2 (default) at round ends too
-    // (A/B; the results are the same bits); k5_prune_stats=1 counts them (pf_scan_prune_stats)
+    // both instantiations drop candidates that cannot reach the query's shared score threshold
+    // (pf_prune.h): k5_prune=0 off, 1 at block starts only, 2 (default) at round ends too (A/B; the
+    // results are the same bits); k5_prune_batch=0 turns only the batches off (the one-build A/B of
+    // cfg 4); k5_prune_stats=1 counts them (pf_scan_prune_stats)
     static const long pr = pf::debug_long("k5_prune", 2);
+    static const bool prb = pf::debug_long("k5_prune_batch", 1) != 0;
     static const bool prs = pf::debug_long("k5_prune_stats", 0) != 0;
     const uint32_t p = pr <= 0 ? 0u : (pf::kPostPrune | (pr == 1 ? pf::kPostPruneBlockOnly : 0u) | (prs ? pf::kPostPruneStats : 0u));
     // filtered launches (pf_set_scan_filter): k5_filter_blockout=0 runs the blocks in which no
     // candidate passes to their end (A/B of the whole-block early-out; the results are the same bits)
     static const bool fko = pf::debug_long("k5_filter_blockout", 1) == 0;
     const uint32_t f = fko ? pf::kPostFiltKeepBlocks : 0u;
-    return (claimed ? p : 0u) | f;
+    return ((claimed || prb) ? p : 0u) | f;
 }
 
 // Blocks per workgroup of a batched postings scan: a workgroup stages its query's tables once

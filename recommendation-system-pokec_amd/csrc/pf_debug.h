@@ -15,10 +15,12 @@
 //                         default 3 (the context's stream, aux, aux2), so consecutive queries' launches
 //                         overlap; 2 leaves out aux2; 4..16 add lanes on streams of their own (for a
 //                         process with more hardware queues, GPU_MAX_HW_QUEUES)
-//   k5_prune=0|1|2        K5: one-query launches drop the candidates that cannot reach the query's shared
-//                         score threshold before their text work (pf_prune.h; the same result bits):
-//                         0 off, 1 at block starts only, 2 (default) at round ends too (A/B)
-//   k5_prune_stats=1      K5: count the candidates seen and dropped (pf_scan_prune_stats)
+//   k5_prune=0|1|2        K5: one-query launches and batches drop the candidates that cannot reach the
+//                         query's shared score threshold before their text work (pf_prune.h; the same
+//                         result bits): 0 off, 1 at block starts only, 2 (default) at round ends too (A/B)
+//   k5_prune_batch=0      K5: the batches do not prune, whatever k5_prune says (the one-query launches
+//                         follow k5_prune; the one-build A/B of cfg 4)
+//   k5_prune_stats=1      K5: count the candidates seen and dropped, batches included (pf_scan_prune_stats)
 //   k5_filter_blockout=0  K5 under a candidate filter (pf_set_scan_filter): blocks in which no candidate
 //                         passes run to their end instead of leaving after the header test (A/B;
 //                         the same result bits)

@@ -56,9 +56,9 @@ int scan_blocks_per_cu(bool packed, bool gtab, uint32_t lds);
 // offsets img_off[] into pool); var_lds = post_var_lds(max n_tok, max lists of an image)
 uint32_t post_var_lds(int n_tok, int n_lists);
 uint32_t post_lds(uint32_t var_lds);
-// mode flags (pf_api.cpp post_mode).  Claimed launches only: kPostPrune = drop candidates below the
-// query's shared score threshold (pf_prune.h), kPostPruneBlockOnly = at block starts only,
-// kPostPruneStats = count them.  kPostFiltKeepBlocks (filtered launches, A/B): a block in which no
+// mode flags (pf_api.cpp post_mode).  Claimed launches and batches alike: kPostPrune = drop candidates
+// below the query's shared score threshold (pf_prune.h; a batch query's is its own sync[q]),
+// kPostPruneBlockOnly = at block starts only, kPostPruneStats = count them.  kPostFiltKeepBlocks (filtered launches, A/B): a block in which no
 // candidate passes the filter runs to its end instead of leaving after its first barrier.
 constexpr uint32_t kPostPrune = 1u << 16, kPostPruneStats = 1u << 17, kPostPruneBlockOnly = 1u << 18;
 constexpr uint32_t kPostFiltKeepBlocks = 1u << 19;
@@ -71,7 +71,7 @@ struct PostLaunch {
     uint32_t var_lds;
     int nq, blk_begin, blk_end, k, blocks;
     uint64_t *parts, *out;
-    ScanSync* sync;  // the launch leaves each query's ScanSync zeroed (post_tail)
+    ScanSync* sync;  // one per query, zeroed (theta and histogram included); the launch leaves each zeroed (post_tail)
     const int32_t* out_rows;
     // the block hand-out, which is the instantiation.  true (nq == 1 only): the grid's workgroups
     // claim every block per XCD group; false: workgroup x of query y takes every blocks-th block of

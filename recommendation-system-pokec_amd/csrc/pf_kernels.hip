@@ -1208,19 +1208,20 @@ __device__ __forceinline__ double tok_product(const PTok* pt, int j, uint32_t tf
 
 // (Round, the serial next_round and the lane-parallel plan_round: pf_plan.h)
 
-// The query's score histogram and theta (ScanSync, pf_prune.h).  At a block's end a wave records the
-// best of its top-k keys that is the block's own (idx in [c0, c1]: each candidate at most once; a key
-// evicted later was still a real candidate with that score) and scores at least thb, the theta the
-// block began with.  One key per wave and block, not all k of them: the true top k of the candidates
-// processed so far are almost surely the best of their own 128, and every agent-scope atomic is
-// served at the memory side, one address at a time: with k keys per wave the first resident
-// round's 36,000 adds on a few dozen bins cost a cfg-2 launch 70 us (0.128 -> 0.200 ms per step).
+// The query's score histogram and theta (ScanSync, pf_prune.h).  At a block's end every wave folds
+// the score bits of the best of its top-k keys that is the block's own (idx in [c0, c1]: each
+// candidate at most once; a key evicted later was still a real candidate with that score) and scores
+// at least thb, the theta the block began with, into one LDS word with a max (positive float bits
+// order as integers): the workgroup's record of the block, nonzero when there is one.  One key per
+// workgroup and block, not one per wave or all k of them: the true top k of the candidates processed
+// so far are almost surely the best of their own block, and every agent-scope atomic is served at
+// the memory side, one address at a time (with k keys per wave the first resident round's 36,000
+// adds on a few dozen bins cost a cfg-2 launch 70 us, 0.128 -> 0.200 ms per step).
 // Any subset recorded is valid: theta is the lower edge of the highest bin with >= k recorded scores
 // at or above it, so >= k real candidates score >= theta.  Relaxed atomics: theta only rises and every
-// value it held is valid, so a reader that sees an older one only prunes less.  Returns whether the
-// wave recorded.
-__device__ __forceinline__ bool prune_record(ScanSync* sy, uint64_t best, int k, uint32_t c0, uint32_t c1,
-                                             uint32_t thb, int lane) {
+// value it held is valid, so a reader that sees an older one only prunes less.
+__device__ __forceinline__ void prune_fold(uint32_t* word, uint64_t best, int k, uint32_t c0, uint32_t c1,
+                                           uint32_t thb, int lane) {
     uint32_t sb = 0u;
     bool rec = false;
     if (lane < k && best != ~0ull) {
@@ -1229,42 +1230,51 @@ __device__ __forceinline__ bool prune_record(ScanSync* sy, uint64_t best, int k,
         rec = idx >= c0 && idx <= c1 && sb >= thb && prune_bin(sb) >= 0;
     }
     const uint64_t bal = __ballot(rec);
-    if (bal == 0ull) return false;
-    if (lane == __ffsll((unsigned long long)bal) - 1)  // ascending keys: the lowest lane holds the best
-        __hip_atomic_fetch_add(&sy->hist[prune_bin(sb)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
+    if (bal == 0ull) return;
+    if (lane == __ffsll((unsigned long long)bal) - 1) atomicMax(word, sb);  // ascending keys: the lowest lane holds the best
 }
 
-// theta from the histogram, by one wave: lane l sums bins top - 13 l .. top - 13 l - 12, a scan over
-// the lanes from the top finds the bin where the count from above reaches k; published with a max.
-// Returns the new theta (>= thb).  Out of line: a workgroup runs it at the start of a block after
-// one in which it recorded, and its 13 counts per lane stay out of the block loop's register budget.
-static __device__ __attribute__((noinline)) uint32_t prune_derive(ScanSync* sy, int k, uint32_t thb, int lane) {
-    constexpr int kPer = (kPruneBins + 63) / 64;
-    uint32_t cb[kPer], s = 0u;
+// theta from the histogram, by one wave at the start of the block after one in which the workgroup
+// recorded (rec, that block's record): the slabs of pf_prune.h, all loads issued together with the
+// load of theta itself.  The wave counts its own record in its registers and sends the record's add
+// only once the loads are back, so the add is not among what they saw and nothing waits for it.
+// The max is sent only if the derived value exceeds both thb and the theta just read.  Returns the
+// block's theta: the highest of thb, the theta read and the derived one (each was valid when read).
+// Out of line: its 13 counts per lane stay out of the block loop's register budget.  Three
+// arguments, not five: with k and the lane passed on their own the filtered instantiations spilled
+// two VGPRs (16 B of scratch).  thk = thb | k: a theta is 0 or a bin's lower edge, its low
+// kPruneShift bits clear, and k <= kMaxTopK fits them.
+static_assert(kMaxTopK < (1 << kPruneShift), "k rides in a theta's low bits");
+static __device__ __attribute__((noinline)) uint32_t prune_derive(ScanSync* sy, uint32_t thk, uint32_t rec) {
+    constexpr uint32_t kLow = (1u << kPruneShift) - 1u;
+    const int lane = (int)(threadIdx.x & 63u), k = (int)(thk & kLow);
+    const uint32_t thb = thk & ~kLow;
+    const int ns = prune_slabs(thb), rb = prune_bin(rec);
+    uint32_t cb[kPruneSlabs];
 #pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-        const int b = kPruneBins - 1 - (kPer * lane + i);
-        cb[i] = b >= 0 ? __hip_atomic_load(&sy->hist[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        s += cb[i];
+    for (int i = 0; i < kPruneSlabs; ++i) {
+        const int b = prune_slab_bin(i, lane);
+        cb[i] = 0u;
+        if (i < ns && prune_bin_live(b, thb)) cb[i] = __hip_atomic_load(&sy->hist[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    const uint32_t incl = wave_incl_scan(s);
-    uint32_t run = incl - s, nt = 0u;
-    if (run < (uint32_t)k && incl >= (uint32_t)k) {
-        int bin = 0;
-        bool got = false;
+    const uint32_t cur = __hip_atomic_load(&sy->theta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t above = 0u, nt = 0u;
 #pragma unroll
-        for (int i = 0; i < kPer; ++i) {
-            run += cb[i];
-            if (!got && run >= (uint32_t)k) {
-                got = true;
-                bin = kPruneBins - 1 - (kPer * lane + i);
-            }
+    for (int i = 0; i < kPruneSlabs; ++i) {
+        if (i < ns && above < (uint32_t)k) {  // wave-uniform
+            const int b = prune_slab_bin(i, lane);
+            const uint32_t c = cb[i] + ((b == rb && prune_bin_live(b, thb)) ? 1u : 0u);
+            const uint32_t incl = wave_incl_scan(c);
+            if (prune_pick(above, incl, c, (uint32_t)k)) nt = prune_edge(b);
+            above += wave_last(incl);
         }
-        nt = prune_edge(bin);
-        if (nt > thb) __hip_atomic_fetch_max(&sy->theta, nt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     nt = wave_max_u32(nt);
+    if (lane == 0) {
+        __hip_atomic_fetch_add(&sy->hist[rb], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (nt > thb && nt > cur) __hip_atomic_fetch_max(&sy->theta, nt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    nt = nt > cur ? nt : cur;
     return nt > thb ? nt : thb;
 }
 
@@ -1284,7 +1294,8 @@ static __device__ __attribute__((noinline)) uint32_t prune_derive(ScanSync* sy, 
 //   <true>  the one-query launch (grid x = workgroups): every block is claimed per XCD group.
 //   <false> the batches (grid = workgroups x queries): a static stride, workgroup bx takes blocks
 //           pb, pb + nbx, ... of its query, pb = bx in XCD-contiguous order.
-// The pruning bound and its counters are <true>'s alone.
+// The pruning bound and its counters are one text for both: a batch workgroup prunes against its
+// query's sync[qy], whose theta warms over the ~32 blocks the workgroup runs in turn.
 // FILT: the context has a candidate filter (pf_filter.h, F; launch_post picks the instantiation): a
 // candidate whose header fails it is dropped like an excluded one, a block in which nobody passes
 // is left after its first barrier.  <XD, false> never reads F and is the code it was without it.
@@ -1356,17 +1367,18 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     uint64_t* lmk = reinterpret_cast<uint64_t*>(base + kLdsLmk);
     uint64_t* cpre = reinterpret_cast<uint64_t*>(base + kLdsCpre);
     double* need = reinterpret_cast<double*>(base + kLdsNeed);
-    // mode bit 16 (the one-query instantiation only): candidates that cannot reach the query's
-    // shared threshold theta (ScanSync, pf_prune.h) are dropped before their text work; bit 18
-    // leaves out the re-check at round ends; bit 17 counts (g_k5_prune).  Uniform over the launch.
+    // mode bit 16 (both hand-outs; a batch workgroup works on its query's own sync[qy]): candidates
+    // that cannot reach the query's shared threshold theta (ScanSync, pf_prune.h) are dropped before
+    // their text work; bit 18 leaves out the re-check at round ends; bit 17 counts (g_k5_prune).
+    // Uniform over the launch.  A sharded launch prunes against the theta of its own block range.
     // A dropped candidate's skip bit is set and its pending columns cleared; its owner thread
     // clears its hit mask in each round's slot phase, so it takes no hit slot, and the place phase
     // passes over the entries whose mask bit is gone: the compaction, the ordered dots, the terms
     // and its row of the owner sums vanish with them.  (The walk still ORs its bits: testing there
     // needs a bitmap in LDS, a barrier per block and a read per entry, and spilled registers.)
-    const bool prune = XD && (mode & kPostPrune) != 0u;
+    const bool prune = (mode & kPostPrune) != 0u;
     const bool prune_rnd = prune && !(mode & kPostPruneBlockOnly);
-    const bool pstats = XD && (mode & kPostPruneStats) != 0u;
+    const bool pstats = (mode & kPostPruneStats) != 0u;
     // The drop mechanics (pend cleared, the mask cleared in the slot phase, place passing over the
     // candidate) serve the filter as well: a filtered instantiation always has them, the batch and
     // k5_prune=0 included; the theta bound itself stays behind `prune`.
@@ -1548,11 +1560,12 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         K5T(1);
         if (prune && tid >= kPostThreads - 64) {
             // the block's need[u], by the last wave (wave 0 plans the rounds); read after the barrier
-            // below.  After a block in which the workgroup recorded (misc[5], set before that block's
-            // last barrier) the wave first derives theta anew.
+            // below.  After a block in which the workgroup recorded (misc[5], that block's record, folded
+            // before its last barrier) the wave takes the record, sends it and derives theta anew.
             thb = (uint32_t)__builtin_amdgcn_readfirstlane((int)thb);
-            if (misc[5] != 0u) {
-                thb = prune_derive(sync + qy, k, thb, lane);
+            const uint32_t rec = misc[5];
+            if (rec != 0u) {
+                thb = prune_derive(sync + qy, thb | (uint32_t)k, rec);
                 wave_sync();
                 if (lane == 0) misc[5] = 0u;
             }
@@ -1977,8 +1990,8 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         if (keys[1] < keys[0]) { const uint64_t x = keys[0]; keys[0] = keys[1]; keys[1] = x; }
 #pragma unroll
         for (int kk = 0; kk < kCandsPerThread; ++kk) topk_push(best, keys[kk], k, lane);
-        // 6. the block's best survivor goes into the query's score histogram
-        if (prune && prune_record(sync + qy, best, k, c0, c1, misc[4], lane) && lane == 0) misc[5] = 1u;
+        // 6. the block's best survivor becomes the workgroup's record (sent at the next block's start)
+        if (prune) prune_fold(&misc[5], best, k, c0, c1, misc[4], lane);
         K5T(12);
 #ifdef PF_K5_BLOCKLOG
         if (tid == 0) {
@@ -1991,6 +2004,17 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         }
 #endif
         next_block(false);
+    }
+    // The record of the workgroup's last block has no next block to send it: the deriving wave's
+    // first lane sends it here (the other workgroups of the query still derive from it) and waits
+    // for the add's return, so it has arrived before the tail's barrier, hence before this
+    // workgroup's ticket and before the query's last workgroup zeroes the ScanSync.
+    if (prune && tid == kPostThreads - 64) {
+        const uint32_t rec = misc[5];  // (folded before the last block's closing barrier)
+        if (rec != 0u) {
+            const uint32_t old = __hip_atomic_fetch_add(&sync[qy].hist[prune_bin(rec)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::"v"(old));
+        }
     }
 #ifdef PF_K5_TIMERS
     tacc[13] = clock64() - tstart;

@@ -35,6 +35,28 @@ PF_HD inline float prune_float(uint32_t bits) {
     return v.f;
 }
 
+// Deriving theta from the histogram, by one wave in slabs of 64 bins from the top: slab i is bins
+// top - 64 i .. top - 64 i - 63 and lane l takes bin top - 64 i - l, so one load instruction of the
+// wave covers two 128-B lines.  A derived theta is used only if it exceeds thb, the theta the block
+// began with (0, or a bin's lower edge), so only the bins above prune_bin(thb) can yield it: the
+// slabs that hold none of them are not read, and a lane at or below that bin counts 0.  With the
+// counts from above accumulated slab by slab, the answer is the one bin where they reach k; if the
+// live bins never reach k the block keeps thb.  (tests/cpp/derive_check.cpp runs these functions
+// lane by lane against a serial scan from the top bin.)
+constexpr int kPruneSlab = 64;
+constexpr int kPruneSlabs = (kPruneBins + kPruneSlab - 1) / kPruneSlab;  // 13
+// the bin of slab i's lane l (negative past the histogram's low end, in the last slab)
+PF_HD inline int prune_slab_bin(int slab, int lane) { return kPruneBins - 1 - (kPruneSlab * slab + lane); }
+// the bin counts for a block that began with thb: above thb's own bin (thb = 0: every bin)
+PF_HD inline bool prune_bin_live(int bin, uint32_t thb) { return bin > prune_bin(thb); }
+// slabs with at least one live bin: 0 (thb in the top bin) .. kPruneSlabs (thb = 0)
+PF_HD inline int prune_slabs(uint32_t thb) { return (kPruneBins - 1 - prune_bin(thb) + kPruneSlab - 1) / kPruneSlab; }
+// this lane's bin is the answer: `above` = the count of the slabs before, incl = the inclusive sum
+// over the slab's lanes up to this one, c = its own count
+PF_HD inline bool prune_pick(uint32_t above, uint32_t incl, uint32_t c, uint32_t k) {
+    return above + incl >= k && above + incl - c < k;
+}
+
 // need[u]: what the term sum of a candidate with u terms used must reach for its score to reach
 // theta (float bits; 0 = no threshold yet: 0, nothing is dropped).  nterms = 7 + T.
 //
