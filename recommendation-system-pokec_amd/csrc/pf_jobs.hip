@@ -25,6 +25,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "pf_block.h"
 #include "pf_device.h"
 #include "pf_jobs.h"
 
@@ -36,75 +37,6 @@ constexpr int kJobWaves = kJobThreads / 64;
 // (a hub's sequence of 40,000 elements is 40 chunks with 4 barriers each instead of 160)
 constexpr int kGatherThreads = 1024;
 constexpr int kGatherWaves = kGatherThreads / 64;
-
-// ---------------------------------------------------------------- block helpers
-// exclusive rank of `flag` among the block's threads and the block total (ballots + LDS)
-template <int NW = kJobWaves>
-__device__ __forceinline__ int block_rank(bool flag, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t m = __ballot(flag);
-    const int r = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const int x = wsum[w];
-        if (w < wave) before += x;
-        total += x;
-    }
-    __syncthreads();
-    return before + r;
-}
-
-// block_rank for two flags per thread whose items are ordered all-f0-items first (thread order),
-// then all f1-items: one LDS exchange (wsum holds 2 * NW words)
-template <int NW>
-__device__ __forceinline__ void block_rank2(bool f0, bool f1, int* wsum, int& r0, int& r1, int& t0, int& t1) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t m0 = __ballot(f0), m1 = __ballot(f1);
-    const uint64_t below = (1ull << lane) - 1ull;
-    r0 = __popcll(m0 & below);
-    r1 = __popcll(m1 & below);
-    if (lane == 0) {
-        wsum[wave] = __popcll(m0);
-        wsum[NW + wave] = __popcll(m1);
-    }
-    __syncthreads();
-    int b0 = 0, b1 = 0;
-    t0 = t1 = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const int x0 = wsum[w], x1 = wsum[NW + w];
-        if (w < wave) { b0 += x0; b1 += x1; }
-        t0 += x0;
-        t1 += x1;
-    }
-    __syncthreads();
-    r0 += b0;
-    r1 += t0 + b1;
-}
-
-// inclusive prefix of v over the block; total in `total`
-template <int NW = kJobWaves>
-__device__ __forceinline__ int block_scan_incl(int v, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-    x = (int)wave_incl_scan((uint32_t)x);
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const int t = wsum[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    __syncthreads();
-    return before + x;
-}
 
 // ---------------------------------------------------------------- adjacency under a view
 // Row of node x for job J: the job's own row, then the newest visible override, then the
