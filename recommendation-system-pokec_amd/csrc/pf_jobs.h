@@ -18,6 +18,21 @@ struct ImgJob {
     int64_t scr_off;
 };
 
+inline int pow2_lg(int64_t n) {
+    int lg = 4;
+    while (((int64_t)1 << lg) < n) ++lg;
+    return lg;
+}
+
+// K3's per-job hash table (DevJob::ht_lg; keys | pos | flags, 3 << lg int32 words): load <= 0.5 over
+// row(u) + {u}, the kept candidates and one more round of claims.  kGatherChunk is K3's round (2 x
+// pf_jobs.hip kGatherThreads): the last round claims up to this many table slots past the limit.
+// all: a kDjAll job, whose table holds the exclusions only.
+constexpr int64_t kGatherChunk = 2048;
+inline int gather_ht_lg(bool all, int64_t nf, int64_t cap) {
+    return all ? pow2_lg(2 * (nf + 1)) : pow2_lg(2 * (nf + 1 + cap + kGatherChunk));
+}
+
 // filt (fields == 0: none): the candidate filter of the batch's kDjAll jobs, tested on the tile headers of st
 hipError_t launch_gather(const DevJobsStore& g, const DevView& v, const DevJob* jobs, int njobs, const int32_t* pool,
                          const int64_t* pool64, int32_t* ht, int32_t* seq, int32_t* cand_slot, int32_t* cand_id,

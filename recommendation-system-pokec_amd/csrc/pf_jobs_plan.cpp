@@ -28,8 +28,6 @@ constexpr int64_t kChunkElems = 192ll << 20; // element workspace per chunk (x 1
 constexpr int64_t kChunkHt = 128ll << 20;    // gather hash tables per chunk (int32 words)
 constexpr size_t kPipeJobs = 1024;           // calls of this many jobs or more run as pipelined chunks
 constexpr uint32_t kStageLimitJobs = 48 * 1024;  // as pf_api.cpp kStageLimit (LDS-staged tables)
-constexpr int64_t kGatherChunk = 2048;          // K3's round (2 x pf_jobs.hip kGatherThreads): the last
-                                                // round claims up to this many table slots past the limit
 
 int32_t node_of(const pf_ctx* c, int32_t uid) {
     const auto& dn = c->jb.dense_node;  // uids of a dense range: one load (built at open)
@@ -59,12 +57,6 @@ int32_t ensure_node(pf_ctx* c, int32_t uid) {
 // candidates per pair block = the pair kernel's block (one pair per thread, pf_kernels.h)
 constexpr int64_t kPairSpan = kPairThreads;
 size_t a16z(size_t x) { return (x + 15) & ~(size_t)15; }
-
-int pow2_lg(int64_t n) {
-    int lg = 4;
-    while (((int64_t)1 << lg) < n) ++lg;
-    return lg;
-}
 
 // K6's image of profile idx (QConst | table | values), for the resident pool built at open and
 // for the per-call builds: its size and table offsets, its ImgJob, its build class and scratch.
@@ -611,7 +603,7 @@ void plan_job(pf_ctx* c, const Job& Jb, JP& p, bool raw) {
         if (!raw && Jb.all_candidates) {
             p.kind = kDjAll;
             p.cap = hc.n;
-            p.ht_lg = pow2_lg(2 * ((int64_t)p.F.size() + 1));
+            p.ht_lg = gather_ht_lg(true, (int64_t)p.F.size(), p.cap);
         } else {
             p.kind = raw ? (graph ? kDjRawGraph : kDjRawCollab) : kDjInterest;
             for (int32_t f : p.F) {
@@ -620,7 +612,7 @@ void plan_job(pf_ctx* c, const Job& Jb, JP& p, bool raw) {
                 else p.seqlen += std::max<int64_t>(rl, 0);
             }
             p.cap = std::min<int64_t>(L, p.seqlen);
-            p.ht_lg = pow2_lg(2 * ((int64_t)p.F.size() + 1 + p.cap + kGatherChunk));
+            p.ht_lg = gather_ht_lg(false, (int64_t)p.F.size(), p.cap);
         }
         p.elems = p.cap;
         p.ht_words = 3ll << p.ht_lg;
@@ -658,7 +650,7 @@ void plan_job(pf_ctx* c, const Job& Jb, JP& p, bool raw) {
         p.kind = kDjCollab;
         for (int32_t f : p.F) p.seqlen += std::max<int64_t>(rowlen(f), 0);
         p.cap = std::min<int64_t>(L, p.seqlen);
-        p.ht_lg = pow2_lg(2 * ((int64_t)p.F.size() + 1 + p.cap + kGatherChunk));
+        p.ht_lg = gather_ht_lg(false, (int64_t)p.F.size(), p.cap);
         p.elems = p.cap + (int64_t)p.fd.size() * (1 + p.cap);
         p.ht_words = 3ll << p.ht_lg;
     } else {
