@@ -427,7 +427,7 @@ typedef struct pf_layout_stats {
     int32_t n_tiles;
     int64_t post_bytes;       /* postings store: entries + norms + cells + headers (0 if absent) */
     int32_t scan_kernel;      /* kernel the next all-candidates scan uses: PF_SCAN_STREAM / PF_SCAN_POSTINGS */
-    int32_t pad;
+    int32_t resident_images;  /* 1 if every user's pair image was built at pf_open and kept (0: built per call) */
     int64_t shard_cands;      /* candidates in this context's shard (pf_set_shard) for that kernel */
     int64_t shard_entries;    /* their postings entries (tokens, clubs, friends; 0 without postings) */
 } pf_layout_stats;

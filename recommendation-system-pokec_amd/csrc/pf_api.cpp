@@ -646,7 +646,7 @@ int build_resident_post(pf_ctx* c) {
         auto it = hc.adj.find(hc.uid[i]);
         if (it != hc.adj.end()) adj[i] = &it->second;
         // users without a resident K1' image (outside the device tables' limits) get none either
-        off[i + 1] = J.img_lg[i] ? (int64_t)pf::post_part_bound(hc, (int32_t)i, (adj[i] ? adj[i]->size() : 0) + 1) : 0;
+        off[i + 1] = J.img.lg[i] ? (int64_t)pf::post_part_bound(hc, (int32_t)i, (adj[i] ? adj[i]->size() : 0) + 1) : 0;
     }, 1 << 14);
     off[0] = sizeof(pf::QConst);  // the first image's QConst-sized lead stays inside the pool
     for (int32_t i = 0; i < n; ++i) off[i + 1] += off[i];
@@ -1766,7 +1766,7 @@ int pf_layout(const pf_ctx* c, pf_layout_stats* o) {
     o->n_tiles = (int32_t)c->hs.tile_steps.size();
     o->post_bytes = c->post_bytes;
     o->scan_kernel = c->use_post() ? PF_SCAN_POSTINGS : PF_SCAN_STREAM;
-    o->pad = 0;
+    o->resident_images = c->jb.pimg ? 1 : 0;
     o->shard_cands = 0;
     o->shard_entries = 0;
     if (c->use_post()) {

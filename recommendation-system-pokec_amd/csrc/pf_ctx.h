@@ -104,9 +104,7 @@ struct JobsState {
     std::vector<int32_t> dense_node;             // uid -> node (-1 none) when the uids are dense
     std::vector<int32_t> g_uid, g_len;           // host mirrors (new uids from pf_set_adj append nodes)
     bool nodes_dirty = false;
-    std::vector<uint8_t> img_lg;                 // per idx: query-table log2 (0 = outside the device limits)
-    std::vector<int32_t> img_nset;               // per idx: clubs + friends words of the record
-    std::vector<uint32_t> img_rows;              // per idx: ImgJob::rows (its completion / age table rows)
+    ImgPlan img;                                 // per idx: the sizes of its query image (pf_jobs.h)
     std::vector<uint32_t> img_stamp;             // per idx: the layout pass that last gave it an image ...
     std::vector<int32_t> img_pos;                // ... and that image's index (no hash map per call)
     uint32_t img_gen = 0;

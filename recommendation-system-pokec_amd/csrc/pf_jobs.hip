@@ -394,7 +394,7 @@ template <bool PACKED, bool LDS>
 __global__ __launch_bounds__(kJobThreads) void qimage_kernel(DevStore st, DevJobsStore g, const ImgJob* __restrict__ ij,
                                                              uint8_t* __restrict__ pool, uint32_t* __restrict__ scratch,
                                                              int32_t* __restrict__ fail) {
-    __shared__ int s_fail, s_nuniq;
+    __shared__ int s_fail, s_nuniq, s_ones[2];
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const ImgJob I = ij[blockIdx.x];
     const int tid = threadIdx.x;
@@ -449,6 +449,7 @@ __global__ __launch_bounds__(kJobThreads) void qimage_kernel(DevStore st, DevJob
         q->excl_off = (uint32_t)((PACKED ? 1u : 3u) << I.lg);
         s_fail = 0;
         s_nuniq = 0;
+        if (!PACKED) s_ones[0] = s_ones[1] = 0;
     }
     // 2. the record's words once (tokens: their value entries, vi = token rank, recommender.cpp:74-85)
     const uint32_t len = record_words(h2, PACKED);
@@ -499,19 +500,29 @@ __global__ __launch_bounds__(kJobThreads) void qimage_kernel(DevStore st, DevJob
         items[nset + k] = e;  // tokens are distinct (column, tid) pairs
     }
     // 3. distinct clubs / friends: a thread owns a word it claims first in the set; items
-    //    [0, nuniq) are the sets, [nset, nset + ntok) the tokens
+    //    [0, nuniq) are the sets, [nset, nset + ntok) the tokens.  0 marks an empty slot.  Packed ids
+    //    are below 2^30 (kIdLimit): one set, key = id + 1 with the kind in bit 31.  Wide ids are any
+    //    uint32: the clubs take the set's lower half and the friends its upper half (ImgJob::dlg
+    //    counts a bit more for it), key = id + 1, and the one id whose key would be the empty mark,
+    //    0xFFFFFFFF, is claimed through a flag per kind instead.
     for (uint32_t j = tid; j < nset; j += kJobThreads) {
         const uint32_t w = rw[j];
         const bool club = j < nc;
         const uint32_t id = PACKED ? (club ? (w & ~kTagClub) : w) : w;
-        const uint32_t key = (id + 1u) | (club ? 0u : 0x80000000u);
-        uint32_t h = (node_hash((int32_t)key) >> 5) & dmask;
+        const uint32_t key = PACKED ? ((id + 1u) | (club ? 0u : 0x80000000u)) : id + 1u;
+        const uint32_t smask = PACKED ? dmask : dmask >> 1;
+        uint32_t* set = PACKED ? dset : dset + (club ? 0u : smask + 1u);
         bool won = false;
-        for (;;) {
-            const uint32_t old = atomicCAS(&dset[h], 0u, key);
-            if (old == 0u) { won = true; break; }
-            if (old == key) break;
-            h = (h + 1u) & dmask;
+        if (!PACKED && key == 0u) {
+            won = atomicExch(&s_ones[club ? 0 : 1], 1) == 0;
+        } else {
+            uint32_t h = (node_hash((int32_t)key) >> 5) & smask;
+            for (;;) {
+                const uint32_t old = atomicCAS(&set[h], 0u, key);
+                if (old == 0u) { won = true; break; }
+                if (old == key) break;
+                h = (h + 1u) & smask;
+            }
         }
         if (won) {
             uint64_t e;

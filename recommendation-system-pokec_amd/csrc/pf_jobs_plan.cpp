@@ -59,47 +59,8 @@ constexpr int64_t kPairSpan = kPairThreads;
 size_t a16z(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // K6's image of profile idx (QConst | table | values), for the resident pool built at open and
-// for the per-call builds: its size and table offsets, its ImgJob, its build class and scratch.
-// Meaningful for J.img_lg[idx] != 0 only (0: the tables are outside the device limits).
-const int kImgLge = lg_for(0);  // the exclusion table is empty (the pair images carry no exclusions)
-int64_t img_ntok(const pf_ctx* c, int32_t idx) {
-    return c->hc.tok_off[(size_t)(idx + 1) * c->hc.T] - c->hc.tok_off[(size_t)idx * c->hc.T];
-}
-size_t img_nkeys(const pf_ctx* c, int32_t idx) {  // 8-B entries: the table(s), then the exclusion table
-    return ((size_t)(c->hs.packed ? 1u : 3u) << c->jb.img_lg[idx]) + ((size_t)1 << kImgLge);
-}
-constexpr uint32_t kImgKeysOff = (uint32_t)sizeof(QConst);  // byte offsets from the image's start
-uint32_t img_vals_off(const pf_ctx* c, int32_t idx) { return (uint32_t)a16z(sizeof(QConst) + img_nkeys(c, idx) * 8); }
-size_t img_bytes(const pf_ctx* c, int32_t idx) {
-    return img_vals_off(c, idx) + a16z((size_t)img_ntok(c, idx) * sizeof(QVal));
-}
-int img_dlg(const pf_ctx* c, int32_t idx) { return pow2_lg(2 * (int64_t)c->jb.img_nset[idx] + 2); }
-ImgJob img_job(const pf_ctx* c, int32_t idx, uint32_t pool_off) {  // the image at byte pool_off of its pool
-    ImgJob m{};
-    m.idx = idx;
-    m.lg = c->jb.img_lg[idx];
-    m.lge = kImgLge;
-    m.dlg = img_dlg(c, idx);
-    m.rows = c->jb.img_rows[idx];
-    m.const_off = pool_off;
-    m.keys_off = pool_off + kImgKeysOff;
-    m.vals_off = pool_off + img_vals_off(c, idx);
-    return m;
-}
-// K6 builds in three launches: 0 small LDS builds (<= kImgLdsSmall, many workgroups per CU),
-// 1 large LDS builds (<= kImgLds), 2 hub users in global memory
-int img_build_class(const pf_ctx* c, int32_t idx) {
-    const int lg = c->jb.img_lg[idx];
-    const uint32_t need = lg ? qimage_lds(lg, kImgLge, img_dlg(c, idx), (uint32_t)(c->jb.img_nset[idx] + img_ntok(c, idx)),
-                                          c->hs.packed)
-                             : 0u;
-    return need == 0 ? 2 : (need <= kImgLdsSmall ? 0 : 1);
-}
-// scratch words of a class-2 build: set + u64 items + the table's u64 copy (the SoA transform)
-int64_t img_scratch_words(const pf_ctx* c, int32_t idx) {
-    return ((int64_t)1 << img_dlg(c, idx)) + 2 * ((int64_t)c->jb.img_nset[idx] + img_ntok(c, idx)) +
-           2 * (int64_t)img_nkeys(c, idx);
-}
+// for the per-call builds: its size and table offsets, its ImgJob, its build class and scratch are
+// pf_jobs.h's img_* over J.img (the plan of every user's image, build_img_plan).
 
 // Every user's query image (K6's layout: QConst | table | values) built once at open into one
 // resident pool, when it fits a third of the free HBM (at 1.63M users ~10^4 B each: a few
@@ -114,7 +75,7 @@ int build_resident_images(pf_ctx* c) {
     const int32_t n = c->hc.n;
     if (debug_long("resident_images", 1) == 0 || n == 0) return PF_OK;
     std::vector<int64_t> off((size_t)n + 1, 0);
-    par_jobs((size_t)n, [&](size_t i) { off[i + 1] = J.img_lg[i] ? (int64_t)img_bytes(c, (int32_t)i) : 0; }, 1 << 14);
+    par_jobs((size_t)n, [&](size_t i) { off[i + 1] = J.img.lg[i] ? (int64_t)img_bytes(J.img, (int32_t)i) : 0; }, 1 << 14);
     for (int32_t i = 0; i < n; ++i) off[i + 1] += off[i];
     const size_t total = (size_t)off[n];
     size_t freeb = 0, totb = 0;
@@ -133,31 +94,17 @@ int build_resident_images(pf_ctx* c) {
         while (i1 < n && (size_t)(off[i1 + 1] - off[i0]) <= kBatchBytes && i1 - i0 < (1 << 18)) ++i1;
         std::vector<ImgJob> ij;
         ij.reserve((size_t)(i1 - i0));
-        std::vector<uint8_t> cls;
-        cls.reserve((size_t)(i1 - i0));
         for (int32_t idx = i0; idx < i1; ++idx) {
-            if (!J.img_lg[idx]) continue;
-            cls.push_back((uint8_t)img_build_class(c, idx));
-            ij.push_back(img_job(c, idx, (uint32_t)(off[idx] - off[i0])));
+            if (!J.img.lg[idx]) continue;
+            ij.push_back(img_job(J.img, idx, (uint32_t)(off[idx] - off[i0])));
         }
-        std::vector<ImgJob> ord;
-        ord.reserve(ij.size());
-        int nc[3] = {0, 0, 0};
-        int64_t scr = 0;
-        for (int k = 0; k < 3; ++k)
-            for (size_t x = 0; x < ij.size(); ++x)
-                if (cls[x] == k) {
-                    ImgJob m = ij[x];
-                    m.scr_off = scr;
-                    if (k == 2) scr += img_scratch_words(c, m.idx);
-                    ord.push_back(m);
-                    ++nc[k];
-                }
-        if (!ord.empty()) {
-            HIPCHK(c, upload(c, d_ij, ord));
-            HIPCHK(c, d_scr.ensure((size_t)std::max<int64_t>(scr, 1) * 4));
-            HIPCHK(c, launch_qimages(c->ds, J.js, d_ij.as<ImgJob>(), nc[0], nc[1], nc[2], J.d_pimg.as<uint8_t>() + off[i0],
-                                     d_scr.as<uint32_t>(), d_fail.as<int32_t>(), c->stream));
+        ImgBatch ord;
+        img_batch(J.img, ij, ord);
+        if (!ord.ij.empty()) {
+            HIPCHK(c, upload(c, d_ij, ord.ij));
+            HIPCHK(c, d_scr.ensure((size_t)std::max<int64_t>(ord.scr, 1) * 4));
+            HIPCHK(c, launch_qimages(c->ds, J.js, d_ij.as<ImgJob>(), ord.nc[0], ord.nc[1], ord.nc[2],
+                                     J.d_pimg.as<uint8_t>() + off[i0], d_scr.as<uint32_t>(), d_fail.as<int32_t>(), c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));  // d_ij / d_scr are reused by the next batch
         }
         i0 = i1;
@@ -182,44 +129,15 @@ int jobs_open(pf_ctx* c) {
     auto& J = c->jb;
     const HostCorpus& hc = c->hc;
     const HostStore& hs = c->hs;
-    const int32_t n = hc.n, T = hc.T;
+    const int32_t n = hc.n;
     const bool packed = hs.packed;
     J.ok = false;
     StageClock sc;
     // image-builder tables: QConst template, region rows, completion / age rows (glibc exp)
-    QConst tmpl;
-    qconst_template(hc, packed, tmpl);
-    std::vector<QConst> tv(1, tmpl);
-    std::vector<double> sreg(4 * 16, 0.0);
-    for (int a = 1; a <= 3; ++a) {
-        double r[4][4];
-        qconst_sig_reg(hc, a, r);
-        for (int b = 0; b < 4; ++b)
-            for (int m = 0; m < 4; ++m) sreg[a * 16 + b * 4 + m] = r[b][m];
-    }
-    auto ratio_rows = [&](const std::vector<int32_t>& v, int slot, std::vector<int32_t>& vals, std::vector<double>& rows) {
-        for (int32_t x : v) if (x > 0) vals.push_back(x);
-        std::sort(vals.begin(), vals.end());
-        vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
-        rows.assign(vals.size() * (kValTab + 1), 0.0);
-        par_jobs(vals.size(), [&](size_t i) { qconst_ratio_row(hc, slot, vals[i], &rows[i * (kValTab + 1)]); }, 16);
-    };
-    std::vector<int32_t> comp_vals, age_vals;
-    std::vector<double> comp_rows, age_rows;
-    ratio_rows(hc.comp, PF_F_COMPLETION, comp_vals, comp_rows);
-    ratio_rows(hc.age, PF_F_AGE, age_vals, age_rows);
-    // idf per column by tid rank (pf_store.h: the engine's token ids are column ranks), one dense
-    // table for every column with an idf map
-    std::vector<int64_t> dense_off(T, -1);
-    std::vector<int32_t> dense_len(T, 0);
-    std::vector<float> dense;
-    for (int t = 0; t < T; ++t) {
-        if (!hc.has_idf[t]) continue;
-        dense_off[t] = (int64_t)dense.size();
-        dense_len[t] = (int32_t)hc.idf[t].size();
-        dense.insert(dense.end(), hc.idf[t].begin(), hc.idf[t].end());
-    }
-    if (dense.empty()) dense.push_back(1.0f);
+    // and the idf per column by tid rank (pf_jobs.h ImgTables)
+    ImgTables it;
+    build_img_tables(hc, packed, it);
+    std::vector<QConst> tv(1, it.tmpl);
     sc.lap("image-builder tables");
     // graph: nodes 0..n-1 = profiles (idx), then adj_list uids without a profile
     J.xnode.clear();
@@ -314,46 +232,20 @@ int jobs_open(pf_ctx* c) {
         club_dense[k] = (int32_t)(std::lower_bound(club_id.begin(), club_id.end(), (int32_t)hc.clubs[k]) - club_id.begin());
     }, 1 << 16);
     sc.lap("club indices");
-    // per profile: query-table size (pf_store.cpp build_query) and its raw set words
-    J.img_lg.assign(n, 0);
-    J.img_nset.assign(n, 0);
-    par_jobs((size_t)n, [&](size_t i) {
-        std::vector<uint32_t> v(hc.clubs.begin() + hc.club_off[i], hc.clubs.begin() + hc.club_off[i + 1]);
-        std::sort(v.begin(), v.end());
-        const size_t dc = (size_t)(std::unique(v.begin(), v.end()) - v.begin());
-        v.assign(hc.friends.begin() + hc.friend_off[i], hc.friends.begin() + hc.friend_off[i + 1]);
-        std::sort(v.begin(), v.end());
-        const size_t df = (size_t)(std::unique(v.begin(), v.end()) - v.begin());
-        const size_t nt = (size_t)(hc.tok_off[(i + 1) * (size_t)T] - hc.tok_off[i * (size_t)T]);
-        const int lg = packed ? lg_for(dc + df + nt) : std::max({lg_for(dc), lg_for(df), lg_for(nt)});
-        const bool ok = lg <= kMaxHashLog2 && nt < (packed ? (1u << kTidBits) : (1u << 22));
-        J.img_lg[i] = ok ? (uint8_t)lg : 0;
-        J.img_nset[i] = (int32_t)((hc.club_off[i + 1] - hc.club_off[i]) + (hc.friend_off[i + 1] - hc.friend_off[i]));
-    }, 4096);
-    // per profile: its completion / age rows in the image-builder tables (ImgJob::rows)
-    // (0xFFFFFFFF: more than 65534 distinct values, K6 looks the rows up itself)
-    const bool rows16 = comp_vals.size() < 0xFFFFu && age_vals.size() < 0xFFFFu;
-    J.img_rows.assign(n, rows16 ? 0u : 0xFFFFFFFFu);
-    if (rows16) par_jobs((size_t)n, [&](size_t i) {
-        auto row = [](const std::vector<int32_t>& vals, int32_t v) -> uint32_t {
-            if (v <= 0) return 0u;
-            auto it = std::lower_bound(vals.begin(), vals.end(), v);
-            return (it != vals.end() && *it == v) ? (uint32_t)(it - vals.begin()) + 1u : 0u;
-        };
-        J.img_rows[i] = row(comp_vals, hc.comp[i]) | (row(age_vals, hc.age[i]) << 16);
-    }, 1 << 14);
+    // per profile: the sizes of its query image and its completion / age rows (pf_jobs.h ImgPlan)
+    build_img_plan(hc, hs, it, J.img);
     std::vector<int32_t> slot_of(hs.slot_of_idx.begin(), hs.slot_of_idx.end());
     sc.lap("image sizes");
     hipError_t e = hipSuccess;
     if (e == hipSuccess) e = upload(c, J.d_tmpl, tv);
-    if (e == hipSuccess) e = upload(c, J.d_sigreg, sreg);
-    if (e == hipSuccess) e = upload(c, J.d_comp_vals, comp_vals);
-    if (e == hipSuccess) e = upload(c, J.d_comp_rows, comp_rows);
-    if (e == hipSuccess) e = upload(c, J.d_age_vals, age_vals);
-    if (e == hipSuccess) e = upload(c, J.d_age_rows, age_rows);
-    if (e == hipSuccess) e = upload(c, J.d_idf_doff, dense_off);
-    if (e == hipSuccess) e = upload(c, J.d_idf_dlen, dense_len);
-    if (e == hipSuccess) e = upload(c, J.d_idf_dense, dense);
+    if (e == hipSuccess) e = upload(c, J.d_sigreg, it.sig_reg);
+    if (e == hipSuccess) e = upload(c, J.d_comp_vals, it.comp_vals);
+    if (e == hipSuccess) e = upload(c, J.d_comp_rows, it.comp_rows);
+    if (e == hipSuccess) e = upload(c, J.d_age_vals, it.age_vals);
+    if (e == hipSuccess) e = upload(c, J.d_age_rows, it.age_rows);
+    if (e == hipSuccess) e = upload(c, J.d_idf_doff, it.dense_off);
+    if (e == hipSuccess) e = upload(c, J.d_idf_dlen, it.dense_len);
+    if (e == hipSuccess) e = upload(c, J.d_idf_dense, it.dense);
     if (e == hipSuccess) e = upload(c, J.d_slot_of, slot_of);
     if (e == hipSuccess) e = upload(c, J.d_goff, g_off);
     if (e == hipSuccess) e = upload(c, J.d_glen, J.g_len);
@@ -372,8 +264,8 @@ int jobs_open(pf_ctx* c) {
     g.comp_rows = J.d_comp_rows.as<double>();
     g.age_vals = J.d_age_vals.as<int32_t>();
     g.age_rows = J.d_age_rows.as<double>();
-    g.n_comp = (int32_t)comp_vals.size();
-    g.n_age = (int32_t)age_vals.size();
+    g.n_comp = (int32_t)it.comp_vals.size();
+    g.n_age = (int32_t)it.age_vals.size();
     g.idf_dense_off = J.d_idf_doff.as<int64_t>();
     g.idf_dense_len = J.d_idf_dlen.as<int32_t>();
     g.idf_dense = J.d_idf_dense.as<float>();
@@ -837,7 +729,7 @@ int plan_images(pf_ctx* c, ChunkPlan& cp) {
         std::vector<int32_t> order(n), pos(n);
         std::vector<uint8_t> cls(n);
         int nc[3] = {0, 0, 0};
-        for (size_t k = 0; k < n; ++k) ++nc[cls[k] = (uint8_t)img_build_class(c, cp.img_idx[k])];
+        for (size_t k = 0; k < n; ++k) ++nc[cls[k] = (uint8_t)img_build_class(J.img, cp.img_idx[k])];
         cp.n_small = nc[0];
         cp.n_lds = nc[0] + nc[1];
         int at[3] = {0, cp.n_small, cp.n_lds};
@@ -850,22 +742,22 @@ int plan_images(pf_ctx* c, ChunkPlan& cp) {
     cp.refs.resize(n);
     for (size_t k = 0; k < n; ++k) {
         const int32_t idx = cp.img_idx[k];
-        if (J.img_lg[idx] == 0) return c->fail(PF_EUNSUPP, "query hash table too large");
+        if (J.img.lg[idx] == 0) return c->fail(PF_EUNSUPP, "query hash table too large");
         QImageRef& r = cp.refs[k];
         r.keys_off = kImgKeysOff;
-        r.vals_off = img_vals_off(c, idx);
+        r.vals_off = img_vals_off(J.img, idx);
         if (resident) {
             r.const_off = (uint32_t)(J.pimg_off[idx] >> 4);
         } else {
             ImgJob& m = cp.ij[k];
-            m = img_job(c, idx, (uint32_t)cp.ipool);
+            m = img_job(J.img, idx, (uint32_t)cp.ipool);
             r.const_off = (uint32_t)(cp.ipool >> 4);
-            cp.ipool += img_bytes(c, idx);
+            cp.ipool += img_bytes(J.img, idx);
             if (cp.ipool >= (size_t)UINT32_MAX) return c->fail(PF_EUNSUPP, "query images of one batch exceed 4 GB");
             m.scr_off = cp.scr;
-            if ((int)k >= cp.n_lds) cp.scr += img_scratch_words(c, idx);
+            if ((int)k >= cp.n_lds) cp.scr += img_scratch_words(J.img, idx);
         }
-        const size_t kv = img_nkeys(c, idx) * 8 + (size_t)img_ntok(c, idx) * sizeof(QVal);
+        const size_t kv = img_nkeys(J.img, idx) * 8 + (size_t)J.img.ntok[idx] * sizeof(QVal);
         r.lds_bytes = kv <= kStageLimitJobs ? (uint32_t)kv : 0u;
     }
     // The pair blocks in three launches by their image: LDS-staged images whose block fits two
@@ -1081,7 +973,7 @@ int enqueue_chunk(pf_ctx* c, const ChunkPlan& cp, const PlanLayout& L, JobsState
         HIPCHK(c, launch_pair_stats(c->ds, d_blk, (int)cp.nblk, slots, acc, st.sp));
         for (const PairGen& g : cp.gens)  // the staged image per pair block (QConst + tables)
             for (int f = 0; f < g.nf; ++f)
-                J.st_img_bytes += (int64_t)g.nch * (int64_t)img_bytes(c, cp.img_idx[cp.gp2[g.fl + f].x]);
+                J.st_img_bytes += (int64_t)g.nch * (int64_t)img_bytes(J.img, cp.img_idx[cp.gp2[g.fl + f].x]);
     }
     hl.lap(kHpCollab);  // images, gathers, pairs launched
     HIPCHK(c, hipEventRecord(W.ev_pairs, st.sp));

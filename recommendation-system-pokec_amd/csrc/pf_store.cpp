@@ -6,6 +6,7 @@
 
 #include "pf_debug.h"
 #include "pf_filter.h"
+#include "pf_jobs.h"
 
 #include <algorithm>
 #include <atomic>
@@ -510,6 +511,79 @@ void qconst_ratio_row(const HostCorpus& hc, int slot, int a, double* out) {
     out[0] = 0.0;
     for (int v = 1; v <= kValTab; ++v)
         out[v] = a > 0 ? term(hc, slot, (double)std::min(a, v) / (double)std::max(a, v)) : 0.0;
+}
+
+// K6's inputs (pf_jobs.h): the QConst parts above as tables, and the sizes of every user's image
+void build_img_tables(const HostCorpus& hc, bool packed, ImgTables& t) {
+    const int T = hc.T;
+    qconst_template(hc, packed, t.tmpl);
+    t.sig_reg.assign(4 * 16, 0.0);
+    for (int a = 1; a <= 3; ++a) {
+        double r[4][4];
+        qconst_sig_reg(hc, a, r);
+        for (int b = 0; b < 4; ++b)
+            for (int m = 0; m < 4; ++m) t.sig_reg[a * 16 + b * 4 + m] = r[b][m];
+    }
+    auto ratio_rows = [&](const std::vector<int32_t>& v, int slot, std::vector<int32_t>& vals, std::vector<double>& rows) {
+        vals.clear();
+        for (int32_t x : v) if (x > 0) vals.push_back(x);
+        std::sort(vals.begin(), vals.end());
+        vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
+        rows.assign(vals.size() * (kValTab + 1), 0.0);
+        par_dyn((int64_t)vals.size(), 16, [&](int64_t lo, int64_t hi) {
+            for (int64_t i = lo; i < hi; ++i) qconst_ratio_row(hc, slot, vals[i], &rows[i * (kValTab + 1)]);
+        });
+    };
+    ratio_rows(hc.comp, PF_F_COMPLETION, t.comp_vals, t.comp_rows);
+    ratio_rows(hc.age, PF_F_AGE, t.age_vals, t.age_rows);
+    t.dense_off.assign(T, -1);
+    t.dense_len.assign(T, 0);
+    t.dense.clear();
+    for (int c = 0; c < T; ++c) {
+        if (!hc.has_idf[c]) continue;
+        t.dense_off[c] = (int64_t)t.dense.size();
+        t.dense_len[c] = (int32_t)hc.idf[c].size();
+        t.dense.insert(t.dense.end(), hc.idf[c].begin(), hc.idf[c].end());
+    }
+    if (t.dense.empty()) t.dense.push_back(1.0f);
+}
+
+void build_img_plan(const HostCorpus& hc, const HostStore& hs, const ImgTables& t, ImgPlan& p) {
+    const int32_t n = hc.n, T = hc.T;
+    const bool packed = hs.packed;
+    p.packed = packed;
+    p.lge = lg_for(0);
+    // per profile: query-table size (build_query) and its raw set words
+    p.lg.assign(n, 0);
+    p.nset.assign(n, 0);
+    p.ntok.assign(n, 0);
+    // its completion / age rows in the image-builder tables (ImgJob::rows)
+    // (0xFFFFFFFF: more than 65534 distinct values, K6 looks the rows up itself)
+    const bool rows16 = t.comp_vals.size() < 0xFFFFu && t.age_vals.size() < 0xFFFFu;
+    p.rows.assign(n, rows16 ? 0u : 0xFFFFFFFFu);
+    auto row = [](const std::vector<int32_t>& vals, int32_t v) -> uint32_t {
+        if (v <= 0) return 0u;
+        auto it = std::lower_bound(vals.begin(), vals.end(), v);
+        return (it != vals.end() && *it == v) ? (uint32_t)(it - vals.begin()) + 1u : 0u;
+    };
+    par_dyn(n, 4096, [&](int64_t lo, int64_t hi) {
+        std::vector<uint32_t> v;
+        for (int64_t i = lo; i < hi; ++i) {
+            v.assign(hc.clubs.begin() + hc.club_off[i], hc.clubs.begin() + hc.club_off[i + 1]);
+            std::sort(v.begin(), v.end());
+            const size_t dc = (size_t)(std::unique(v.begin(), v.end()) - v.begin());
+            v.assign(hc.friends.begin() + hc.friend_off[i], hc.friends.begin() + hc.friend_off[i + 1]);
+            std::sort(v.begin(), v.end());
+            const size_t df = (size_t)(std::unique(v.begin(), v.end()) - v.begin());
+            const size_t nt = (size_t)(hc.tok_off[(size_t)(i + 1) * T] - hc.tok_off[(size_t)i * T]);
+            const int lg = packed ? lg_for(dc + df + nt) : std::max({lg_for(dc), lg_for(df), lg_for(nt)});
+            const bool ok = lg <= kMaxHashLog2 && nt < (packed ? (1u << kTidBits) : (1u << 22));
+            p.lg[i] = ok ? (uint8_t)lg : 0;
+            p.nset[i] = (int32_t)((hc.club_off[i + 1] - hc.club_off[i]) + (hc.friend_off[i + 1] - hc.friend_off[i]));
+            p.ntok[i] = (int32_t)nt;
+            if (rows16) p.rows[i] = row(t.comp_vals, hc.comp[i]) | (row(t.age_vals, hc.age[i]) << 16);
+        }
+    });
 }
 
 ProfileView view_of(const HostCorpus& hc, int32_t i) {

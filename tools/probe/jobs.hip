@@ -8,7 +8,7 @@
 //      summation order, and the fused top-k hand-off (and K8 for a job with topk > 64);
 //   D  K7 clubs_kernel: every club's sum in the stream order, acc left zero;
 //   E  K8 topk_kernel.
-// K6 (qimage_kernel) and pair_stats_kernel are not here.  Prints one summary line per part and OK;
+// K6 (qimage_kernel) has a probe of its own (qimage.hip); pair_stats_kernel is not here.  Prints one summary line per part and OK;
 // at the first HIP error or mismatch it prints FAIL ... and exits 1 without another launch.
 #include <hip/hip_runtime.h>
 
