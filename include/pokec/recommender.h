@@ -227,6 +227,9 @@ inline void release_engines() {
     });
 }
 
+// How a group query combines a candidate's scores against the seeds (pokec_fas.h PF_GROUP_*)
+enum class GroupAgg { Mean = PF_GROUP_MEAN, Min = PF_GROUP_MIN, Max = PF_GROUP_MAX };
+
 template <class Profile>
 class BasicRecommender {
 public:
@@ -374,6 +377,45 @@ public:
     ScoreTerms profile_similarity_terms_adhoc(const Profile& A, const Profile& B, const FieldSelect& select) const {
         const pf_field_select s = select.c_form();
         return adhoc_terms_(A, B.user_id, &s);
+    }
+
+    // Group query (pokec_fas.h pf_group_query): the top-k profiles of the map most similar to the
+    // seed users as a group, by the mean, the minimum ("similar to every seed") or the maximum
+    // ("similar to any seed") of the per-seed scores.  Seeds not of the map are dropped; the seeds
+    // and `exclude` are never returned; exclude_adj also drops every seed's adj_list row, as the
+    // caller's adj_list holds it now.  topk above 64 is refused (an empty list, last_error says why).
+    Ranked recommend_for_group(const std::vector<int>& seeds, int topk, GroupAgg agg = GroupAgg::Mean,
+                               bool exclude_adj = false, const std::vector<int>& exclude = {}) const {
+        Ranked out;
+        if (!profiles || topk <= 0 || seeds.empty()) return out;
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return out;
+        std::lock_guard<std::mutex> g(e->mu);
+        if (exclude_adj && adj_list)
+            for (int s : seeds)
+                if (sync_row_(*e, s) != PF_OK) return fail_(e->ctx, out);
+        const std::vector<int32_t> sd(seeds.begin(), seeds.end()), ex(exclude.begin(), exclude.end());
+        const pf_group_query q{sd.data(), (int32_t)sd.size(), (int32_t)agg, exclude_adj ? PF_GROUP_EXCLUDE_ADJ : 0u,
+                               ex.empty() ? nullptr : ex.data(), (int32_t)ex.size()};
+        std::vector<int32_t> ids((size_t)topk);
+        std::vector<float> sc((size_t)topk);
+        int32_t n = 0;
+        if (pf_recommend_group(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n) != PF_OK) return fail_(e->ctx, out);
+        for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
+        return out;
+    }
+    // The group's aggregate score of B, a profile of the map (NaN when B or every seed is not): how
+    // well B fits the group.  No exclusion applies: a seed is scored like anyone else.
+    float group_similarity(const std::vector<int>& seeds, const Profile& B, GroupAgg agg = GroupAgg::Mean) const {
+        float out = NAN;
+        if (!profiles || seeds.empty()) return out;
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return out;
+        std::lock_guard<std::mutex> g(e->mu);
+        const std::vector<int32_t> sd(seeds.begin(), seeds.end());
+        const pf_group_query q{sd.data(), (int32_t)sd.size(), (int32_t)agg, 0u, nullptr, 0};
+        const int32_t b = B.user_id;
+        return pf_group_scores(e->ctx, &q, &b, 1, nullptr, &out) == PF_OK ? out : NAN;
     }
 
     // Push adj_list row `uid` to the engine now.  Never needed for correctness (every call

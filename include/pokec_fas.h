@@ -385,6 +385,73 @@ int pf_recommend_interest_profile_terms(pf_ctx* ctx, const pf_query_profile* q, 
                                         pf_pair_terms_head* head, double* terms);
 
 /*
+ * Group query: "who is similar to THESE people" (the members of a club, a user's friends, a seed
+ * audience).  Every candidate is scored against every seed and the scores are combined per candidate.
+ *   Seeds        Stored users.  Unknown uids are dropped; of a repeated uid the first occurrence
+ *                counts; G is the number that remain, in the caller's order.  G = 0 gives count 0 and
+ *                PF_OK, as an unknown query uid does.
+ *   Per seed     s_g(B) is the float profile_similarity(seed_g, B) of the reference, bit for bit what
+ *                the all-candidates scan and the pair kernel compute, under the context's field
+ *                selection (pf_set_scan_select) exactly as PF_MODE_ALL.
+ *   Aggregate    PF_GROUP_MEAN: double acc = 0; acc += (double)s_g for g = 0 .. G-1 in that order;
+ *                score = (float)(acc / (double)G).  PF_GROUP_MIN / PF_GROUP_MAX: m = s_0, then for
+ *                g = 1 .. G-1 in order m = s_g < m ? s_g : m (MAX: s_g > m).  With G = 1 all three
+ *                return s_0 itself.
+ *   Candidates   A stored user of the context's shard (pf_set_shard) that passes the context's
+ *                candidate filter, is not a seed, is not in exclude_uid and, under
+ *                PF_GROUP_EXCLUDE_ADJ, is in no seed's current adj_list row (pf_set_adj is honoured).
+ *                With the flag off a candidate in adj[seed] is scored against that seed like anyone
+ *                else.  Results are ranked (score desc, uid asc).
+ *   State        The filter and the selection travel by value with the launches; nothing in the
+ *                context changes, and the by-uid calls before and after are identical.
+ *   Refusals     PF_EINVAL: n_seeds > PF_GROUP_MAX_SEEDS, a negative count, an unknown agg, unknown
+ *                flag bits, a NULL array with a positive count.  PF_EUNSUPP: topk > 64; an exclusion
+ *                union (the kept seeds + the known uids of exclude_uid + under PF_GROUP_EXCLUDE_ADJ
+ *                the seeds' adj_list rows, distinct) of more than PF_GROUP_MAX_EXCLUDE uids: the
+ *                union rides in one query image's exclusion table, a cuckoo table of at most 2^16
+ *                slots filled to 0.4.  pf_last_error names the reason.
+ *   Groups       The ng groups are independent and run one after the other.
+ * The scan (fas_group_kernel) packs the seeds' query images, in order, into
+ * passes of as many images as fit one workgroup's LDS budget and reads the shard's record stream
+ * once per pass; pf_group_plan_of reports the packing.
+ */
+#define PF_GROUP_MEAN 0
+#define PF_GROUP_MIN  1      /* similar to every seed  */
+#define PF_GROUP_MAX  2      /* similar to any seed    */
+#define PF_GROUP_EXCLUDE_ADJ 1u   /* flags: also drop adj[s] of every seed s */
+#define PF_GROUP_MAX_SEEDS 1024
+#define PF_GROUP_MAX_EXCLUDE 26214  /* floor(0.4 * 2^16) */
+
+typedef struct pf_group_query {
+    const int32_t* seed_uid;    int32_t n_seeds;
+    int32_t  agg;               uint32_t flags;
+    const int32_t* exclude_uid; int32_t n_exclude;  /* never returned; unknown uids ignored */
+} pf_group_query;
+
+/* The top-k of each of the ng groups; outputs as pf_recommend_interest (row i of out_uid /
+ * out_score has topk entries, out_count[i] of them written).  ng = 0 returns PF_OK. */
+int pf_recommend_group(pf_ctx* ctx, const pf_group_query* g, int32_t ng, int32_t topk,
+                       int32_t* out_uid, float* out_score, int32_t* out_count);
+/* The aggregate of one group for n listed users (NaN for an unknown b_uid, and for every user when
+ * G = 0), under `select` (NULL = none, as pf_fas_pairs_select; the context's selection plays no
+ * part).  No filter and no exclusion applies: a seed is scored like anyone else.  Computed by the
+ * pair kernel (G x n pairs, in chunks) and aggregated on the host: a second route to the scan's
+ * numbers ("how well does this user fit the club"). */
+int pf_group_scores(pf_ctx* ctx, const pf_group_query* g, const int32_t* b_uid, int64_t n,
+                    const pf_field_select* select, float* out);
+/* What pf_recommend_group would launch for the group: the G kept seeds, the passes over the record
+ * stream, the images probed in global memory (tables above the LDS staging limit), and the bytes
+ * read: n_passes x the shard's record stream and 48-B headers (pf_scan_bytes' K1 figure). */
+typedef struct pf_group_plan { int32_t n_seeds, n_passes, n_global, pad; int64_t stream_bytes; } pf_group_plan;
+int pf_group_plan_of(pf_ctx* ctx, const pf_group_query* g, pf_group_plan* out);
+/* LDS bytes image i of the group's G kept seeds takes in a pass (out[G]: constants + staged
+ * tables, the constants alone for an image probed in global memory), then out[G] = the bytes a
+ * pass takes besides its images and out[G + 1] = the LDS budget of a pass; cap >= G + 2 entries.
+ * A pass is the longest prefix of the remaining seeds whose sum fits the budget (at least one,
+ * at most PF_DEBUG group_tile=N). */
+int pf_group_image_lds(pf_ctx* ctx, const pf_group_query* g, int32_t* out, int32_t cap);
+
+/*
  * Device-resident all-candidates scan for the multi-GPU bench: scores the
  * queries against this context's shard and writes, per query, `topk` packed
  * 64-bit keys to DEVICE memory d_keys[nq*topk] on `stream` (a hipStream_t).

@@ -87,6 +87,39 @@ def match_line(body):
     return " ".join(words)
 
 
+def group_line(body):
+    """The api_cli "GROUP ..." line of a POST /api/group body {"seeds": [...], "topk": 20, "agg":
+    "mean", "exclude": [...], "exclude_adj": false}; ValueError on a field of the wrong shape."""
+    if not isinstance(body, dict):
+        raise ValueError("the body must be a JSON object")
+    unknown = set(body) - {"seeds", "topk", "agg", "exclude", "exclude_adj"}
+    if unknown:
+        raise ValueError("unknown field: " + sorted(unknown)[0])
+
+    def uids(name, v):
+        if not isinstance(v, (list, tuple)) or any(isinstance(x, bool) or not isinstance(x, int) or x < 0 for x in v):
+            raise ValueError(name + " must be a list of non-negative integers")
+        return [str(x) for x in v]
+
+    seeds = uids("seeds", body.get("seeds"))
+    if not seeds:
+        raise ValueError("seeds must name at least one user")
+    agg = body.get("agg", "mean")
+    if agg not in ("mean", "min", "max"):
+        raise ValueError("agg must be mean, min or max")
+    topk = body.get("topk", 20)
+    if isinstance(topk, bool) or not isinstance(topk, int) or topk < 0:
+        raise ValueError("topk must be a non-negative integer")
+    if not isinstance(body.get("exclude_adj", False), bool):
+        raise ValueError("exclude_adj must be true or false")
+    words = ["GROUP", str(topk), agg] + seeds
+    if body.get("exclude_adj", False):
+        words.append("noadj")
+    if body.get("exclude"):
+        words.append("exclude=" + ",".join(uids("exclude", body["exclude"])))
+    return " ".join(words)
+
+
 def load_config(root):
     """config.yaml as the reference reads it (app.py:15-23); absent file = defaults."""
     cfg = {}
@@ -242,6 +275,14 @@ def create_app(root, cli_cmd=None, load_users=None, ready_timeout=120.0, request
     def api_match(body: dict):
         try:
             line = match_line(body)
+        except (ValueError, TypeError) as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        return JSONResponse(cli_json(line))
+
+    @app.post("/api/group")
+    def api_group(body: dict):
+        try:
+            line = group_line(body)
         except (ValueError, TypeError) as e:
             raise HTTPException(status_code=422, detail=str(e))
         return JSONResponse(cli_json(line))

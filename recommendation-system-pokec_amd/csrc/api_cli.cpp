@@ -9,6 +9,9 @@
 // given on the line, for a person who is not a user of the corpus (pf_recommend_interest_profile).
 // It answers {"recommendations":{"interest":[{"id":..,"score":..},..]}}, USER's list format, or
 // {"error":"bad request","detail":..} / {"error":"engine failure","detail":..}.
+// GROUP <topk> <mean|min|max> <uid> <uid> ... [noadj] [exclude=<uid,uid,...>] is the group query
+// (pf_recommend_group): the users most similar to the listed seed users as a group; noadj also drops
+// every seed's adj_list row.  It answers {"recommendations":{"group":[..]}} or the same two errors.
 //
 //   pokec_api_cli [load_users] [--root DIR] [--device N] [--no-cap] [--cache PATH]
 //
@@ -212,6 +215,59 @@ int main(int argc, char** argv) {
             std::ostringstream os;
             os << "{\"recommendations\":{";
             write_list(os, "interest", r, nullptr);
+            os << "}}";
+            std::cout << os.str() << std::endl;
+            continue;
+        }
+        if (cmd == "GROUP") {
+            // GROUP <topk> <mean|min|max> <uid> <uid> ... [noadj] [exclude=<uid,uid,...>]
+            std::istringstream iss(line);
+            std::string w, agg;
+            int topk = -1;
+            iss >> w >> topk >> agg;
+            std::vector<int32_t> seeds, excl;
+            uint32_t flags = 0;
+            bool ok = !iss.fail() && topk >= 0 && (agg == "mean" || agg == "min" || agg == "max");
+            auto number = [](const std::string& t, int32_t& v) {
+                if (t.empty() || t.size() > 10) return false;
+                for (char ch : t)
+                    if (ch < '0' || ch > '9') return false;
+                const long long x = atoll(t.c_str());
+                v = (int32_t)x;
+                return x <= 2147483647LL;
+            };
+            while (ok && iss >> w) {
+                int32_t v = 0;
+                if (w == "noadj") {
+                    flags |= PF_GROUP_EXCLUDE_ADJ;
+                } else if (w.rfind("exclude=", 0) == 0) {
+                    std::istringstream es(w.substr(8));
+                    std::string t;
+                    while (ok && std::getline(es, t, ',')) {
+                        ok = number(t, v);
+                        excl.push_back(v);
+                    }
+                } else {
+                    ok = number(w, v);
+                    seeds.push_back(v);
+                }
+            }
+            if (!ok || seeds.empty()) {
+                std::cout << "{\"error\":\"bad request\",\"detail\":\"GROUP <topk> <mean|min|max> <uid>... [noadj] [exclude=<uid,...>]\"}"
+                          << std::endl;
+                continue;
+            }
+            const pf_group_query q{seeds.data(), (int32_t)seeds.size(), agg == "mean" ? PF_GROUP_MEAN : (agg == "min" ? PF_GROUP_MIN : PF_GROUP_MAX),
+                                   flags, excl.empty() ? nullptr : excl.data(), (int32_t)excl.size()};
+            List r(topk > 0 ? topk : 1);
+            if (pf_recommend_group(ctx, &q, 1, topk, r.id.data(), r.score.data(), &r.n) != PF_OK) {
+                std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
+                std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
+                continue;
+            }
+            std::ostringstream os;
+            os << "{\"recommendations\":{";
+            write_list(os, "group", r, nullptr);
             os << "}}";
             std::cout << os.str() << std::endl;
             continue;

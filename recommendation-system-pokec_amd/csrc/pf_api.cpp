@@ -1831,3 +1831,6 @@ int pf_profile_read(pf_ctx* c, double* total_ms, int64_t* launches) {
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- group query (pf_recommend_group ...)
+#include "pf_group_api.h"

@@ -29,6 +29,9 @@
 //                         (A/B: bit-exact, slower)
 //   k5s_static=1          K5s (variant build): static slice hand-out instead of claimed slices (A/B)
 //   k5s_batch_slices=N    K5s (variant build): slices per wave of a batched launch (default 16; A/B)
+//   group_tile=N          group scan (pf_recommend_group): at most N query images per pass (default:
+//                         as many as fit the pass's LDS budget; tests force 1, 2 and 3 passes' worth)
+//   group_lds=BYTES       group scan: the LDS budget of a pass (default 40960, four workgroups per CU; A/B)
 //   load_threads=N        loader threads (default: min(16, hardware threads))
 //   resident_post=0       one-query all-candidates scans build and upload their K5 image per call
 //                         instead of launching from the postings images built at open (A/B)

@@ -2381,3 +2381,7 @@ hipError_t launch_pairs(const PairsLaunch& L) {
 }
 
 }  // namespace pf
+
+// ---------------------------------------------------------------- group scan (pf_recommend_group)
+// fas_group_kernel and launch_group: a sibling of K1 built from the pieces above, in a file of its own
+#include "pf_group_kernel.h"

@@ -39,7 +39,8 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_set_scan_filter", "pf_scan_filter_count", "pf_set_scan_select", "pf_fas_pairs_select",
            "pf_num_cols", "pf_fas_pairs_terms", "pf_recommend_interest_all_terms",
            "pf_recommend_interest_profile", "pf_fas_profile_pairs", "pf_fas_profile_pairs_terms",
-           "pf_recommend_interest_profile_terms"]
+           "pf_recommend_interest_profile_terms",
+           "pf_recommend_group", "pf_group_scores", "pf_group_plan_of", "pf_group_image_lds"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
               "pf_dataset_profile_order", "pf_dataset_adj_order", "pf_dataset_profile_json", "pf_dataset_club_name",
@@ -251,6 +252,40 @@ class QueryProfile(ctypes.Structure):
                     tokens=tokens, exclude=arr(self.exclude_uid, self.n_exclude, ctypes.c_int32))
 
 
+PF_GROUP_MEAN, PF_GROUP_MIN, PF_GROUP_MAX = 0, 1, 2
+PF_GROUP_EXCLUDE_ADJ = 1
+PF_GROUP_MAX_SEEDS = 1024
+PF_GROUP_MAX_EXCLUDE = 26214
+_GROUP_AGG = {"mean": PF_GROUP_MEAN, "min": PF_GROUP_MIN, "max": PF_GROUP_MAX}
+
+
+class GroupQuery(ctypes.Structure):
+    """pf_group_query: a set of seed users whose look-alikes are asked for.  GroupQuery.make(...)
+    builds one and keeps its arrays alive."""
+    _fields_ = [("seed_uid", ctypes.c_void_p), ("n_seeds", ctypes.c_int32),
+                ("agg", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("exclude_uid", ctypes.c_void_p), ("n_exclude", ctypes.c_int32)]
+
+    @classmethod
+    def make(cls, seeds, agg="mean", exclude=(), exclude_adj=False):
+        """agg: "mean" / "min" / "max" or a PF_GROUP_* value; exclude: uids never returned;
+        exclude_adj: also drop every seed's adj_list row."""
+        g = cls()
+        g._seeds = np.ascontiguousarray(np.asarray(list(seeds), dtype=np.int32))
+        g._exclude = np.ascontiguousarray(np.asarray(list(exclude), dtype=np.int32))
+        g.seed_uid, g.n_seeds = (g._seeds.ctypes.data if len(g._seeds) else None), len(g._seeds)
+        g.exclude_uid, g.n_exclude = (g._exclude.ctypes.data if len(g._exclude) else None), len(g._exclude)
+        g.agg = _GROUP_AGG[agg] if isinstance(agg, str) else int(agg)
+        g.flags = PF_GROUP_EXCLUDE_ADJ if exclude_adj else 0
+        return g
+
+
+class GroupPlan(ctypes.Structure):
+    """pf_group_plan: what a group scan launches (kept seeds, passes, global-memory images, bytes)."""
+    _fields_ = [("n_seeds", ctypes.c_int32), ("n_passes", ctypes.c_int32), ("n_global", ctypes.c_int32),
+                ("pad", ctypes.c_int32), ("stream_bytes", ctypes.c_int64)]
+
+
 class PfJobsStats(ctypes.Structure):
     _fields_ = [("jobs", ctypes.c_int64), ("candidates", ctypes.c_int64), ("pairs", ctypes.c_int64),
                 ("pair_alg_bytes", ctypes.c_int64), ("pair_record_bytes", ctypes.c_int64),
@@ -323,6 +358,10 @@ def lib():
         L.pf_fas_profile_pairs_terms.argtypes = [V, V, V, I64, ctypes.POINTER(FieldSelect), V, V]
         L.pf_recommend_interest_profile_terms.argtypes = [V, V, I32, I32, V, V, V, V, V]
         L.pf_scan_keys_async.argtypes = [V, V, I32, I32, V, V]
+        L.pf_recommend_group.argtypes = [V, ctypes.POINTER(GroupQuery), I32, I32, V, V, V]
+        L.pf_group_scores.argtypes = [V, ctypes.POINTER(GroupQuery), V, I64, ctypes.POINTER(FieldSelect), V]
+        L.pf_group_plan_of.argtypes = [V, ctypes.POINTER(GroupQuery), ctypes.POINTER(GroupPlan)]
+        L.pf_group_image_lds.argtypes = [V, ctypes.POINTER(GroupQuery), V, I32]
         L.pf_merge_keys_async.argtypes = [V, V, I32, I32, I32, V, V]
         L.pf_decode_keys.argtypes = [V, I32, V, V, V]
         L.pf_decode_keys.restype = None
@@ -634,6 +673,59 @@ class FasEngine:
                                                        None if select is None else ctypes.byref(select),
                                                        head.ctypes.data, terms.ctypes.data), "pf_fas_profile_pairs_terms")
         return PairTerms(head, terms)
+
+    # -- group query (pf_group_query): who is similar to a set of seed users
+    def recommend_group(self, seeds, k, agg="mean", exclude=(), exclude_adj=False, filter=None, select=None):
+        """The top-k users most similar to the seed users as a group: (ids, scores).  agg: "mean",
+        "min" (similar to every seed) or "max" (similar to any seed).  The seeds and `exclude` are
+        never returned; exclude_adj also drops every seed's adj_list row.  filter / select as in
+        recommend_interest_all: those in force before the call are restored afterwards."""
+        g = GroupQuery.make(seeds, agg, exclude, exclude_adj)
+        k = max(int(k), 0)
+        ou = np.zeros(max(k, 1), np.int32)
+        os_ = np.zeros(max(k, 1), np.float32)
+        oc = np.zeros(1, np.int32)
+        prev, prev_sel = self._filter, self._select
+        try:
+            if filter is not None:
+                self.set_scan_filter(filter)
+            if select is not None:
+                self.set_scan_select(select)
+            self._check(self._L.pf_recommend_group(self.h, ctypes.byref(g), 1, k, ou.ctypes.data, os_.ctypes.data,
+                                                   oc.ctypes.data), "pf_recommend_group")
+        finally:
+            if filter is not None:
+                self.set_scan_filter(prev)
+            if select is not None:
+                self.set_scan_select(prev_sel)
+        return ou[:oc[0]].copy(), os_[:oc[0]].copy()
+
+    def group_scores(self, seeds, b_uid, agg="mean", select=None):
+        """The group's aggregate score of each listed user (NaN for an unknown uid), with no filter and
+        no exclusion, under select (a FieldSelect) or none: computed by the pair kernel."""
+        g = GroupQuery.make(seeds, agg)
+        b = _i32(b_uid)
+        out = np.empty(len(b), np.float32)
+        self._check(self._L.pf_group_scores(self.h, ctypes.byref(g), b.ctypes.data, len(b),
+                                            None if select is None else ctypes.byref(select), out.ctypes.data),
+                    "pf_group_scores")
+        return out
+
+    def group_plan(self, seeds, agg="mean", exclude=(), exclude_adj=False):
+        """What recommend_group would launch for these seeds (a GroupPlan)."""
+        g = GroupQuery.make(seeds, agg, exclude, exclude_adj)
+        p = GroupPlan()
+        self._check(self._L.pf_group_plan_of(self.h, ctypes.byref(g), ctypes.byref(p)), "pf_group_plan_of")
+        return p
+
+    def group_image_lds(self, seeds, agg="mean", exclude=(), exclude_adj=False):
+        """(per kept seed: LDS bytes of its image in a pass, a pass's bytes besides its images, a
+        pass's LDS budget): the inputs of the packing rule group_plan().n_passes follows."""
+        g = GroupQuery.make(seeds, agg, exclude, exclude_adj)
+        out = np.zeros(len(g._seeds) + 2, np.int32)
+        self._check(self._L.pf_group_image_lds(self.h, ctypes.byref(g), out.ctypes.data, len(out)), "pf_group_image_lds")
+        G = self.group_plan(seeds, agg, exclude, exclude_adj).n_seeds
+        return out[:G].copy(), int(out[G]), int(out[G + 1])
 
     def fof_candidates(self, uid, limit, flavour=PF_FOF_GRAPH):
         cap = max(int(limit), 1) + 1
