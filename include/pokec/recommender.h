@@ -136,6 +136,36 @@ struct FieldSelect {
     }
 };
 
+// Which part of the ranked order an all-candidates call returns (pokec_fas.h pf_scan_window): a
+// floor (results score >= min_score), a paging cursor (results rank strictly after (after_score,
+// after_uid): pass a page's last result to get the next page) and, with `count`, the number of
+// candidates in the window, returned through the call's `total` argument.  Under a window topk is
+// at most 64: the cursor is the way deeper.
+struct ScoreWindow {
+    bool has_min = false, has_after = false, count = false;
+    float min_score = 0.f, after_score = 0.f;
+    int after_uid = 0;
+
+    static ScoreWindow floor(float s) { ScoreWindow w; w.has_min = true; w.min_score = s; return w; }
+    static ScoreWindow after(float score, int uid) {
+        ScoreWindow w;
+        w.has_after = true;
+        w.after_score = score;
+        w.after_uid = uid;
+        return w;
+    }
+    ScoreWindow with_floor(float s) const { ScoreWindow w = *this; w.has_min = true; w.min_score = s; return w; }
+    ScoreWindow with_count() const { ScoreWindow w = *this; w.count = true; return w; }
+
+    pf_scan_window c_form() const {
+        pf_scan_window w{};
+        if (has_min) { w.fields |= PF_WIN_MIN; w.min_score = min_score; }
+        if (has_after) { w.fields |= PF_WIN_AFTER; w.after_score = after_score; w.after_uid = after_uid; }
+        if (count) w.fields |= PF_WIN_COUNT;
+        return w;
+    }
+};
+
 // The breakdown of a pair's FAS (pokec_fas.h pf_fas_pairs_terms): the per-field sigmoid terms the
 // reference adds to sum_Si.  terms has 7 + (set_text_columns' list) doubles, slot k < 7 the fixed
 // field PF_F_*, slot 7 + t column t; a slot is present where its mask bit is set (`fixed` bit k,
@@ -310,6 +340,21 @@ public:
         return run_(3, user, topk, 0, &f, &s);
     }
 
+    // The same inside a score window (a floor, a paging cursor, a count): the engine's window is set
+    // for this call and cleared afterwards, under the engine's lock.  total (optional) receives the
+    // number of candidates in the window when window.count is set.  The cursor of page n + 1 is page
+    // n's last result; a page shorter than topk ends the ranking.
+    Ranked recommend_interest_all(int user, int topk, const ScoreWindow& window, int64_t* total = nullptr) const {
+        const pf_scan_window w = window.c_form();
+        return run_(3, user, topk, 0, nullptr, nullptr, &w, total);
+    }
+    Ranked recommend_interest_all(int user, int topk, const ScoreWindow& window, const CandidateFilter& filter,
+                                  int64_t* total = nullptr) const {
+        const pf_cand_filter f = filter.c_form();
+        const pf_scan_window w = window.c_form();
+        return run_(3, user, topk, 0, &f, nullptr, &w, total);
+    }
+
     // recommender_similarity.cpp:10-124,126-128, for two profiles of the map
     float profile_similarity(const Profile& A, const Profile& B) const {
         return pair_(engine_(), A.user_id, B.user_id);
@@ -349,20 +394,13 @@ public:
     // map; its user_id plays no part.  The all-candidates top-k over every profile of the map but
     // those in `exclude` (nothing is excluded implicitly: pass A's own id and friends to leave them out).
     Ranked recommend_by_profile(const Profile& A, int topk, const std::vector<int>& exclude = {}) const {
-        Ranked out;
-        if (!profiles || topk <= 0) return out;
-        std::shared_ptr<detail::Engine> e = engine_();
-        if (!e) return out;
-        std::lock_guard<std::mutex> g(e->mu);
-        QueryHold h;
-        const pf_query_profile q = query_of_(e->ctx, A, exclude, h);
-        topk = (int)std::min<int64_t>(topk, e->n_users + 1);
-        std::vector<int32_t> ids((size_t)topk);
-        std::vector<float> sc((size_t)topk);
-        int32_t n = 0;
-        if (pf_recommend_interest_profile(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n) != PF_OK) return fail_(e->ctx, out);
-        for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
-        return out;
+        return by_profile_(A, topk, exclude, nullptr, nullptr);
+    }
+    // ... inside a score window (ScoreWindow: the cursor takes a profile query past result 64)
+    Ranked recommend_by_profile(const Profile& A, int topk, const std::vector<int>& exclude, const ScoreWindow& window,
+                                int64_t* total = nullptr) const {
+        const pf_scan_window w = window.c_form();
+        return by_profile_(A, topk, exclude, &w, total);
     }
     // profile_similarity(A, B) with A by value and B of the map (NaN when B is not); the overload over
     // the selected fields only
@@ -386,23 +424,13 @@ public:
     // caller's adj_list holds it now.  topk above 64 is refused (an empty list, last_error says why).
     Ranked recommend_for_group(const std::vector<int>& seeds, int topk, GroupAgg agg = GroupAgg::Mean,
                                bool exclude_adj = false, const std::vector<int>& exclude = {}) const {
-        Ranked out;
-        if (!profiles || topk <= 0 || seeds.empty()) return out;
-        std::shared_ptr<detail::Engine> e = engine_();
-        if (!e) return out;
-        std::lock_guard<std::mutex> g(e->mu);
-        if (exclude_adj && adj_list)
-            for (int s : seeds)
-                if (sync_row_(*e, s) != PF_OK) return fail_(e->ctx, out);
-        const std::vector<int32_t> sd(seeds.begin(), seeds.end()), ex(exclude.begin(), exclude.end());
-        const pf_group_query q{sd.data(), (int32_t)sd.size(), (int32_t)agg, exclude_adj ? PF_GROUP_EXCLUDE_ADJ : 0u,
-                               ex.empty() ? nullptr : ex.data(), (int32_t)ex.size()};
-        std::vector<int32_t> ids((size_t)topk);
-        std::vector<float> sc((size_t)topk);
-        int32_t n = 0;
-        if (pf_recommend_group(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n) != PF_OK) return fail_(e->ctx, out);
-        for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
-        return out;
+        return for_group_(seeds, topk, agg, exclude_adj, exclude, nullptr, nullptr);
+    }
+    // ... inside a score window (ScoreWindow: the cursor takes a group query past result 64)
+    Ranked recommend_for_group(const std::vector<int>& seeds, int topk, GroupAgg agg, bool exclude_adj,
+                               const std::vector<int>& exclude, const ScoreWindow& window, int64_t* total = nullptr) const {
+        const pf_scan_window w = window.c_form();
+        return for_group_(seeds, topk, agg, exclude_adj, exclude, &w, total);
     }
     // The group's aggregate score of B, a profile of the map (NaN when B or every seed is not): how
     // well B fits the group.  No exclusion applies: a seed is scored like anyone else.
@@ -445,8 +473,72 @@ public:
     size_t total_users = 0;
 
 private:
+    // The engine's score window for the span of one call (set here, cleared on the way out: the facade
+    // keeps none in force between calls); total() reads the call's count when the window counts.
+    struct WindowScope {
+        pf_ctx* ctx;
+        const pf_scan_window* w;
+        int rc = PF_OK;
+        WindowScope(pf_ctx* c, const pf_scan_window* win) : ctx(c), w(win) {
+            if (w) rc = pf_set_scan_window(ctx, w);
+        }
+        ~WindowScope() {
+            if (w) (void)pf_set_scan_window(ctx, nullptr);
+        }
+        bool total(int64_t* out) const {
+            if (!w || !out || !(w->fields & PF_WIN_COUNT)) return true;
+            int32_t n = 0;
+            *out = 0;
+            return pf_scan_window_totals(ctx, out, 1, &n) == PF_OK;
+        }
+    };
+
+    Ranked by_profile_(const Profile& A, int topk, const std::vector<int>& exclude, const pf_scan_window* window,
+                       int64_t* total) const {
+        Ranked out;
+        if (!profiles || topk <= 0) return out;
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return out;
+        std::lock_guard<std::mutex> g(e->mu);
+        QueryHold h;
+        const pf_query_profile q = query_of_(e->ctx, A, exclude, h);
+        topk = (int)std::min<int64_t>(topk, e->n_users + 1);
+        std::vector<int32_t> ids((size_t)topk);
+        std::vector<float> sc((size_t)topk);
+        int32_t n = 0;
+        WindowScope ws(e->ctx, window);
+        if (ws.rc != PF_OK || pf_recommend_interest_profile(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n) != PF_OK)
+            return fail_(e->ctx, out);
+        if (!ws.total(total)) return fail_(e->ctx, out);
+        for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
+        return out;
+    }
+
+    Ranked for_group_(const std::vector<int>& seeds, int topk, GroupAgg agg, bool exclude_adj, const std::vector<int>& exclude,
+                      const pf_scan_window* window, int64_t* total) const {
+        Ranked out;
+        if (!profiles || topk <= 0 || seeds.empty()) return out;
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return out;
+        std::lock_guard<std::mutex> g(e->mu);
+        if (exclude_adj && adj_list)
+            for (int s : seeds)
+                if (sync_row_(*e, s) != PF_OK) return fail_(e->ctx, out);
+        const std::vector<int32_t> sd(seeds.begin(), seeds.end()), ex(exclude.begin(), exclude.end());
+        const pf_group_query q{sd.data(), (int32_t)sd.size(), (int32_t)agg, exclude_adj ? PF_GROUP_EXCLUDE_ADJ : 0u,
+                               ex.empty() ? nullptr : ex.data(), (int32_t)ex.size()};
+        std::vector<int32_t> ids((size_t)topk);
+        std::vector<float> sc((size_t)topk);
+        int32_t n = 0;
+        WindowScope ws(e->ctx, window);
+        if (ws.rc != PF_OK || pf_recommend_group(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n) != PF_OK) return fail_(e->ctx, out);
+        if (!ws.total(total)) return fail_(e->ctx, out);
+        for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
+        return out;
+    }
+
     Ranked run_(int kind, int user, int topk, int limit, const pf_cand_filter* filter = nullptr,
-                const pf_field_select* select = nullptr) const {
+                const pf_field_select* select = nullptr, const pf_scan_window* window = nullptr, int64_t* total = nullptr) const {
         Ranked out;
         if (!profiles || !adj_list || topk <= 0) return out;
         std::shared_ptr<detail::Engine> e = engine_();
@@ -473,7 +565,12 @@ private:
             default:
                 if (filter) rc = pf_set_scan_filter(e->ctx, filter);
                 if (select && rc == PF_OK) rc = pf_set_scan_select(e->ctx, select);
-                if (rc == PF_OK) rc = pf_recommend_interest(e->ctx, &q, 1, topk, PF_MODE_ALL, 0, ids.data(), sc.data(), &n);
+                {
+                    WindowScope ws(e->ctx, rc == PF_OK ? window : nullptr);
+                    if (rc == PF_OK) rc = ws.rc;
+                    if (rc == PF_OK) rc = pf_recommend_interest(e->ctx, &q, 1, topk, PF_MODE_ALL, 0, ids.data(), sc.data(), &n);
+                    if (rc == PF_OK && !ws.total(total)) rc = PF_EINTERNAL;
+                }
                 if (filter) {  // the filter in force before the call
                     const int rr = pf_set_scan_filter(e->ctx, e->scan_filter.fields ? &e->scan_filter : nullptr);
                     if (rc == PF_OK) rc = rr;

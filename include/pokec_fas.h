@@ -452,6 +452,57 @@ int pf_group_plan_of(pf_ctx* ctx, const pf_group_query* g, pf_group_plan* out);
 int pf_group_image_lds(pf_ctx* ctx, const pf_group_query* g, int32_t* out, int32_t cap);
 
 /*
+ * Score window of the all-candidates scans: a floor ("at least this similar"), a paging cursor ("load
+ * more") and a match count ("how many").  A window restricts which candidates are RANKED; every score
+ * is computed bit for bit as without one.
+ *   The test     A candidate is in the window when it is rankable as without one (in the shard, passing
+ *                the filter, not excluded) and
+ *                  under PF_WIN_MIN   its float score is >= min_score;
+ *                  under PF_WIN_AFTER it ranks strictly after the cursor in the engine's order: score <
+ *                                     after_score, or score == after_score and uid > after_uid (signed).
+ *                The cursor is a position, not a member: after_uid need not be a stored user and
+ *                after_score need not be anybody's score.  -0.0 is 0.0, as in the ranking.
+ *   Results      The window's first topk in (score desc, uid asc); out_count < topk means the window is
+ *                exhausted.
+ *   Paging       Page n + 1 is the same call with after_* set to page n's last result; the pages
+ *                concatenated equal the unwindowed ranking.  This holds for profile and group queries
+ *                too, whose topk stops at 64: the cursor takes them to any depth.
+ *   State        Context state like the filter and the selection; it travels by value with every launch,
+ *                so asynchronous scans already queued keep theirs.  Read by
+ *                pf_recommend_interest(PF_MODE_ALL), pf_recommend_interest_profile, pf_recommend_group,
+ *                their _terms forms and pf_scan_keys_async, and by nothing else: FoF interest, collab,
+ *                clubs, the pair calls, pf_group_scores and the hold-out drivers never see it.  One
+ *                window serves all nq queries of a call (a floor and a count suit batches; a cursor is
+ *                meant for nq == 1 but is legal for any).  No query image, resident image or store
+ *                changes; with none set every result and every launch is what it was.
+ *   Count        Under PF_WIN_COUNT a synchronous scan call also stores, per query, the number of
+ *                candidates of this context's shard in the window, whatever topk > 0 is (topk = 0 scans
+ *                nothing and stores no count).
+ *                pf_scan_window_totals returns the last such call's values (*n = that call's nq; at most
+ *                cap are written); a value is 0 for an unknown uid and for a group with G = 0.
+ *                PF_EINVAL when no counted call has run.  Sharded callers sum the per-shard values.
+ *   The floor    seeds the postings scan's pruning threshold (it is valid before the first block), so a
+ *                floored scan begins no block cold and is, if anything, cheaper than the unwindowed one.
+ *                A counted scan holds the threshold at the floor and prunes no further.
+ *   Refusals     PF_EINVAL: unknown bits in fields, non-zero flags, a NaN score under its bit; the window
+ *                in force is left alone.  PF_EUNSUPP (pf_last_error names the reason): a window in force
+ *                with topk > 64 on PF_MODE_ALL (the job pipeline does not read it: the cursor is the way
+ *                deep), PF_WIN_COUNT with pf_scan_keys_async.  min_score <= 0 passes everybody and
+ *                min_score > 1 may pass nobody; neither is an error.
+ */
+#define PF_WIN_MIN   1u   /* min_score holds */
+#define PF_WIN_AFTER 2u   /* after_score / after_uid hold */
+#define PF_WIN_COUNT 4u   /* also count the candidates in the window */
+typedef struct pf_scan_window {
+    uint32_t fields, flags;          /* flags must be 0 */
+    float    min_score, after_score;
+    int32_t  after_uid, pad;
+} pf_scan_window; /* 24 B */
+/* NULL or fields == 0 clears. */
+int pf_set_scan_window(pf_ctx* ctx, const pf_scan_window* window);
+int pf_scan_window_totals(pf_ctx* ctx, int64_t* out, int32_t cap, int32_t* n);
+
+/*
  * Device-resident all-candidates scan for the multi-GPU bench: scores the
  * queries against this context's shard and writes, per query, `topk` packed
  * 64-bit keys to DEVICE memory d_keys[nq*topk] on `stream` (a hipStream_t).
@@ -513,7 +564,9 @@ int pf_layout(const pf_ctx* ctx, pf_layout_stats* out);
  * bytes are those of the unfiltered scan (a filtered one reads the same headers and ranges and
  * skips the list entries of the blocks in which nobody passes).  The field selection
  * (pf_set_scan_select) is ignored as well: the bytes are those of the unselected scan (a selected
- * one reads no entry of a deselected column's or set's lists). */
+ * one reads no entry of a deselected column's or set's lists).  The score window (pf_set_scan_window)
+ * is ignored too: the bytes are those of the unwindowed scan (a floored one skips the list entries of
+ * the candidates its seeded threshold drops). */
 int pf_scan_bytes(pf_ctx* ctx, const int32_t* query_uid, int32_t nq, int64_t* out_bytes);
 /* Counters of the postings scan's pruning, summed over the postings scans of this process
  * (one-query launches and batches) since the last reset while PF_DEBUG k5_prune_stats=1 is set (zeros otherwise): out[5] =

@@ -21,6 +21,11 @@ and one route of the engine's own:
                                          "tokens": {"<column index>": [[tid, tf], ...]}}, every field optional.
                                         Text columns are token ids: callers that ran the reference's encoder, or
                                         that match on the fixed fields and clubs only (no text -> id ETL here).
+    POST /api/match and /api/group also take the score window (pokec_fas.h pf_scan_window):
+                                        "min_score": 0.3 (only results scoring at least that), "after": "<next>" (the
+                                        "next" token of the page before: load more) and "count": true (the reply gains
+                                        "total", the number of users in the window).  A reply to a body with one of
+                                        them ends with "next", the token of its last result.
 
 What differs, because the reference's file cannot run as written:
   * it has unresolved merge-conflict markers (app.py:38-42, 147-159); the start-up wait here
@@ -41,6 +46,7 @@ import contextlib
 import json
 import os
 import queue
+import re
 import subprocess
 import sys
 import threading
@@ -51,12 +57,38 @@ DEFAULT_CLI = os.path.join(HERE, "pokec_api_cli")
 KINDS = {"graph": "graph", "collab": "collaborative", "interest": "interest", "clubs": "clubs"}
 
 
+_CURSOR = re.compile(r"^[0-9a-fA-F]{8}:-?[0-9]{1,10}$")
+
+
+def window_words(body):
+    """The score window's words of a /api/match or /api/group body (csrc/match_line.h): min_score,
+    after (a "next" token as a reply gave it) and count; ValueError on a field of the wrong shape."""
+    words = []
+    v = body.get("min_score")
+    if v is not None:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            raise ValueError("min_score must be a number")
+        words.append("min=" + repr(float(v)))
+    v = body.get("after")
+    if v is not None:
+        if not isinstance(v, str) or not _CURSOR.match(v):
+            raise ValueError("after must be the \"next\" token of an earlier reply")
+        words.append("after=" + v)
+    v = body.get("count", False)
+    if not isinstance(v, bool):
+        raise ValueError("count must be true or false")
+    if v:
+        words.append("count")
+    return words
+
+
 def match_line(body):
     """The api_cli "MATCH ..." line of a POST /api/match body (csrc/match_line.h); ValueError on a
     field of the wrong shape."""
     if not isinstance(body, dict):
         raise ValueError("the body must be a JSON object")
-    unknown = set(body) - {"topk", "public", "gender", "completion", "age", "region", "clubs", "friends", "exclude", "tokens"}
+    unknown = set(body) - {"topk", "public", "gender", "completion", "age", "region", "clubs", "friends", "exclude", "tokens",
+                           "min_score", "after", "count"}
     if unknown:
         raise ValueError("unknown field: " + sorted(unknown)[0])
 
@@ -84,15 +116,15 @@ def match_line(body):
             raise ValueError("tokens must map a column index to [[tid, tf], ...]")
         if row:
             words.append(f"c{t}=" + ",".join(ints("tokens", p).replace(",", ":") for p in row))
-    return " ".join(words)
+    return " ".join(words + window_words(body))
 
 
 def group_line(body):
     """The api_cli "GROUP ..." line of a POST /api/group body {"seeds": [...], "topk": 20, "agg":
-    "mean", "exclude": [...], "exclude_adj": false}; ValueError on a field of the wrong shape."""
+    "mean", "exclude": [...], "exclude_adj": false} and the window's fields (window_words); ValueError on a field of the wrong shape."""
     if not isinstance(body, dict):
         raise ValueError("the body must be a JSON object")
-    unknown = set(body) - {"seeds", "topk", "agg", "exclude", "exclude_adj"}
+    unknown = set(body) - {"seeds", "topk", "agg", "exclude", "exclude_adj", "min_score", "after", "count"}
     if unknown:
         raise ValueError("unknown field: " + sorted(unknown)[0])
 
@@ -117,7 +149,7 @@ def group_line(body):
         words.append("noadj")
     if body.get("exclude"):
         words.append("exclude=" + ",".join(uids("exclude", body["exclude"])))
-    return " ".join(words)
+    return " ".join(words + window_words(body))
 
 
 def load_config(root):

@@ -82,6 +82,33 @@ void write_list(std::ostringstream& os, const char* name, const List& l, const p
     os << "]";
 }
 
+// The score window of one MATCH / GROUP line (match_line.h: min=, after=, count): set for the span of
+// the call, cleared on the way out.  A line without those words touches nothing and its reply is the
+// line it always was; with one, tail() adds the last result's cursor and, under `count`, the total.
+struct WindowScope {
+    pf_ctx* ctx;
+    pf_scan_window w;
+    bool ok = true;
+    WindowScope(pf_ctx* c, const pf_scan_window& win) : ctx(c), w(win) {
+        if (w.fields) ok = pf_set_scan_window(ctx, &w) == PF_OK;
+    }
+    ~WindowScope() {
+        if (w.fields) pf_set_scan_window(ctx, nullptr);
+    }
+    std::string tail(const List& r, int topk) const {
+        if (!w.fields) return "";
+        std::ostringstream os;
+        if (r.n > 0) os << ",\"next\":\"" << pokec::window_cursor(r.score[(size_t)r.n - 1], r.id[(size_t)r.n - 1]) << "\"";
+        else os << ",\"next\":null";
+        if ((w.fields & PF_WIN_COUNT) && topk > 0) {  // (topk = 0 scans nothing and counts nothing)
+            int64_t total = 0;
+            int32_t n = 0;
+            if (pf_scan_window_totals(ctx, &total, 1, &n) == PF_OK) os << ",\"total\":" << total;
+        }
+        return os.str();
+    }
+};
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -207,7 +234,8 @@ int main(int argc, char** argv) {
             }
             const pf_query_profile q = m.profile();
             List r(m.topk > 0 ? m.topk : 1);
-            if (pf_recommend_interest_profile(ctx, &q, 1, m.topk, r.id.data(), r.score.data(), &r.n) != PF_OK) {
+            const WindowScope ws(ctx, m.window);
+            if (!ws.ok || pf_recommend_interest_profile(ctx, &q, 1, m.topk, r.id.data(), r.score.data(), &r.n) != PF_OK) {
                 std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
                 std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
                 continue;
@@ -215,17 +243,19 @@ int main(int argc, char** argv) {
             std::ostringstream os;
             os << "{\"recommendations\":{";
             write_list(os, "interest", r, nullptr);
-            os << "}}";
+            os << "}" << ws.tail(r, m.topk) << "}";
             std::cout << os.str() << std::endl;
             continue;
         }
         if (cmd == "GROUP") {
-            // GROUP <topk> <mean|min|max> <uid> <uid> ... [noadj] [exclude=<uid,uid,...>]
+            // GROUP <topk> <mean|min|max> <uid> <uid> ... [noadj] [exclude=<uid,uid,...>] and the window's
+            // words (match_line.h): [min=<float>] [after=<hex>:<uid>] [count]
             std::istringstream iss(line);
             std::string w, agg;
             int topk = -1;
             iss >> w >> topk >> agg;
             std::vector<int32_t> seeds, excl;
+            pf_scan_window win{};
             uint32_t flags = 0;
             bool ok = !iss.fail() && topk >= 0 && (agg == "mean" || agg == "min" || agg == "max");
             auto number = [](const std::string& t, int32_t& v) {
@@ -238,7 +268,10 @@ int main(int argc, char** argv) {
             };
             while (ok && iss >> w) {
                 int32_t v = 0;
-                if (w == "noadj") {
+                const int ww = pokec::parse_window_word(w, win);
+                if (ww != 0) {
+                    ok = ww > 0;
+                } else if (w == "noadj") {
                     flags |= PF_GROUP_EXCLUDE_ADJ;
                 } else if (w.rfind("exclude=", 0) == 0) {
                     std::istringstream es(w.substr(8));
@@ -253,14 +286,15 @@ int main(int argc, char** argv) {
                 }
             }
             if (!ok || seeds.empty()) {
-                std::cout << "{\"error\":\"bad request\",\"detail\":\"GROUP <topk> <mean|min|max> <uid>... [noadj] [exclude=<uid,...>]\"}"
+                std::cout << "{\"error\":\"bad request\",\"detail\":\"GROUP <topk> <mean|min|max> <uid>... [noadj] [exclude=<uid,...>] [min=<float>] [after=<hex>:<uid>] [count]\"}"
                           << std::endl;
                 continue;
             }
             const pf_group_query q{seeds.data(), (int32_t)seeds.size(), agg == "mean" ? PF_GROUP_MEAN : (agg == "min" ? PF_GROUP_MIN : PF_GROUP_MAX),
                                    flags, excl.empty() ? nullptr : excl.data(), (int32_t)excl.size()};
             List r(topk > 0 ? topk : 1);
-            if (pf_recommend_group(ctx, &q, 1, topk, r.id.data(), r.score.data(), &r.n) != PF_OK) {
+            const WindowScope ws(ctx, win);
+            if (!ws.ok || pf_recommend_group(ctx, &q, 1, topk, r.id.data(), r.score.data(), &r.n) != PF_OK) {
                 std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
                 std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
                 continue;
@@ -268,7 +302,7 @@ int main(int argc, char** argv) {
             std::ostringstream os;
             os << "{\"recommendations\":{";
             write_list(os, "group", r, nullptr);
-            os << "}}";
+            os << "}" << ws.tail(r, topk) << "}";
             std::cout << os.str() << std::endl;
             continue;
         }

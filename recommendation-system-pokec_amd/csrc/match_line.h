@@ -4,12 +4,19 @@
 //   MATCH <topk> [public=N] [gender=N] [completion=N] [age=N] [region=a,b,c] [clubs=id,id,..]
 //         [friends=id,id,..] [exclude=uid,uid,..] [c<t>=tid:tf,tid:tf,..]...
 //
+// and the score window's words (pokec_fas.h pf_scan_window), which GROUP takes as well:
+//         [min=<float>] [after=<8 hex digits of the score's float bits>:<uid>] [count]
+// The cursor token carries the float's bits because printed decimal scores lose them; a reply to a
+// line with one of these words ends with "next":"<hex>:<uid>", the last result's cursor.
+//
 // A field that is not given is missing; an empty region part ("region=3,,27") is missing; c<t> is
 // text column t of the engine's list, as token ids (the text -> id ETL is not part of the engine).
 // Engine-free, so the parser is tested without a GPU.
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -23,6 +30,7 @@ struct MatchLine {
     int32_t pub = -1, gen = -1, comp = 0, age = 0, reg[3] = {-1, -1, -1};
     std::vector<uint32_t> clubs, friends;
     std::vector<int32_t> exclude;
+    pf_scan_window window{};  // fields == 0: the line has none of the window's words
     std::vector<std::vector<std::pair<int32_t, int32_t>>> cols;  // [n_cols] (tid, tf) in the line's order
     // the C struct over this object's arrays (valid while the object lives and is not changed)
     std::vector<int64_t> off;
@@ -63,6 +71,52 @@ inline std::vector<std::string> split(const std::string& s, char sep) {
 }
 }  // namespace match_detail
 
+// One word of a MATCH / GROUP line as a word of the score window: 1 = taken into `win`, 0 = not a
+// window word, -1 = a window word with a malformed value.
+inline int parse_window_word(const std::string& w, pf_scan_window& win) {
+    if (w == "count") {
+        win.fields |= PF_WIN_COUNT;
+        return 1;
+    }
+    if (w.rfind("min=", 0) == 0) {
+        const std::string val = w.substr(4);
+        char* end = nullptr;
+        const float f = std::strtof(val.c_str(), &end);
+        if (val.empty() || *end != '\0' || f != f) return -1;
+        win.fields |= PF_WIN_MIN;
+        win.min_score = f;
+        return 1;
+    }
+    if (w.rfind("after=", 0) == 0) {
+        const std::string val = w.substr(6);
+        long long uid = 0;
+        if (val.size() < 10 || val[8] != ':' || !match_detail::to_int(val.substr(9), INT32_MIN, INT32_MAX, uid)) return -1;
+        uint32_t bits = 0;
+        for (int i = 0; i < 8; ++i) {
+            const char ch = val[(size_t)i];
+            const int d = ch >= '0' && ch <= '9' ? ch - '0' : (ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : (ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1));
+            if (d < 0) return -1;
+            bits = bits << 4 | (uint32_t)d;
+        }
+        float f;
+        std::memcpy(&f, &bits, sizeof f);
+        if (f != f) return -1;
+        win.fields |= PF_WIN_AFTER;
+        win.after_score = f;
+        win.after_uid = (int32_t)uid;
+        return 1;
+    }
+    return 0;
+}
+// the cursor token of a result: its score's float bits and its uid
+inline std::string window_cursor(float score, int32_t uid) {
+    uint32_t bits = 0;
+    std::memcpy(&bits, &score, sizeof bits);
+    char buf[32];
+    std::snprintf(buf, sizeof buf, "%08x:%d", bits, uid);
+    return buf;
+}
+
 // Parses the words after "MATCH" for an engine of n_cols text columns; false with `why` on a
 // malformed line (an unknown key, a value that is not a number, a column outside the engine's list).
 inline bool parse_match_line(const std::string& rest, int n_cols, MatchLine& m, std::string& why) {
@@ -76,6 +130,9 @@ inline bool parse_match_line(const std::string& rest, int n_cols, MatchLine& m, 
     m.topk = (int)v;
     const long long i32lo = INT32_MIN, i32hi = INT32_MAX;
     while (iss >> w) {
+        const int ww = parse_window_word(w, m.window);
+        if (ww < 0) { why = "bad value: " + w; return false; }
+        if (ww > 0) continue;
         const size_t eq = w.find('=');
         if (eq == std::string::npos || eq == 0) { why = "not key=value: " + w; return false; }
         const std::string key = w.substr(0, eq), val = w.substr(eq + 1);

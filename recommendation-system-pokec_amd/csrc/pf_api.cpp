@@ -348,8 +348,38 @@ int batch_blocks_per_wg() {
 uint32_t post_image_lds(const pf::QPostHead* h) {
     return pf::post_lds(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend));
 }
-// LDS a filtered launch takes on top of an image's (the filter's words; pf_kernels.h kFiltLds)
-uint32_t filt_lds(const pf_ctx* c) { return c->filt.fields ? pf::kFiltLds : 0u; }
+// LDS a filtered / windowed launch takes on top of an image's (the filter's and the window's words;
+// pf_kernels.h kFiltLds, kWinLds)
+uint32_t filt_lds(const pf_ctx* c) { return (c->filt.fields ? pf::kFiltLds : 0u) + (c->win.fields ? pf::kWinLds : 0u); }
+
+// A counted synchronous call (a window with PF_WIN_COUNT): the launches write each query's count to
+// its row of d_totals, zeroed first (an unknown uid and an empty group stay 0); finish() brings the
+// rows to win_totals after the call's launches.  Not counted: every member function does nothing.
+struct CountScope {
+    pf_ctx* c;
+    int n;
+    bool on;
+    CountScope(pf_ctx* ctx, int nq) : c(ctx), n(nq), on((ctx->win.fields & pf::kWinCount) != 0u && nq > 0) {}
+    ~CountScope() { c->cur_totals = nullptr; }
+    int begin() {
+        if (!on) return PF_OK;
+        HIPCHK(c, c->d_totals.ensure((size_t)n * sizeof(uint32_t)));
+        HIPCHK(c, hipMemsetAsync(c->d_totals.p, 0, (size_t)n * sizeof(uint32_t), c->stream));
+        c->cur_totals = c->d_totals.as<uint32_t>();
+        return PF_OK;
+    }
+    void at(size_t row0) { if (on) c->cur_totals = c->d_totals.as<uint32_t>() + row0; }
+    int finish() {
+        c->cur_totals = nullptr;
+        if (!on) return PF_OK;
+        std::vector<uint32_t> v((size_t)n);
+        HIPCHK(c, hipMemcpyAsync(v.data(), c->d_totals.p, v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->win_totals.assign(v.begin(), v.end());
+        c->win_totals_set = true;
+        return PF_OK;
+    }
+};
 
 int scan_lanes();
 
@@ -463,8 +493,8 @@ int lane_end(pf_ctx* c, const LaneUse& u, hipEvent_t stop, hipStream_t caller, u
 }
 
 // Workgroups of a one-query K5 launch before the clamp to the shard's blocks (the launches, pf_scan_bytes)
-int one_query_grid(const pf_ctx* c, uint32_t var_lds, bool filtered, bool selected, bool lanes) {
-    return one_query_wgs(c->num_cus * pf::post_blocks_per_cu(var_lds, true, filtered, selected), lanes);
+int one_query_grid(const pf_ctx* c, uint32_t var_lds, bool filtered, bool selected, bool windowed, bool lanes) {
+    return one_query_wgs(c->num_cus * pf::post_blocks_per_cu(var_lds, true, filtered, selected, windowed), lanes);
 }
 
 // Where a K5 launch reads its queries: image q at pool + img_off[q] (its QConst there, or at qconst
@@ -520,7 +550,7 @@ int scan_post_one(pf_ctx* c, uint32_t var_lds, int32_t row, int k, uint64_t* d_k
     pf_ctx::ScanLane* ln = lu.ln;
     const hipStream_t ls = ln ? ln->st : s;
     const int blocks = std::max(1, std::min(c->wb_end - c->wb_begin,
-                                            one_query_grid(c, var_lds, c->filt.fields != 0u, c->sel.on != 0u, ln != nullptr)));
+                                            one_query_grid(c, var_lds, c->filt.fields != 0u, c->sel.on != 0u, c->win.fields != 0u, ln != nullptr)));
     PostQueries Q;
     rc = place(ln, ls, Q);
     if (rc != PF_OK) return rc;
@@ -537,7 +567,8 @@ int scan_post_one(pf_ctx* c, uint32_t var_lds, int32_t row, int k, uint64_t* d_k
                                .blk_begin = c->wb_begin, .blk_end = c->wb_end, .k = k, .blocks = blocks,
                                .parts = part_buf.as<uint64_t>(), .out = ln ? lu.keys : dst, .sync = Q.sync,
                                .out_rows = Q.out_rows, .claimed = true, .mode = post_mode(true), .e0 = timed ? e0 : nullptr,
-                               .e1 = stop, .s = ls, .qconst = Q.qconst, .filt = c->filt, .sel = c->sel}));
+                               .e1 = stop, .s = ls, .qconst = Q.qconst, .filt = c->filt, .sel = c->sel, .win = c->win_post(),
+                               .totals = c->cur_totals ? c->cur_totals + row : nullptr}));
     // the caller's stream: wait for the lane's launch (its stop event), copy its row out
     if (ln && (rc = lane_end(c, lu, stop, s, dst, k)) != PF_OK) return rc;
     if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
@@ -567,7 +598,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q]->data() + sizeof(pf::QConst));
         vl[q] = pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend);
         // the hand-out is the call's, not a launch's: a class of one query of a batch stays a batch launch
-        pcu[q] = pf::post_blocks_per_cu(vl[q], false, c->filt.fields != 0u, c->sel.on != 0u);
+        pcu[q] = pf::post_blocks_per_cu(vl[q], false, c->filt.fields != 0u, c->sel.on != 0u, c->win.fields != 0u);
         order[q] = q;
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pcu[a] > pcu[b]; });
@@ -586,6 +617,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
     hipEvent_t e0, e1;
     rc = scan_events(c, timed, e0, e1);
     if (rc != PF_OK) return rc;
+    const pf::ScanWindow wpost = c->win_post();
     // one launch per class (timed: the first one's start and the last one's end time the call)
     for (int q0 = 0; q0 < nq;) {
         int q1 = q0;
@@ -596,7 +628,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
                                    .parts = c->d_part.as<uint64_t>() + (size_t)q0 * (blocks + 8) * k, .out = d_keys,
                                    .sync = Q.sync + q0, .out_rows = Q.out_rows + q0, .claimed = false, .mode = post_mode(false),
                                    .e0 = (timed && q0 == 0) ? e0 : nullptr, .e1 = (timed && q1 == nq) ? e1 : nullptr, .s = s,
-                                   .qconst = nullptr, .filt = c->filt, .sel = c->sel}));
+                                   .qconst = nullptr, .filt = c->filt, .sel = c->sel, .win = wpost, .totals = c->cur_totals}));
         q0 = q1;
     }
     if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
@@ -762,7 +794,7 @@ int scan_stream_images(pf_ctx* c, int nq, const std::vector<int32_t>& rows, int 
     HIPCHK(c, pf::launch_scan({.st = c->ds, .pool = d_images, .refs_dev = d_refs, .lds = im.max_lds, .gtab = im.gtab, .nq = nq,
                                .tile_begin = c->tile_begin, .tile_end = c->tile_end, .k = k, .blocks = blocks,
                                .parts = c->d_part.as<uint64_t>(), .out = d_keys, .sync = d_sync, .out_rows = d_rows, .s = s,
-                               .filt = c->filt, .sel = c->sel}));
+                               .filt = c->filt, .sel = c->sel, .win = c->win, .totals = c->cur_totals}));
     if (timed) {
         HIPCHK(c, hipEventRecord(e1, s));
         c->last_ev0 = e0;
@@ -1285,8 +1317,12 @@ static int recommend_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps
                               int32_t* oc) {
     const int32_t nq = (int32_t)ps.size();
     HIPCHK(c, c->d_out.ensure((size_t)nq * topk * sizeof(uint64_t)));
+    CountScope cnt(c, nq);
+    int crc = cnt.begin();
+    if (crc != PF_OK) return crc;
     const size_t chunk = 256;
     for (size_t b = 0; b < ps.size(); b += chunk) {
+        cnt.at(b);
         // a launch's share of a longer call: views of the same arrays
         std::vector<pf::ProfileOwned> part;
         const std::vector<pf::ProfileOwned>* use = &ps;
@@ -1306,7 +1342,7 @@ static int recommend_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
     for (int i = 0; i < nq; ++i) pf_decode_keys(&keys[(size_t)i * topk], topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
-    return PF_OK;
+    return cnt.finish();
 }
 
 static int profile_args(pf_ctx* c, const pf_query_profile* q, int32_t nq, int32_t topk, int32_t* ou, float* os, int32_t* oc) {
@@ -1423,6 +1459,9 @@ int pf_recommend_interest(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk,
         HIPCHK(c, c->d_out.ensure((size_t)nq * topk * sizeof(uint64_t)));
         if ((int)idx.size() < nq)  // rows of unknown users stay empty
             HIPCHK(c, hipMemsetAsync(c->d_out.p, 0xFF, (size_t)nq * topk * sizeof(uint64_t), c->stream));
+        CountScope cnt(c, nq);
+        const int crc = cnt.begin();
+        if (crc != PF_OK) return crc;
         const int chunk = 256;
         for (size_t b = 0; b < idx.size(); b += chunk) {
             std::vector<int32_t> ii(idx.begin() + b, idx.begin() + std::min(idx.size(), b + chunk));
@@ -1435,8 +1474,11 @@ int pf_recommend_interest(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk,
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (!idx.empty() && c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
         for (int i = 0; i < nq; ++i) pf_decode_keys(&keys[(size_t)i * topk], topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
-        return PF_OK;
+        return cnt.finish();
     }
+    if (mode == PF_MODE_ALL && c->win.fields != 0u)
+        return c->fail(PF_EUNSUPP, "scan window: topk above 64 runs in the job pipeline, which reads no window "
+                                   "(page with the cursor instead)");
     // FoF-limited (reference) mode, or ALL with topk beyond the in-kernel bound
     std::vector<pf::Job> jobs(nq);
     for (int i = 0; i < nq; ++i) {
@@ -1666,8 +1708,38 @@ int pf_scan_filter_count(pf_ctx* c, int64_t* n) {
     return PF_OK;
 }
 
+static_assert(PF_WIN_MIN == pf::kWinMin && PF_WIN_AFTER == pf::kWinAfter && PF_WIN_COUNT == pf::kWinCount,
+              "pf_window.h restates the public window bits");
+static_assert(sizeof(pf_scan_window) == 24, "pf_scan_window is 24 B");
+
+int pf_set_scan_window(pf_ctx* c, const pf_scan_window* w) {
+    if (!c) return PF_EINVAL;
+    if (!w || w->fields == 0u) {
+        c->win_pub = pf_scan_window{};
+        c->win = pf::ScanWindow{};
+        return PF_OK;
+    }
+    if ((w->fields & ~pf::kWinAllFields) || w->flags != 0u) return c->fail(PF_EINVAL, "scan window: unknown bits in fields / flags");
+    if ((w->fields & PF_WIN_MIN) && std::isnan(w->min_score)) return c->fail(PF_EINVAL, "scan window: min_score is NaN");
+    if ((w->fields & PF_WIN_AFTER) && std::isnan(w->after_score)) return c->fail(PF_EINVAL, "scan window: after_score is NaN");
+    c->win_pub = *w;
+    c->win = pf::window_make(w->fields, w->min_score, w->after_score, w->after_uid);
+    return PF_OK;
+}
+
+int pf_scan_window_totals(pf_ctx* c, int64_t* out, int32_t cap, int32_t* n) {
+    if (!c) return PF_EINVAL;
+    if (!n || cap < 0 || (cap && !out)) return c->fail(PF_EINVAL, "scan window totals: null argument");
+    if (!c->win_totals_set) return c->fail(PF_EINVAL, "scan window totals: no counted call has run");
+    *n = (int32_t)c->win_totals.size();
+    for (int32_t i = 0; i < std::min(cap, *n); ++i) out[i] = c->win_totals[(size_t)i];
+    return PF_OK;
+}
+
 int pf_scan_keys_async(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, uint64_t* d_keys, void* stream) {
     if (!c || nq < 0 || topk <= 0 || topk > pf::kMaxTopK || (nq && (!q || !d_keys))) return PF_EINVAL;
+    if (c->win.fields & pf::kWinCount)
+        return c->fail(PF_EUNSUPP, "scan window: PF_WIN_COUNT with pf_scan_keys_async (a count needs a synchronous call)");
     (void)hipSetDevice(c->device);
     hipStream_t s = (hipStream_t)stream;  // as given: NULL is the null stream
     std::vector<int32_t> idx, rows;
@@ -1737,7 +1809,7 @@ int pf_scan_bytes(pf_ctx* c, const int32_t* q, int32_t nq, int64_t* out) {
     }
     // workgroups that stage a query's image, as scan_post launches the fitting queries
     const int nwb = c->wb_end - c->wb_begin;
-    const int wgs = nfit == 1 ? one_query_grid(c, pf::post_var_lds(max_tok, max_lists), false, false, true)
+    const int wgs = nfit == 1 ? one_query_grid(c, pf::post_var_lds(max_tok, max_lists), false, false, false, true)
                               : (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg();
     par_jobs((size_t)nq, [&](size_t i) {
         out[i] = kind[i] == 0 ? 0 : (kind[i] == 2 ? k1 : post_query_bytes(c, imgs[i], wgs));

@@ -24,6 +24,7 @@
 #include "pf_batch.h"
 #include "pf_jobs.h"
 #include "pf_store.h"
+#include "pf_window.h"
 #include "pokec_fas.h"
 
 namespace pf {
@@ -233,6 +234,24 @@ struct pf_ctx {
     // field selection of the all-candidates scans (pf_set_scan_select; on == 0: none), in its device
     // form: taken by value like the filter, by every scan launch and every kDjAll chunk's pair stage
     pf::FieldSel sel{};
+    // score window of the all-candidates scans (pf_set_scan_window; fields == 0: none): the public
+    // struct as given (the cursor's score and uid, for K5's idx bound) and its uid-keyed device form,
+    // taken by value like the filter by every scan launch (never by a kDjAll chunk: topk > 64 under a
+    // window is refused).  A counted synchronous call fills win_totals, one value per query.
+    pf_scan_window win_pub{};
+    pf::ScanWindow win{};
+    DBuf d_totals;                       // the counted launches' count words, one per result row
+    std::vector<int64_t> win_totals;     // the last counted call's values (pf_scan_window_totals)
+    bool win_totals_set = false;
+    // K5's form of the window: the cursor's uid turned into the first idx whose uid exceeds it
+    pf::ScanWindow win_post() const {
+        if (!(win.fields & pf::kWinAfter)) return win;
+        const auto it = std::upper_bound(hc.uid.begin(), hc.uid.end(), win_pub.after_uid);
+        return pf::window_for_idx(win, win_pub.after_score, (uint32_t)(it - hc.uid.begin()));
+    }
+    // where the launches of the synchronous call in progress write their counts (row 0 of its current
+    // chunk in d_totals); nullptr outside a counted call
+    uint32_t* cur_totals = nullptr;
     // pinned staging ring for the per-call query upload (a slot is reused only after
     // the copy that read it has completed)
     struct Stage {

@@ -16,6 +16,7 @@
 #include "pf_filter.h"
 #include "pf_select.h"
 #include "pf_types.h"
+#include "pf_window.h"
 
 namespace pf {
 
@@ -87,6 +88,10 @@ struct GroupLaunch {
     hipStream_t s;
     const CandFilter& filt;
     const FieldSel& sel;
+    // the context's score window (pf_window.h; uid-keyed), tested on the aggregate's key in the last
+    // pass; a counted one writes the group's count to totals[0] (device, nullptr otherwise)
+    const ScanWindow& win;
+    uint32_t* totals;
 };
 hipError_t launch_group(const GroupLaunch& L);
 // resident workgroups per CU of a pass's instantiation at its LDS size

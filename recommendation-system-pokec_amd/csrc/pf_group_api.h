@@ -144,7 +144,7 @@ int group_scan(pf_ctx* c, const GroupPlan& P, int agg, int k, uint64_t* d_keys, 
                                     .tile_end = c->tile_end, .k = k, .blocks = blocks[p], .acc = c->d_scores.as<double>(),
                                     .parts = c->d_part.as<uint64_t>(), .out = d_keys,
                                     .sync = reinterpret_cast<pf::ScanSync*>(base + refs_b + offs_b), .s = c->stream,
-                                    .filt = c->filt, .sel = c->sel}));
+                                    .filt = c->filt, .sel = c->sel, .win = c->win, .totals = c->cur_totals}));
     if (timed) {
         HIPCHK(c, hipEventRecord(e1, c->stream));
         c->last_ev0 = e0;
@@ -171,7 +171,11 @@ int pf_recommend_group(pf_ctx* c, const pf_group_query* g, int32_t ng, int32_t t
     if (topk == 0) return PF_OK;
     HIPCHK(c, c->d_out.ensure((size_t)topk * sizeof(uint64_t)));
     std::vector<uint64_t> keys((size_t)topk);
+    CountScope cnt(c, ng);  // a counted window: group i's count in row i (0 for G = 0)
+    const int crc = cnt.begin();
+    if (crc != PF_OK) return crc;
     for (int32_t i = 0; i < ng; ++i) {
+        cnt.at((size_t)i);
         GroupPlan P;
         int rc = group_plan(c, g[i], P);
         if (rc != PF_OK) return rc;
@@ -182,7 +186,7 @@ int pf_recommend_group(pf_ctx* c, const pf_group_query* g, int32_t ng, int32_t t
         if (c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
         pf_decode_keys(keys.data(), topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
     }
-    return PF_OK;
+    return cnt.finish();
 }
 
 int pf_group_scores(pf_ctx* c, const pf_group_query* g, const int32_t* b, int64_t n, const pf_field_select* s, float* out) {

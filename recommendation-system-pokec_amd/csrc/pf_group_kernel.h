@@ -52,7 +52,8 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_group_kernel(DevStore st,
                                                                  double* __restrict__ accbuf,
                                                                  uint64_t* __restrict__ parts,
                                                                  ScanSync* __restrict__ sync,
-                                                                 uint64_t* __restrict__ out, CandFilter F, FieldSel S) {
+                                                                 uint64_t* __restrict__ out, CandFilter F, FieldSel S,
+                                                                 ScanWindow WN, uint32_t* __restrict__ totals) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // stage the pass's images side by side (stage_query's copies, per image)
     for (int i = 0; i < A.nimg; ++i) {
@@ -78,6 +79,7 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_group_kernel(DevStore st,
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint64_t list = ~0ull;
+    uint32_t wcnt = 0u;  // a counted window: the wave's keys in it
     // Static tile hand-out, longest tiles first: band b = tiles [b*W, (b+1)*W), wave w takes one per
     // band, alternating direction.  A slot is owned by one wave per pass, and the stream orders the passes.
     const int W = (int)gridDim.x * (kScanThreads / 64), wid = (int)blockIdx.x * (kScanThreads / 64) + wave;
@@ -144,11 +146,16 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_group_kernel(DevStore st,
             const float f = A.agg == kGroupMean ? (float)(acc / (double)A.n_seeds) : (float)acc;
             if (!excluded<PACKED>(ve, (uint32_t)uid)) key = score_key(f, uid);
         }
+        // the score window (pf_window.h; fields == 0: none), on the aggregate's key
+        if (WN.fields != 0u) {
+            if (!window_pass(key, WN)) key = ~0ull;
+            if (WN.fields & kWinCount) wcnt += (uint32_t)__popcll(__ballot(key != ~0ull));
+        }
         topk_push(list, key, A.k, lane);
     }
     if (!A.last) return;
     post_tail(list, A.k, reinterpret_cast<uint64_t*>(smem + A.hits_off + ((size_t)A.hit_bytes + 4u) * blockDim.x), sync,
-              parts, out, nullptr, 0, (int)blockIdx.x, (int)gridDim.x);
+              parts, out, nullptr, 0, (int)blockIdx.x, (int)gridDim.x, (WN.fields & kWinCount) != 0u, wcnt, totals);
 }
 
 using GroupKernel = decltype(&fas_group_kernel<false, false>);
@@ -160,10 +167,11 @@ static GroupKernel group_kernel(bool packed, bool gtab) {
 
 hipError_t launch_group(const GroupLaunch& L) {
     if (L.pass.nimg <= 0) return hipSuccess;
+    if ((L.win.fields & kWinCount) && !L.totals) return hipErrorInvalidValue;
     const GroupArgs A{L.pass.img0, L.pass.nimg, L.pass.hits_off, L.hit_bytes, L.first ? 1 : 0, L.last ? 1 : 0, L.agg,
                       L.n_seeds, L.excl_img, L.tile_begin, L.tile_end, L.k};
     hipLaunchKernelGGL(group_kernel(L.st.packed, L.pass.gtab), dim3(L.blocks), dim3(kScanThreads), L.pass.lds, L.s, L.st,
-                       L.pool, L.refs_dev, L.off_dev, A, L.acc, L.parts, L.sync, L.out, L.filt, L.sel);
+                       L.pool, L.refs_dev, L.off_dev, A, L.acc, L.parts, L.sync, L.out, L.filt, L.sel, L.win, L.totals);
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 #include "pf_filter.h"
 #include "pf_select.h"
 #include "pf_types.h"
+#include "pf_window.h"
 
 namespace pf {
 
@@ -48,6 +49,10 @@ struct ScanLaunch {
     // by value likewise (on == 0: none): the context's field selection (pf_select.h), applied to
     // each block's staged copy of its query's constants
     const FieldSel& sel;
+    // by value likewise (fields == 0: none): the context's score window (pf_window.h), uid-keyed; a
+    // counted one (kWinCount) writes each query's count to totals[its row] (device, nullptr otherwise)
+    const ScanWindow& win;
+    uint32_t* totals;
 };
 hipError_t launch_scan(const ScanLaunch& L);
 // resident scan blocks per CU at this dynamic LDS size (HIP occupancy API)
@@ -64,6 +69,10 @@ constexpr uint32_t kPostPrune = 1u << 16, kPostPruneStats = 1u << 17, kPostPrune
 constexpr uint32_t kPostFiltKeepBlocks = 1u << 19;
 // dynamic LDS a filtered launch takes on top of post_lds(var_lds): the filter, parked past the query's tables
 constexpr uint32_t kFiltLds = (uint32_t)sizeof(CandFilter);
+static_assert(kFiltLds % 16 == 0, "the window's words follow the filter's");
+// ... and a windowed one: the window, parked past the filter
+constexpr uint32_t kWinLds = 32;
+static_assert(sizeof(ScanWindow) <= kWinLds, "the window's LDS");
 struct PostLaunch {
     const PostStore& ps;
     const uint8_t* pool;
@@ -90,11 +99,16 @@ struct PostLaunch {
     // launch takes the SEL instantiation, which patches its staged copy of the query's constants and
     // leaves the deselected columns and set lists out of its tables.  It needs no LDS of its own.
     const FieldSel& sel;
+    // by value likewise (fields == 0: none): the context's score window (pf_window.h) with its cursor
+    // in idx space (window_for_idx); a windowed launch takes the WIN instantiation and kWinLds bytes.
+    // A counted one (kWinCount) writes each query's count to totals[its row] (device, nullptr otherwise)
+    const ScanWindow& win;
+    uint32_t* totals;
 };
 hipError_t launch_post(const PostLaunch& L);
 // workgroups per CU of the instantiation launch_post takes for `claimed`, `filtered` (a filter is
-// set) and `selected` (a field selection is set)
-int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered, bool selected);
+// set), `selected` (a field selection is set) and `windowed` (a score window is set)
+int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered, bool selected, bool windowed);
 // candidates of idx range [i0, i1) of the postings headers (ps.hdr), or with ps.hdr null of slots
 // [i0, i1) of the tile headers, that pass filt: added to *count (device, zeroed by the caller)
 hipError_t launch_filter_count(const PostStore& ps, const DevStore& st, int32_t i0, int32_t i1, const CandFilter& filt,

@@ -867,10 +867,20 @@ __device__ __forceinline__ uint64_t merge_lists(At at, int nl, int k, uint64_t* 
 // parts: per query (nbx + 8) lists of k keys.  sc: LDS for max(nw * k, 64) keys.  Hand-offs
 // (pf_device.h take_ticket): a list is published with write-through stores drained before the
 // ticket and read with L1-bypassing loads after it.
+// counted (a window with PF_WIN_COUNT, pf_window.h): wcnt is the wave's share of the candidates in the
+// window (K5: the workgroup's, in wave 0).  Its add to the query's count word has returned before the
+// barrier below, hence before the workgroup's ticket, as the last block's histogram record has; the
+// final merger reads the word after the last ticket and writes it to totals[row] before it zeroes the
+// struct.  A launch that does not count passes false and is the code it was.
 __device__ __forceinline__ void post_tail(uint64_t list, int k, uint64_t* sc, ScanSync* __restrict__ sync,
                                           uint64_t* __restrict__ parts, uint64_t* __restrict__ out,
-                                          const int32_t* __restrict__ out_rows, int qy, int bx, int nbx) {
+                                          const int32_t* __restrict__ out_rows, int qy, int bx, int nbx,
+                                          bool counted = false, uint32_t wcnt = 0u, uint32_t* __restrict__ totals = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
+    if (counted && lane == 0 && wcnt != 0u) {
+        const uint32_t old = __hip_atomic_fetch_add(&sync[qy].wcount, wcnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("" ::"v"(old));
+    }
     __syncthreads();
     if (lane < k) sc[wave * k + lane] = list;
     __syncthreads();
@@ -911,6 +921,7 @@ __device__ __forceinline__ void post_tail(uint64_t list, int k, uint64_t* sc, Sc
     const uint64_t fin = merge_lists([&](int w) { return qparts + (size_t)(nbx + w) * k; }, ng, k, sc, lane);
     const int row = out_rows ? out_rows[qy] : qy;
     if (lane < k) out[(size_t)row * k + lane] = fin;
+    if (counted && lane == 0) totals[row] = __hip_atomic_load(&sy->wcount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // the query's rendezvous left zeroed for the next launch that uses it (a one-query launch from
     // the resident images reuses its lane's ScanSync with no upload): every workgroup of the query
     // took its group ticket after its last block claim, and every group its done ticket, so nothing
@@ -927,13 +938,14 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_scan_kernel(DevStore st, 
                                                                 ScanSync* __restrict__ sync,
                                                                 uint64_t* __restrict__ out,
                                                                 const int32_t* __restrict__ out_rows, CandFilter F,
-                                                                FieldSel S) {
+                                                                FieldSel S, ScanWindow WN, uint32_t* __restrict__ totals) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const QImageRef r = refs[blockIdx.y];
     char* scratch;
     const QView v = stage_query<GTAB>(smem, pool, r, &scratch, S);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint64_t list = ~0ull;
+    uint32_t wcnt = 0u;  // a counted window: the wave's keys in it
     // Tile hand-out, longest tiles first.  Static zig-zag for all but the last two bands
     // (band b = tiles [b*W, (b+1)*W) holds W near-equal tiles; wave w takes one per band,
     // alternating direction), then the tail from per-XCD counters, so waves that drew
@@ -1001,10 +1013,15 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_scan_kernel(DevStore st, 
             const int32_t uid = (int32_t)h1.w;
             if (!excluded<PACKED>(v, (uint32_t)uid)) key = score_key(f, uid);
         }
+        // the score window (pf_window.h; fields == 0: none): a key outside it is no key
+        if (WN.fields != 0u) {
+            if (!window_pass(key, WN)) key = ~0ull;
+            if (WN.fields & kWinCount) wcnt += (uint32_t)__popcll(__ballot(key != ~0ull));
+        }
         topk_push(list, key, k, lane);
     }
     post_tail(list, k, reinterpret_cast<uint64_t*>(scratch), sync, parts, out,
-              out_rows, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x);
+              out_rows, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, (WN.fields & kWinCount) != 0u, wcnt, totals);
 }
 
 // ---------------------------------------------------------------- K5: postings scan
@@ -1306,14 +1323,24 @@ static __device__ __attribute__((noinline)) uint32_t prune_derive(ScanSync* sy, 
 // block's prefix (no entry is walked, no round is planned for them), and the deselected club /
 // friend lists are left out of the set lists.  S is read during staging only: nothing of it lives
 // through the block loop.  <XD, FILT, false> never reads S and is the code it was without it.
-template <bool XD, bool FILT, bool SEL>
+// WIN: the context has a score window (pf_window.h, W with its cursor in idx space; launch_post picks
+// the instantiation).  A key outside the window becomes ~0 before the lane's 2-key sort: it is never
+// pushed, never in `best` and never folded into the histogram, so "only keyed candidates are
+// recorded" (pf_prune.h) holds and theta stays valid under a cursor.  A floor seeds every block's
+// theta with W.theta0, valid before the first block: the bound drops only candidates strictly below
+// theta, so nobody at or above the floor dies, and the exact >= min_score test is the key's.  A
+// counted launch keeps theta at the seed (no record, no derive: candidates between the floor and a
+// risen theta would be dropped uncounted), counts its in-window keys into misc[6] and hands the sum
+// to post_tail.  W's words are parked in LDS past the filter's, like the filter.  <XD, FILT, SEL,
+// false> never reads W and is the code it was without it.
+template <bool XD, bool FILT, bool SEL, bool WIN>
 __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(PostStore ps, const uint8_t* __restrict__ pool,
                                                               const uint32_t* __restrict__ img_off, int32_t blk_begin,
                                                               int32_t blk_end, int32_t k, uint64_t* __restrict__ parts,
                                                               ScanSync* __restrict__ sync, uint64_t* __restrict__ out,
                                                               const int32_t* __restrict__ out_rows, uint32_t mode,
                                                               const uint8_t* __restrict__ qconst, CandFilter F,
-                                                              FieldSel S) {
+                                                              FieldSel S, ScanWindow W, uint32_t* __restrict__ totals) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int qy = XD ? 0 : (int)blockIdx.y;
     const int bx = (int)blockIdx.x;
@@ -1391,6 +1418,11 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         smem + (((uint32_t)(reinterpret_cast<char*>(colof) + H.n_tok - smem) + 15u) & ~15u));
     if constexpr (FILT) {
         if (tid == 0) *fl = F;
+    }
+    // the window's words, in the kWinLds bytes a windowed launch allocates past the filter's
+    const ScanWindow* wl = reinterpret_cast<const ScanWindow*>(reinterpret_cast<char*>(fl) + (FILT ? kFiltLds : 0u));
+    if constexpr (WIN) {
+        if (tid == 0) *const_cast<ScanWindow*>(wl) = W;
     }
     if (tid < 16) misc[tid] = 0u;
     stage(smem, qcp, sizeof(QConst));
@@ -1507,6 +1539,9 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
         // the threshold as of now (only ever raised: a stale value prunes less), with the headers' loads
         uint32_t thb = 0u;
         if (prune) thb = __hip_atomic_load(&sync[qy].theta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (WIN) {  // a floor's seed: no block begins cold (published by the staging barrier)
+            if (prune) thb = max(thb, wl->theta0);
+        }
 #pragma unroll 1  // (unrolled by two, its second lane set's masks and trip count lived through the block loop)
         for (int j = tid; j < nl; j += kPostThreads)
             rng[j] = list_range(ps, j < H.n_tok ? toks[j].l : sets[j - H.n_tok], c0, c1);
@@ -1981,8 +2016,17 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 const float f = fas_score(sum[kk], uk, ftab[uk]);  // (double)uk / (double)(kNumFixed + q.n_cols)
                 // keyed by idx (idx order = uid order); uids are filled in before the merge
                 key = score_key(f, (int32_t)(c0 + kk * kPostThreads + tid));
+                if constexpr (WIN) {
+                    if (!window_pass(key, *wl)) key = ~0ull;
+                }
             }
             keys[kk] = key;
+        }
+        if constexpr (WIN) {
+            if (wl->fields & kWinCount) {  // the wave's keys in the window, one LDS add
+                const uint32_t nin = (uint32_t)__popcll(__ballot(keys[0] != ~0ull)) + (uint32_t)__popcll(__ballot(keys[1] != ~0ull));
+                if (lane == 0 && nin != 0u) atomicAdd(&misc[6], nin);
+            }
         }
         // the lane's 2 keys ascending, then pushed best-first: after the first push the
         // wave's threshold rejects most of the rest
@@ -1991,7 +2035,8 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
 #pragma unroll
         for (int kk = 0; kk < kCandsPerThread; ++kk) topk_push(best, keys[kk], k, lane);
         // 6. the block's best survivor becomes the workgroup's record (sent at the next block's start)
-        if (prune) prune_fold(&misc[5], best, k, c0, c1, misc[4], lane);
+        // (a counted launch records nothing: its theta stays at the window's seed)
+        if (prune && !(WIN && (wl->fields & kWinCount))) prune_fold(&misc[5], best, k, c0, c1, misc[4], lane);
         K5T(12);
 #ifdef PF_K5_BLOCKLOG
         if (tid == 0) {
@@ -2035,7 +2080,14 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
     // tail scratch in the (idle) slots: merge keys, then flag / threshold / block ids
     uint64_t* sc = reinterpret_cast<uint64_t*>(slot);
 
-    post_tail(best, k, sc, sync, parts, out, out_rows, qy, bx, nbx);
+    if constexpr (WIN) {
+        // misc[6] is complete: its adds came before each block's closing barrier.  (The tail's scratch is
+        // the slots, not misc.)
+        const bool counted = (wl->fields & kWinCount) != 0u;
+        post_tail(best, k, sc, sync, parts, out, out_rows, qy, bx, nbx, counted, tid == 0 ? misc[6] : 0u, totals);
+    } else {
+        post_tail(best, k, sc, sync, parts, out, out_rows, qy, bx, nbx);
+    }
 }
 
 // ---------------------------------------------------------------- K2: merge
@@ -2197,19 +2249,23 @@ static PairsKernel pairs_kernel(bool packed, bool gtab) {
                                               {fas_pairs_kernel<true, false>, fas_pairs_kernel<true, true>}};
     return tab[packed][gtab];
 }
-using PostKernel = decltype(&fas_post_kernel<false, false, false>);
-static PostKernel post_kernel(bool claimed, bool filtered, bool selected) {
-    static constexpr PostKernel tab[2][2][2] = {{{fas_post_kernel<false, false, false>, fas_post_kernel<false, false, true>},
-                                                 {fas_post_kernel<false, true, false>, fas_post_kernel<false, true, true>}},
-                                                {{fas_post_kernel<true, false, false>, fas_post_kernel<true, false, true>},
-                                                 {fas_post_kernel<true, true, false>, fas_post_kernel<true, true, true>}}};
-    return tab[claimed][filtered][selected];
+using PostKernel = decltype(&fas_post_kernel<false, false, false, false>);
+static PostKernel post_kernel(bool claimed, bool filtered, bool selected, bool windowed) {
+#define PF_POST_ROW(XD, FILT, SEL) {fas_post_kernel<XD, FILT, SEL, false>, fas_post_kernel<XD, FILT, SEL, true>}
+    static constexpr PostKernel tab[2][2][2][2] = {
+        {{PF_POST_ROW(false, false, false), PF_POST_ROW(false, false, true)},
+         {PF_POST_ROW(false, true, false), PF_POST_ROW(false, true, true)}},
+        {{PF_POST_ROW(true, false, false), PF_POST_ROW(true, false, true)},
+         {PF_POST_ROW(true, true, false), PF_POST_ROW(true, true, true)}}};
+#undef PF_POST_ROW
+    return tab[claimed][filtered][selected][windowed];
 }
 
 hipError_t launch_scan(const ScanLaunch& L) {
     if (L.nq <= 0) return hipSuccess;
+    if ((L.win.fields & kWinCount) && !L.totals) return hipErrorInvalidValue;
     hipLaunchKernelGGL(scan_kernel(L.st.packed, L.gtab), dim3(L.blocks, L.nq), dim3(kScanThreads), L.lds, L.s, L.st, L.pool,
-                       L.refs_dev, L.tile_begin, L.tile_end, L.k, L.parts, L.sync, L.out, L.out_rows, L.filt, L.sel);
+                       L.refs_dev, L.tile_begin, L.tile_end, L.k, L.parts, L.sync, L.out, L.out_rows, L.filt, L.sel, L.win, L.totals);
     return hipGetLastError();
 }
 
@@ -2283,13 +2339,15 @@ hipError_t launch_post(const PostLaunch& L) {
     if (L.nq <= 0) return hipSuccess;
     // the claimed hand-out is the one-query instantiation's and nobody else's
     if (L.claimed && L.nq != 1) return hipErrorInvalidValue;
-    const uint32_t lds = post_lds(L.var_lds) + (L.filt.fields ? kFiltLds : 0u);  // + the filter's words (fas_post_kernel)
+    if ((L.win.fields & kWinCount) && !L.totals) return hipErrorInvalidValue;
+    // + the filter's and the window's words (fas_post_kernel)
+    const uint32_t lds = post_lds(L.var_lds) + (L.filt.fields ? kFiltLds : 0u) + (L.win.fields ? kWinLds : 0u);
     // timed launches (e0, e1 given): the kernel's own start and end timestamps, taken from its
     // dispatch (hipExtLaunchKernelGGL), instead of two marker packets around it.  The filter and the field
     // selection travel in the launch's own arguments: a later pf_set_scan_filter / _select does not reach them
-    hipExtLaunchKernelGGL(post_kernel(L.claimed, L.filt.fields != 0u, L.sel.on != 0u), dim3(L.blocks, L.nq), dim3(kPostThreads),
+    hipExtLaunchKernelGGL(post_kernel(L.claimed, L.filt.fields != 0u, L.sel.on != 0u, L.win.fields != 0u), dim3(L.blocks, L.nq), dim3(kPostThreads),
                           lds, L.s, L.e0, L.e1, 0u, L.ps, L.pool, L.img_off, L.blk_begin, L.blk_end, L.k, L.parts, L.sync, L.out,
-                          L.out_rows, L.mode, L.qconst, L.filt, L.sel);
+                          L.out_rows, L.mode, L.qconst, L.filt, L.sel, L.win, L.totals);
 #ifdef PF_K5_BLOCKLOG
     {
         static int calls = 0;
@@ -2330,16 +2388,16 @@ hipError_t k5_prune_stats_read(unsigned long long* out, bool reset) {
     return e;
 }
 
-int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered, bool selected) {
+int post_blocks_per_cu(uint32_t var_lds, bool claimed, bool filtered, bool selected, bool windowed) {
     // per thread, by instantiation (the one launch_post takes for `claimed`, the filter and the
     // selection) and LDS bytes (a batch asks once per query: the occupancy API once per size)
-    static thread_local std::unordered_map<uint32_t, int> memos[8];
-    auto& memo = memos[4 * (int)selected + 2 * (int)filtered + (int)claimed];
+    static thread_local std::unordered_map<uint32_t, int> memos[16];
+    auto& memo = memos[8 * (int)windowed + 4 * (int)selected + 2 * (int)filtered + (int)claimed];
     auto it = memo.find(var_lds);
     if (it != memo.end()) return it->second;
     int nb = 0;
-    const size_t lds = post_lds(var_lds) + (filtered ? kFiltLds : 0u);
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, post_kernel(claimed, filtered, selected), kPostThreads, lds);
+    const size_t lds = post_lds(var_lds) + (filtered ? kFiltLds : 0u) + (windowed ? kWinLds : 0u);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, post_kernel(claimed, filtered, selected, windowed), kPostThreads, lds);
     nb =(e == hipSuccess && nb > 0) ? nb : 1;
     if (memo.size() > 4096) memo.clear();
     memo.emplace(var_lds, nb);

@@ -153,7 +153,10 @@ struct ScanSync {
     // K5's pruning threshold (pf_prune.h): the float bits of theta, only ever raised, and the
     // score histogram it is derived from (kPruneBins bins, padded to whole 16-B lines)
     unsigned int theta;
-    unsigned int pad1[15];
+    // a counted launch's candidates in the window (pf_window.h): one add per wave or workgroup before
+    // its ticket, written out by post_tail's final merger
+    unsigned int wcount;
+    unsigned int pad1[14];
     unsigned int hist[784];
 };
 static_assert(sizeof(ScanSync) % 16 == 0, "post_tail zeroes ScanSync in 16-B stores");

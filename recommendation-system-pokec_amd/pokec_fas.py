@@ -8,6 +8,7 @@ empty list (recommender_graph.cpp:36-40), results are [(id, score)] sorted by
 `make -C recommendation-system-pokec_amd`); if it or a gfx950 GPU is missing, opening
 an engine raises — there is no CPU fallback.
 """
+import contextlib
 import ctypes
 import os
 
@@ -27,6 +28,8 @@ PF_FILT_KEEP_MISSING = 1
 # field selection of the all-candidates scans (pf_field_select): bit k of `fixed` = PF_F_*
 PF_F_PUBLIC, PF_F_GENDER, PF_F_COMPLETION, PF_F_AGE, PF_F_REGION, PF_F_CLUBS, PF_F_FRIENDS = range(7)
 PF_SEL_FIXED_ALL = 0x7F
+# score window of the all-candidates scans (pf_scan_window)
+PF_WIN_MIN, PF_WIN_AFTER, PF_WIN_COUNT = 1, 2, 4
 FIXED_FIELD_NAMES = ("public", "gender", "completion", "age", "region", "clubs", "friends")
 
 # every entry point of include/pokec_fas.h
@@ -40,7 +43,8 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_num_cols", "pf_fas_pairs_terms", "pf_recommend_interest_all_terms",
            "pf_recommend_interest_profile", "pf_fas_profile_pairs", "pf_fas_profile_pairs_terms",
            "pf_recommend_interest_profile_terms",
-           "pf_recommend_group", "pf_group_scores", "pf_group_plan_of", "pf_group_image_lds"]
+           "pf_recommend_group", "pf_group_scores", "pf_group_plan_of", "pf_group_image_lds",
+           "pf_set_scan_window", "pf_scan_window_totals"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
               "pf_dataset_profile_order", "pf_dataset_adj_order", "pf_dataset_profile_json", "pf_dataset_club_name",
@@ -136,6 +140,54 @@ class FieldSelect(ctypes.Structure):
         g = FieldSelect()
         ctypes.memmove(ctypes.byref(g), ctypes.byref(self), ctypes.sizeof(FieldSelect))
         return g
+
+
+class ScanWindow(ctypes.Structure):
+    """pf_scan_window: which part of the ranked order the all-candidates scans return.  A floor
+    (min_score), a paging cursor (after_score, after_uid: results rank strictly after it) and a
+    count of the candidates in the window.  ScanWindow.make(...) builds one from keyword arguments."""
+    _fields_ = [("fields", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("min_score", ctypes.c_float),
+                ("after_score", ctypes.c_float), ("after_uid", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+    @classmethod
+    def make(cls, min_score=None, after=None, count=False):
+        """min_score: rank only candidates scoring >= it; after: (score, uid) of the last result of
+        the page before (any position will do: it need not be a member); count: also count the
+        candidates in the window (FasEngine.scan_window_totals)."""
+        w = cls()
+        if min_score is not None:
+            w.fields |= PF_WIN_MIN
+            w.min_score = float(np.float32(min_score))
+        if after is not None:
+            w.fields |= PF_WIN_AFTER
+            w.after_score = float(np.float32(after[0]))
+            w.after_uid = int(after[1])
+        if count:
+            w.fields |= PF_WIN_COUNT
+        return w
+
+    def copy(self):
+        g = ScanWindow()
+        ctypes.memmove(ctypes.byref(g), ctypes.byref(self), ctypes.sizeof(ScanWindow))
+        return g
+
+
+def pages(call, k, window=None):
+    """Page through a ranking: call(k, window) -> (ids, scores) is asked for page after page, each
+    with the cursor set to the page before's last result (on top of `window`'s floor and count),
+    until a page comes back short.  Yields each non-empty page.  Example:
+        for ids, scores in pages(lambda k, w: eng.recommend_interest_all([u], k, window=w)[0], 64): ..."""
+    w = ScanWindow() if window is None else window.copy()
+    while True:
+        ids, scores = call(k, w if w.fields else None)[:2]
+        if len(ids):
+            yield ids, scores
+        if len(ids) < k or k <= 0:
+            return
+        w = w.copy()
+        w.fields |= PF_WIN_AFTER
+        w.after_score = float(scores[-1])
+        w.after_uid = int(ids[-1])
 
 
 class PairTermsHead(ctypes.Structure):
@@ -362,6 +414,8 @@ def lib():
         L.pf_group_scores.argtypes = [V, ctypes.POINTER(GroupQuery), V, I64, ctypes.POINTER(FieldSelect), V]
         L.pf_group_plan_of.argtypes = [V, ctypes.POINTER(GroupQuery), ctypes.POINTER(GroupPlan)]
         L.pf_group_image_lds.argtypes = [V, ctypes.POINTER(GroupQuery), V, I32]
+        L.pf_set_scan_window.argtypes = [V, ctypes.POINTER(ScanWindow)]
+        L.pf_scan_window_totals.argtypes = [V, V, I32, ctypes.POINTER(I32)]
         L.pf_merge_keys_async.argtypes = [V, V, I32, I32, I32, V, V]
         L.pf_decode_keys.argtypes = [V, I32, V, V, V]
         L.pf_decode_keys.restype = None
@@ -421,6 +475,7 @@ class FasEngine:
         self._inflight = {}
         self._filter = None  # the candidate filter in force (a CandFilter copy), None = none
         self._select = None  # the field selection in force (a FieldSelect copy), None = none
+        self._window = None  # the score window in force (a ScanWindow copy), None = none
         rc = L.pf_open(desc_ptr, device, ctypes.byref(self.h))
         if rc != PF_OK:
             raise FasError(f"pf_open failed ({rc}): {L.pf_last_error(None).decode()}")
@@ -573,38 +628,37 @@ class FasEngine:
     recommend_friends_by_interest = recommend_graph_registration
     recommend_friends_collab = recommend_collaborative
 
-    def recommend_interest_all(self, users, topk, filter=None, select=None, explain=False):
-        """All-candidates interest scan (SURVEY A13).  filter (a CandFilter): rank only the candidates
-        that pass it; select (a FieldSelect): score over the selected fields only.  The filter and the
-        selection in force before the call are restored afterwards.  explain: each result is
-        (ids, scores, PairTerms), the breakdown of every listed score (one more launch and copy)."""
-        if explain:
-            prev, prev_sel = self._filter, self._select
-            try:
-                if filter is not None:
-                    self.set_scan_filter(filter)
-                if select is not None:
-                    self.set_scan_select(select)
-                return self._topk_terms(users, topk)
-            finally:
-                if filter is not None:
-                    self.set_scan_filter(prev)
-                if select is not None:
-                    self.set_scan_select(prev_sel)
-        if filter is None and select is None:
-            return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
-        prev, prev_sel = self._filter, self._select
+    @contextlib.contextmanager
+    def _scoped(self, filter=None, select=None, window=None):
+        """Set the given filter / selection / window for one call; those in force before it are
+        restored afterwards."""
+        prev, prev_sel, prev_win = self._filter, self._select, self._window
         try:
             if filter is not None:
                 self.set_scan_filter(filter)
             if select is not None:
                 self.set_scan_select(select)
-            return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
+            if window is not None:
+                self.set_scan_window(window)
+            yield
         finally:
             if filter is not None:
                 self.set_scan_filter(prev)
             if select is not None:
                 self.set_scan_select(prev_sel)
+            if window is not None:
+                self.set_scan_window(prev_win)
+
+    def recommend_interest_all(self, users, topk, filter=None, select=None, explain=False, window=None):
+        """All-candidates interest scan (SURVEY A13).  filter (a CandFilter): rank only the candidates
+        that pass it; select (a FieldSelect): score over the selected fields only; window (a
+        ScanWindow): a floor, a paging cursor and a count (scan_window_totals).  The filter, the
+        selection and the window in force before the call are restored afterwards.  explain: each
+        result is (ids, scores, PairTerms), the breakdown of every listed score (one more launch and copy)."""
+        with self._scoped(filter, select, window):
+            if explain:
+                return self._topk_terms(users, topk)
+            return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
 
     # -- query by profile (pf_query_profile): a person who is not a user of the corpus
     def _profile_array(self, profiles):
@@ -634,23 +688,14 @@ class FasEngine:
         return [(ou[i * k:i * k + oc[i]].copy(), os_[i * k:i * k + oc[i]].copy(),
                  PairTerms(head[i * k:i * k + oc[i]], terms[i * k:i * k + oc[i]].copy())) for i in range(n)]
 
-    def recommend_profile(self, profiles, k, filter=None, select=None, explain=False):
+    def recommend_profile(self, profiles, k, filter=None, select=None, explain=False, window=None):
         """The all-candidates top-k of each QueryProfile (one, or a list: one call), for people who are
-        not users of the corpus.  filter / select / explain as in recommend_interest_all: the filter and
-        selection in force before the call are restored afterwards.  A profile's exclusions are its own
-        `exclude` list and nothing else."""
-        prev, prev_sel = self._filter, self._select
-        try:
-            if filter is not None:
-                self.set_scan_filter(filter)
-            if select is not None:
-                self.set_scan_select(select)
+        not users of the corpus.  filter / select / explain / window as in recommend_interest_all: the
+        filter, selection and window in force before the call are restored afterwards (the window's
+        cursor is the way past result 64).  A profile's exclusions are its own `exclude` list and
+        nothing else."""
+        with self._scoped(filter, select, window):
             return self._recommend_profile(profiles, k, explain)
-        finally:
-            if filter is not None:
-                self.set_scan_filter(prev)
-            if select is not None:
-                self.set_scan_select(prev_sel)
 
     def fas_profile_pairs(self, profile, b_uid, select=None):
         """FAS(A = the QueryProfile, B = each stored b_uid); NaN for an unknown b_uid."""
@@ -675,29 +720,19 @@ class FasEngine:
         return PairTerms(head, terms)
 
     # -- group query (pf_group_query): who is similar to a set of seed users
-    def recommend_group(self, seeds, k, agg="mean", exclude=(), exclude_adj=False, filter=None, select=None):
+    def recommend_group(self, seeds, k, agg="mean", exclude=(), exclude_adj=False, filter=None, select=None, window=None):
         """The top-k users most similar to the seed users as a group: (ids, scores).  agg: "mean",
         "min" (similar to every seed) or "max" (similar to any seed).  The seeds and `exclude` are
-        never returned; exclude_adj also drops every seed's adj_list row.  filter / select as in
-        recommend_interest_all: those in force before the call are restored afterwards."""
+        never returned; exclude_adj also drops every seed's adj_list row.  filter / select / window as
+        in recommend_interest_all: those in force before the call are restored afterwards."""
         g = GroupQuery.make(seeds, agg, exclude, exclude_adj)
         k = max(int(k), 0)
         ou = np.zeros(max(k, 1), np.int32)
         os_ = np.zeros(max(k, 1), np.float32)
         oc = np.zeros(1, np.int32)
-        prev, prev_sel = self._filter, self._select
-        try:
-            if filter is not None:
-                self.set_scan_filter(filter)
-            if select is not None:
-                self.set_scan_select(select)
+        with self._scoped(filter, select, window):
             self._check(self._L.pf_recommend_group(self.h, ctypes.byref(g), 1, k, ou.ctypes.data, os_.ctypes.data,
                                                    oc.ctypes.data), "pf_recommend_group")
-        finally:
-            if filter is not None:
-                self.set_scan_filter(prev)
-            if select is not None:
-                self.set_scan_select(prev_sel)
         return ou[:oc[0]].copy(), os_[:oc[0]].copy()
 
     def group_scores(self, seeds, b_uid, agg="mean", select=None):
@@ -779,6 +814,30 @@ class FasEngine:
 
     def clear_scan_select(self):
         self.set_scan_select(None)
+
+    # -- score window of the all-candidates scans (pf_set_scan_window): context state like the filter
+    def set_scan_window(self, window=None, **kw):
+        """Set the window (a ScanWindow, or ScanWindow.make's keyword arguments); None clears it."""
+        if window is None and kw:
+            window = ScanWindow.make(**kw)
+        if window is None or window.fields == 0:
+            self._check(self._L.pf_set_scan_window(self.h, None), "pf_set_scan_window")
+            self._window = None
+            return
+        self._check(self._L.pf_set_scan_window(self.h, ctypes.byref(window)), "pf_set_scan_window")
+        self._window = window.copy()
+
+    def clear_scan_window(self):
+        self.set_scan_window(None)
+
+    def scan_window_totals(self):
+        """Per query of the last counted scan call (a window with count=True): the candidates of this
+        context's shard in the window, as an int64 array."""
+        n = ctypes.c_int32()
+        self._check(self._L.pf_scan_window_totals(self.h, None, 0, ctypes.byref(n)), "pf_scan_window_totals")
+        out = np.zeros(max(n.value, 1), np.int64)
+        self._check(self._L.pf_scan_window_totals(self.h, out.ctypes.data, n.value, ctypes.byref(n)), "pf_scan_window_totals")
+        return out[:n.value].copy()
 
     def scan_filter_count(self):
         """Candidates of this context's shard that pass the filter in force (all without one)."""
