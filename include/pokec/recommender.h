@@ -62,6 +62,7 @@
 #include <list>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -432,6 +433,34 @@ public:
         const pf_scan_window w = window.c_form();
         return for_group_(seeds, topk, agg, exclude_adj, exclude, &w, total);
     }
+    // Collect (pokec_fas.h "Collect"): EVERY candidate of the window, ranked (score desc, uid asc), in
+    // one scan and one device sort: everyone at least this similar to a user, to a profile given by
+    // value, or to a group (its look-alike audience).  window: a floor, a cursor or neither (everybody
+    // rankable); cap: the most entries the caller will take.  A window that holds more than cap throws
+    // std::length_error (its what() names the total: raise the floor or the cap); any other failure
+    // returns an empty list and last_error says why.  The engine's collector is set for this call and
+    // cleared afterwards, under the engine's lock.
+    Ranked collect_interest_all(int user, const ScoreWindow& window = ScoreWindow(), int64_t cap = 1 << 20) const {
+        const pf_scan_window w = window.c_form();
+        Collect col{cap};
+        run_(3, user, 1, 0, nullptr, nullptr, &w, nullptr, &col);
+        return col.take();
+    }
+    Ranked collect_by_profile(const Profile& A, const ScoreWindow& window = ScoreWindow(), int64_t cap = 1 << 20,
+                              const std::vector<int>& exclude = {}) const {
+        const pf_scan_window w = window.c_form();
+        Collect col{cap};
+        by_profile_(A, 1, exclude, &w, nullptr, &col);
+        return col.take();
+    }
+    Ranked collect_for_group(const std::vector<int>& seeds, GroupAgg agg = GroupAgg::Mean, const ScoreWindow& window = ScoreWindow(),
+                             int64_t cap = 1 << 20, bool exclude_adj = false, const std::vector<int>& exclude = {}) const {
+        const pf_scan_window w = window.c_form();
+        Collect col{cap};
+        for_group_(seeds, 1, agg, exclude_adj, exclude, &w, nullptr, &col);
+        return col.take();
+    }
+
     // The group's aggregate score of B, a profile of the map (NaN when B or every seed is not): how
     // well B fits the group.  No exclusion applies: a seed is scored like anyone else.
     float group_similarity(const std::vector<int>& seeds, const Profile& B, GroupAgg agg = GroupAgg::Mean) const {
@@ -493,8 +522,45 @@ private:
         }
     };
 
+    // A collecting call's request and result: the engine's collector for the span of one call (set by
+    // begin, cleared by end: the facade keeps none in force between calls), then the whole window.
+    struct Collect {
+        int64_t cap;
+        Ranked all;
+        int64_t total = 0;
+        bool overflow = false;
+        pf_ctx* ctx = nullptr;
+        explicit Collect(int64_t c) : cap(c) {}
+        int begin(pf_ctx* c) {
+            const int rc = pf_set_scan_collect(c, cap > 0 ? cap : -1);
+            if (rc == PF_OK) ctx = c;
+            return rc;
+        }
+        // after the call: clears the collector and, when the call succeeded, reads its result
+        int end(int rc) {
+            if (!ctx) return rc;
+            (void)pf_set_scan_collect(ctx, 0);
+            if (rc != PF_OK) return rc;
+            int64_t n = 0;
+            if ((rc = pf_scan_collected(ctx, nullptr, nullptr, 0, &n, &total)) != PF_OK) return rc;
+            overflow = total > cap;
+            std::vector<int32_t> ids((size_t)n);
+            std::vector<float> sc((size_t)n);
+            if (n && (rc = pf_scan_collected(ctx, ids.data(), sc.data(), n, &n, &total)) != PF_OK) return rc;
+            all.reserve((size_t)n);
+            for (int64_t i = 0; i < n; ++i) all.emplace_back(ids[(size_t)i], sc[(size_t)i]);
+            return PF_OK;
+        }
+        Ranked take() {
+            if (overflow)
+                throw std::length_error("collect: the window holds " + std::to_string(total) + " candidates, above the cap of " +
+                                        std::to_string(cap));
+            return std::move(all);
+        }
+    };
+
     Ranked by_profile_(const Profile& A, int topk, const std::vector<int>& exclude, const pf_scan_window* window,
-                       int64_t* total) const {
+                       int64_t* total, Collect* col = nullptr) const {
         Ranked out;
         if (!profiles || topk <= 0) return out;
         std::shared_ptr<detail::Engine> e = engine_();
@@ -507,15 +573,18 @@ private:
         std::vector<float> sc((size_t)topk);
         int32_t n = 0;
         WindowScope ws(e->ctx, window);
-        if (ws.rc != PF_OK || pf_recommend_interest_profile(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n) != PF_OK)
-            return fail_(e->ctx, out);
+        int rc = ws.rc;
+        if (rc == PF_OK && col) rc = col->begin(e->ctx);
+        if (rc == PF_OK) rc = pf_recommend_interest_profile(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n);
+        if (col) rc = col->end(rc);
+        if (rc != PF_OK) return fail_(e->ctx, out);
         if (!ws.total(total)) return fail_(e->ctx, out);
         for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
         return out;
     }
 
     Ranked for_group_(const std::vector<int>& seeds, int topk, GroupAgg agg, bool exclude_adj, const std::vector<int>& exclude,
-                      const pf_scan_window* window, int64_t* total) const {
+                      const pf_scan_window* window, int64_t* total, Collect* col = nullptr) const {
         Ranked out;
         if (!profiles || topk <= 0 || seeds.empty()) return out;
         std::shared_ptr<detail::Engine> e = engine_();
@@ -531,14 +600,19 @@ private:
         std::vector<float> sc((size_t)topk);
         int32_t n = 0;
         WindowScope ws(e->ctx, window);
-        if (ws.rc != PF_OK || pf_recommend_group(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n) != PF_OK) return fail_(e->ctx, out);
+        int rc = ws.rc;
+        if (rc == PF_OK && col) rc = col->begin(e->ctx);
+        if (rc == PF_OK) rc = pf_recommend_group(e->ctx, &q, 1, topk, ids.data(), sc.data(), &n);
+        if (col) rc = col->end(rc);
+        if (rc != PF_OK) return fail_(e->ctx, out);
         if (!ws.total(total)) return fail_(e->ctx, out);
         for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
         return out;
     }
 
     Ranked run_(int kind, int user, int topk, int limit, const pf_cand_filter* filter = nullptr,
-                const pf_field_select* select = nullptr, const pf_scan_window* window = nullptr, int64_t* total = nullptr) const {
+                const pf_field_select* select = nullptr, const pf_scan_window* window = nullptr, int64_t* total = nullptr,
+                Collect* col = nullptr) const {
         Ranked out;
         if (!profiles || !adj_list || topk <= 0) return out;
         std::shared_ptr<detail::Engine> e = engine_();
@@ -568,7 +642,9 @@ private:
                 {
                     WindowScope ws(e->ctx, rc == PF_OK ? window : nullptr);
                     if (rc == PF_OK) rc = ws.rc;
+                    if (rc == PF_OK && col) rc = col->begin(e->ctx);
                     if (rc == PF_OK) rc = pf_recommend_interest(e->ctx, &q, 1, topk, PF_MODE_ALL, 0, ids.data(), sc.data(), &n);
+                    if (col) rc = col->end(rc);
                     if (rc == PF_OK && !ws.total(total)) rc = PF_EINTERNAL;
                 }
                 if (filter) {  // the filter in force before the call

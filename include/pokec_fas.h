@@ -503,6 +503,44 @@ int pf_set_scan_window(pf_ctx* ctx, const pf_scan_window* window);
 int pf_scan_window_totals(pf_ctx* ctx, int64_t* out, int32_t cap, int32_t* n);
 
 /*
+ * Collect: every candidate of the score window in one pass.  With a collector in force a scan call
+ * also keeps the whole set PF_WIN_COUNT counts, ranked, next to its own top-k: the look-alike audience
+ * of a group, the near-duplicates of a profile, everyone above a floor inside a filter, in one scan
+ * plus one sort of the matches instead of one scan per 64 results.
+ *   Which calls  The synchronous pf_recommend_interest under PF_MODE_ALL with topk <= 64,
+ *                pf_recommend_interest_profile, pf_recommend_group and their _terms forms, with nq (ng)
+ *                == 1 and topk > 0 (topk = 0 scans nothing and collects nothing).  Refused with
+ *                PF_EUNSUPP (pf_last_error says "collect"): nq or ng above 1, pf_scan_keys_async, topk >
+ *                64 on PF_MODE_ALL.  FoF interest, collab, clubs, the pair calls, pf_group_scores and the
+ *                hold-out drivers never see it.
+ *   The set      Exactly the candidates PF_WIN_COUNT counts: in the shard, passing the filter, not
+ *                excluded, in the window in force; with no window every rankable candidate.  Each comes
+ *                with its uid and its float score, bit for bit what the top-k reports.
+ *   Order        (score desc, uid asc): the first out_count entries are the call's own top-k, and the
+ *                whole list is the cursor's pages concatenated.
+ *   Overflow     total > cap is no error: *total is exact, *n = 0 and nothing is written; raise the floor
+ *                or the cap (a counted call tells the size in advance).  No store ever goes past cap keys.
+ *   Pruning      A collecting scan holds the postings scan's threshold at the window's seed, as a counted
+ *                one does (no floor: no pruning).
+ *   Unchanged    The call's own ids, scores and out_count, and pf_scan_window_totals under PF_WIN_COUNT,
+ *                are what they are without a collector (a collecting call the caller did not ask a count
+ *                of leaves the stored totals alone).  With no collector every result and launch is what
+ *                it was.
+ *   Empty        An unknown uid and a group with G = 0 give total = 0.  Under pf_set_shard the result is
+ *                the shard's; the shards' lists merged by (score desc, uid asc) are the unsharded list.
+ *   State        Context state like the filter, the selection and the window; the buffer and its cap
+ *                travel by value with the launch.  pf_scan_bytes ignores it.
+ */
+/* cap > 0: collect into a buffer of cap keys; 0 clears.
+ * PF_EINVAL: cap < 0 or cap > INT32_MAX.
+ * PF_ENOMEM: the device buffer (8 B per key) cannot be had; the collector in force is left alone. */
+int pf_set_scan_collect(pf_ctx* ctx, int64_t cap);
+/* The last collecting call's result: *total = the candidates in the window; *n = the number written
+ * (total when total <= the collector's cap, else 0); at most out_cap entries are written to out_uid /
+ * out_score, ranked (score desc, uid asc).  PF_EINVAL when no collecting call has run. */
+int pf_scan_collected(pf_ctx* ctx, int32_t* out_uid, float* out_score, int64_t out_cap, int64_t* n, int64_t* total);
+
+/*
  * Device-resident all-candidates scan for the multi-GPU bench: scores the
  * queries against this context's shard and writes, per query, `topk` packed
  * 64-bit keys to DEVICE memory d_keys[nq*topk] on `stream` (a hipStream_t).

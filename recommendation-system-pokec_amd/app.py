@@ -26,6 +26,9 @@ and one route of the engine's own:
                                         "next" token of the page before: load more) and "count": true (the reply gains
                                         "total", the number of users in the window).  A reply to a body with one of
                                         them ends with "next", the token of its last result.
+                                        "all": <cap> asks for the WHOLE window in one call (pokec_fas.h "Collect"): the
+                                        reply's list is everyone in it, ranked, whatever topk is, and ends with
+                                        "total"; a window above cap answers an empty list, "total" and "overflow": true.
 
 What differs, because the reference's file cannot run as written:
   * it has unresolved merge-conflict markers (app.py:38-42, 147-159); the start-up wait here
@@ -62,7 +65,8 @@ _CURSOR = re.compile(r"^[0-9a-fA-F]{8}:-?[0-9]{1,10}$")
 
 def window_words(body):
     """The score window's words of a /api/match or /api/group body (csrc/match_line.h): min_score,
-    after (a "next" token as a reply gave it) and count; ValueError on a field of the wrong shape."""
+    after (a "next" token as a reply gave it), count and all (the collector's cap); ValueError on a
+    field of the wrong shape."""
     words = []
     v = body.get("min_score")
     if v is not None:
@@ -79,6 +83,11 @@ def window_words(body):
         raise ValueError("count must be true or false")
     if v:
         words.append("count")
+    v = body.get("all")
+    if v is not None:
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 2**31 - 1:
+            raise ValueError("all must be a cap between 1 and 2147483647")
+        words.append("all=%d" % v)
     return words
 
 
@@ -88,7 +97,7 @@ def match_line(body):
     if not isinstance(body, dict):
         raise ValueError("the body must be a JSON object")
     unknown = set(body) - {"topk", "public", "gender", "completion", "age", "region", "clubs", "friends", "exclude", "tokens",
-                           "min_score", "after", "count"}
+                           "min_score", "after", "count", "all"}
     if unknown:
         raise ValueError("unknown field: " + sorted(unknown)[0])
 
@@ -124,7 +133,7 @@ def group_line(body):
     "mean", "exclude": [...], "exclude_adj": false} and the window's fields (window_words); ValueError on a field of the wrong shape."""
     if not isinstance(body, dict):
         raise ValueError("the body must be a JSON object")
-    unknown = set(body) - {"seeds", "topk", "agg", "exclude", "exclude_adj", "min_score", "after", "count"}
+    unknown = set(body) - {"seeds", "topk", "agg", "exclude", "exclude_adj", "min_score", "after", "count", "all"}
     if unknown:
         raise ValueError("unknown field: " + sorted(unknown)[0])
 

@@ -109,6 +109,31 @@ struct WindowScope {
     }
 };
 
+// The collector of one MATCH / GROUP line (match_line.h: all=<cap>): set for the span of the call,
+// cleared on the way out.  whole() replaces the call's list by the whole window and gives the reply's
+// tail: "total":N, and "overflow":true with an empty list when N > cap.
+struct CollectScope {
+    pf_ctx* ctx;
+    int64_t cap;
+    bool ok = true;
+    CollectScope(pf_ctx* c, int64_t k) : ctx(c), cap(k) {
+        if (cap > 0) ok = pf_set_scan_collect(ctx, cap) == PF_OK;
+    }
+    ~CollectScope() {
+        if (cap > 0) pf_set_scan_collect(ctx, 0);
+    }
+    bool whole(List& r, std::string& tail) const {
+        int64_t n = 0, total = 0;
+        if (pf_scan_collected(ctx, nullptr, nullptr, 0, &n, &total) != PF_OK) return false;
+        r.id.assign((size_t)n + 1, 0);
+        r.score.assign((size_t)n + 1, 0.f);
+        if (n > 0 && pf_scan_collected(ctx, r.id.data(), r.score.data(), n, &n, &total) != PF_OK) return false;
+        r.n = (int32_t)n;
+        tail = ",\"total\":" + std::to_string(total) + (total > cap ? ",\"overflow\":true" : "");
+        return true;
+    }
+};
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -235,7 +260,11 @@ int main(int argc, char** argv) {
             const pf_query_profile q = m.profile();
             List r(m.topk > 0 ? m.topk : 1);
             const WindowScope ws(ctx, m.window);
-            if (!ws.ok || pf_recommend_interest_profile(ctx, &q, 1, m.topk, r.id.data(), r.score.data(), &r.n) != PF_OK) {
+            const CollectScope cs(ctx, m.collect);
+            if (m.collect > 0 && m.topk < 1) m.topk = 1;  // (topk = 0 scans nothing; the list is the window anyway)
+            std::string tail;
+            if (!ws.ok || !cs.ok || pf_recommend_interest_profile(ctx, &q, 1, m.topk, r.id.data(), r.score.data(), &r.n) != PF_OK ||
+                (m.collect > 0 && !cs.whole(r, tail))) {
                 std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
                 std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
                 continue;
@@ -243,19 +272,20 @@ int main(int argc, char** argv) {
             std::ostringstream os;
             os << "{\"recommendations\":{";
             write_list(os, "interest", r, nullptr);
-            os << "}" << ws.tail(r, m.topk) << "}";
+            os << "}" << (m.collect > 0 ? tail : ws.tail(r, m.topk)) << "}";
             std::cout << os.str() << std::endl;
             continue;
         }
         if (cmd == "GROUP") {
             // GROUP <topk> <mean|min|max> <uid> <uid> ... [noadj] [exclude=<uid,uid,...>] and the window's
-            // words (match_line.h): [min=<float>] [after=<hex>:<uid>] [count]
+            // words (match_line.h): [min=<float>] [after=<hex>:<uid>] [count] [all=<cap>]
             std::istringstream iss(line);
             std::string w, agg;
             int topk = -1;
             iss >> w >> topk >> agg;
             std::vector<int32_t> seeds, excl;
             pf_scan_window win{};
+            int64_t collect = 0;
             uint32_t flags = 0;
             bool ok = !iss.fail() && topk >= 0 && (agg == "mean" || agg == "min" || agg == "max");
             auto number = [](const std::string& t, int32_t& v) {
@@ -269,8 +299,11 @@ int main(int argc, char** argv) {
             while (ok && iss >> w) {
                 int32_t v = 0;
                 const int ww = pokec::parse_window_word(w, win);
+                const int cw = ww == 0 ? pokec::parse_collect_word(w, collect) : 0;
                 if (ww != 0) {
                     ok = ww > 0;
+                } else if (cw != 0) {
+                    ok = cw > 0;
                 } else if (w == "noadj") {
                     flags |= PF_GROUP_EXCLUDE_ADJ;
                 } else if (w.rfind("exclude=", 0) == 0) {
@@ -286,7 +319,7 @@ int main(int argc, char** argv) {
                 }
             }
             if (!ok || seeds.empty()) {
-                std::cout << "{\"error\":\"bad request\",\"detail\":\"GROUP <topk> <mean|min|max> <uid>... [noadj] [exclude=<uid,...>] [min=<float>] [after=<hex>:<uid>] [count]\"}"
+                std::cout << "{\"error\":\"bad request\",\"detail\":\"GROUP <topk> <mean|min|max> <uid>... [noadj] [exclude=<uid,...>] [min=<float>] [after=<hex>:<uid>] [count] [all=<cap>]\"}"
                           << std::endl;
                 continue;
             }
@@ -294,7 +327,11 @@ int main(int argc, char** argv) {
                                    flags, excl.empty() ? nullptr : excl.data(), (int32_t)excl.size()};
             List r(topk > 0 ? topk : 1);
             const WindowScope ws(ctx, win);
-            if (!ws.ok || pf_recommend_group(ctx, &q, 1, topk, r.id.data(), r.score.data(), &r.n) != PF_OK) {
+            const CollectScope cs(ctx, collect);
+            if (collect > 0 && topk < 1) topk = 1;  // (topk = 0 scans nothing; the list is the window anyway)
+            std::string tail;
+            if (!ws.ok || !cs.ok || pf_recommend_group(ctx, &q, 1, topk, r.id.data(), r.score.data(), &r.n) != PF_OK ||
+                (collect > 0 && !cs.whole(r, tail))) {
                 std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
                 std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
                 continue;
@@ -302,7 +339,7 @@ int main(int argc, char** argv) {
             std::ostringstream os;
             os << "{\"recommendations\":{";
             write_list(os, "group", r, nullptr);
-            os << "}" << ws.tail(r, topk) << "}";
+            os << "}" << (collect > 0 ? tail : ws.tail(r, topk)) << "}";
             std::cout << os.str() << std::endl;
             continue;
         }

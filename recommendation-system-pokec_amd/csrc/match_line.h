@@ -8,6 +8,10 @@
 //         [min=<float>] [after=<8 hex digits of the score's float bits>:<uid>] [count]
 // The cursor token carries the float's bits because printed decimal scores lose them; a reply to a
 // line with one of these words ends with "next":"<hex>:<uid>", the last result's cursor.
+// A window-like word of both commands asks for the WHOLE window (pokec_fas.h "Collect"):
+//         [all=<cap>]      1 <= cap <= 2147483647
+// The reply's list is then every candidate of the window, ranked, whatever topk is, and the reply ends
+// with "total":N; when N > cap the list is empty and "overflow":true follows.
 //
 // A field that is not given is missing; an empty region part ("region=3,,27") is missing; c<t> is
 // text column t of the engine's list, as token ids (the text -> id ETL is not part of the engine).
@@ -31,6 +35,7 @@ struct MatchLine {
     std::vector<uint32_t> clubs, friends;
     std::vector<int32_t> exclude;
     pf_scan_window window{};  // fields == 0: the line has none of the window's words
+    int64_t collect = 0;      // all=<cap>; 0: the line has no such word
     std::vector<std::vector<std::pair<int32_t, int32_t>>> cols;  // [n_cols] (tid, tf) in the line's order
     // the C struct over this object's arrays (valid while the object lives and is not changed)
     std::vector<int64_t> off;
@@ -108,6 +113,16 @@ inline int parse_window_word(const std::string& w, pf_scan_window& win) {
     }
     return 0;
 }
+// One word of a MATCH / GROUP line as the collector's word all=<cap>: 1 = taken into `cap`, 0 = another
+// word, -1 = malformed (not a number, below 1, above INT32_MAX)
+inline int parse_collect_word(const std::string& w, int64_t& cap) {
+    if (w.rfind("all=", 0) != 0) return 0;
+    long long v = 0;
+    const std::string val = w.substr(4);
+    if (val.empty() || val[0] == '+' || val[0] == '-' || !match_detail::to_int(val, 1, INT32_MAX, v)) return -1;
+    cap = (int64_t)v;
+    return 1;
+}
 // the cursor token of a result: its score's float bits and its uid
 inline std::string window_cursor(float score, int32_t uid) {
     uint32_t bits = 0;
@@ -133,6 +148,9 @@ inline bool parse_match_line(const std::string& rest, int n_cols, MatchLine& m, 
         const int ww = parse_window_word(w, m.window);
         if (ww < 0) { why = "bad value: " + w; return false; }
         if (ww > 0) continue;
+        const int cw = parse_collect_word(w, m.collect);
+        if (cw < 0) { why = "bad value: " + w; return false; }
+        if (cw > 0) continue;
         const size_t eq = w.find('=');
         if (eq == std::string::npos || eq == 0) { why = "not key=value: " + w; return false; }
         const std::string key = w.substr(0, eq), val = w.substr(eq + 1);

@@ -381,6 +381,56 @@ struct CountScope {
     }
 };
 
+// A collecting synchronous call (pf_set_scan_collect in force, topk > 0): for its own duration the
+// context's window carries kWinCollect | kWinCount, so the call's one launch takes the windowed code,
+// holds K5's theta at the window's seed, counts, and appends (collect_buf()).  Constructed before the
+// call's CountScope, which then counts whether or not the caller asked for PF_WIN_COUNT; finish()
+// comes after the CountScope's: it takes the total, gives the caller's totals back when the count was
+// not theirs, sorts the keys when they fit and brings them to coll_keys.  No collector: every member
+// function does nothing.
+struct CollectScope {
+    pf_ctx* c;
+    bool on;
+    pf::ScanWindow saved;
+    std::vector<int64_t> saved_totals;
+    bool saved_totals_set = false;
+    explicit CollectScope(pf_ctx* ctx) : c(ctx), on(ctx->coll_cap > 0), saved(ctx->win) {}
+    ~CollectScope() { c->win = saved; }
+    int begin(int nq) {
+        if (nq == 0) on = false;  // a call of no queries scans nothing
+        if (!on) return PF_OK;
+        if (nq != 1) return c->fail(PF_EUNSUPP, "scan collect: one query (or group) per collecting call");
+        saved_totals = c->win_totals;
+        saved_totals_set = c->win_totals_set;
+        c->win.fields |= pf::kWinCollect | pf::kWinCount;
+        return PF_OK;
+    }
+    int finish() {
+        c->win = saved;
+        if (!on) return PF_OK;
+        const int64_t total = c->win_totals.empty() ? 0 : c->win_totals[0];
+        if (!(saved.fields & pf::kWinCount)) {
+            c->win_totals.swap(saved_totals);
+            c->win_totals_set = saved_totals_set;
+        }
+        c->coll_keys.clear();
+        c->coll_total = total;
+        c->coll_set = true;
+        if (total == 0 || total > c->coll_cap) return PF_OK;
+        size_t tmp_b = 0;
+        HIPCHK(c, pf::collect_sort_bytes(total, &tmp_b));
+        HIPCHK(c, c->d_coll_tmp.ensure(std::max<size_t>(tmp_b, 16)));
+        HIPCHK(c, c->d_coll_sorted.ensure((size_t)total * sizeof(uint64_t)));
+        HIPCHK(c, pf::collect_sort(c->d_coll.as<uint64_t>(), c->d_coll_sorted.as<uint64_t>(), total, c->d_coll_tmp.p, tmp_b,
+                                   c->stream));
+        c->coll_keys.resize((size_t)total);
+        HIPCHK(c, hipMemcpyAsync(c->coll_keys.data(), c->d_coll_sorted.p, (size_t)total * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return PF_OK;
+    }
+};
+
 int scan_lanes();
 
 // Workgroups of a one-query postings scan: one resident round, or seven eighths of one on the
@@ -568,7 +618,8 @@ int scan_post_one(pf_ctx* c, uint32_t var_lds, int32_t row, int k, uint64_t* d_k
                                .parts = part_buf.as<uint64_t>(), .out = ln ? lu.keys : dst, .sync = Q.sync,
                                .out_rows = Q.out_rows, .claimed = true, .mode = post_mode(true), .e0 = timed ? e0 : nullptr,
                                .e1 = stop, .s = ls, .qconst = Q.qconst, .filt = c->filt, .sel = c->sel, .win = c->win_post(),
-                               .totals = c->cur_totals ? c->cur_totals + row : nullptr}));
+                               .totals = c->cur_totals ? c->cur_totals + row : nullptr, .collect = c->collect_buf(),
+                               .collect_cap = c->collect_cap_dev()}));
     // the caller's stream: wait for the lane's launch (its stop event), copy its row out
     if (ln && (rc = lane_end(c, lu, stop, s, dst, k)) != PF_OK) return rc;
     if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
@@ -628,7 +679,8 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
                                    .parts = c->d_part.as<uint64_t>() + (size_t)q0 * (blocks + 8) * k, .out = d_keys,
                                    .sync = Q.sync + q0, .out_rows = Q.out_rows + q0, .claimed = false, .mode = post_mode(false),
                                    .e0 = (timed && q0 == 0) ? e0 : nullptr, .e1 = (timed && q1 == nq) ? e1 : nullptr, .s = s,
-                                   .qconst = nullptr, .filt = c->filt, .sel = c->sel, .win = wpost, .totals = c->cur_totals}));
+                                   .qconst = nullptr, .filt = c->filt, .sel = c->sel, .win = wpost, .totals = c->cur_totals,
+                                   .collect = c->collect_buf(), .collect_cap = c->collect_cap_dev()}));
         q0 = q1;
     }
     if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
@@ -794,7 +846,8 @@ int scan_stream_images(pf_ctx* c, int nq, const std::vector<int32_t>& rows, int 
     HIPCHK(c, pf::launch_scan({.st = c->ds, .pool = d_images, .refs_dev = d_refs, .lds = im.max_lds, .gtab = im.gtab, .nq = nq,
                                .tile_begin = c->tile_begin, .tile_end = c->tile_end, .k = k, .blocks = blocks,
                                .parts = c->d_part.as<uint64_t>(), .out = d_keys, .sync = d_sync, .out_rows = d_rows, .s = s,
-                               .filt = c->filt, .sel = c->sel, .win = c->win, .totals = c->cur_totals}));
+                               .filt = c->filt, .sel = c->sel, .win = c->win, .totals = c->cur_totals,
+                               .collect = c->collect_buf(), .collect_cap = c->collect_cap_dev()}));
     if (timed) {
         HIPCHK(c, hipEventRecord(e1, s));
         c->last_ev0 = e0;
@@ -1316,9 +1369,12 @@ static int resolve_profiles(pf_ctx* c, const pf_query_profile* q, int32_t nq, st
 static int recommend_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps, int32_t topk, int32_t* ou, float* os,
                               int32_t* oc) {
     const int32_t nq = (int32_t)ps.size();
+    CollectScope col(c);  // a collector in force: this call's window counts and appends
+    int crc = col.begin(nq);
+    if (crc != PF_OK) return crc;
     HIPCHK(c, c->d_out.ensure((size_t)nq * topk * sizeof(uint64_t)));
     CountScope cnt(c, nq);
-    int crc = cnt.begin();
+    crc = cnt.begin();
     if (crc != PF_OK) return crc;
     const size_t chunk = 256;
     for (size_t b = 0; b < ps.size(); b += chunk) {
@@ -1342,7 +1398,8 @@ static int recommend_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
     for (int i = 0; i < nq; ++i) pf_decode_keys(&keys[(size_t)i * topk], topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
-    return cnt.finish();
+    crc = cnt.finish();
+    return crc != PF_OK ? crc : col.finish();
 }
 
 static int profile_args(pf_ctx* c, const pf_query_profile* q, int32_t nq, int32_t topk, int32_t* ou, float* os, int32_t* oc) {
@@ -1456,11 +1513,14 @@ int pf_recommend_interest(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk,
             int32_t x = c->hc.idx_of(q[i]);
             if (x >= 0) { idx.push_back(x); rows.push_back(i); }
         }
+        CollectScope col(c);  // a collector in force: this call's window counts and appends
+        int crc = col.begin(nq);
+        if (crc != PF_OK) return crc;
         HIPCHK(c, c->d_out.ensure((size_t)nq * topk * sizeof(uint64_t)));
         if ((int)idx.size() < nq)  // rows of unknown users stay empty
             HIPCHK(c, hipMemsetAsync(c->d_out.p, 0xFF, (size_t)nq * topk * sizeof(uint64_t), c->stream));
         CountScope cnt(c, nq);
-        const int crc = cnt.begin();
+        crc = cnt.begin();
         if (crc != PF_OK) return crc;
         const int chunk = 256;
         for (size_t b = 0; b < idx.size(); b += chunk) {
@@ -1474,8 +1534,11 @@ int pf_recommend_interest(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk,
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (!idx.empty() && c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
         for (int i = 0; i < nq; ++i) pf_decode_keys(&keys[(size_t)i * topk], topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
-        return cnt.finish();
+        crc = cnt.finish();
+        return crc != PF_OK ? crc : col.finish();
     }
+    if (mode == PF_MODE_ALL && c->coll_cap > 0)
+        return c->fail(PF_EUNSUPP, "scan collect: topk above 64 runs in the job pipeline, which reads no collector");
     if (mode == PF_MODE_ALL && c->win.fields != 0u)
         return c->fail(PF_EUNSUPP, "scan window: topk above 64 runs in the job pipeline, which reads no window "
                                    "(page with the cursor instead)");
@@ -1736,10 +1799,53 @@ int pf_scan_window_totals(pf_ctx* c, int64_t* out, int32_t cap, int32_t* n) {
     return PF_OK;
 }
 
+int pf_set_scan_collect(pf_ctx* c, int64_t cap) {
+    if (!c) return PF_EINVAL;
+    if (cap < 0 || cap > (int64_t)INT32_MAX) return c->fail(PF_EINVAL, "scan collect: cap below 0 or above INT32_MAX");
+    if (cap == 0) {  // cleared; the buffers stay for the next collector
+        c->coll_cap = 0;
+        return PF_OK;
+    }
+    (void)hipSetDevice(c->device);
+    const size_t bytes = (size_t)cap * sizeof(uint64_t);
+    if (bytes > c->d_coll.cap) {  // the new buffer first: a refusal leaves the collector in force alone
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return c->fail(PF_ENOMEM, "scan collect: no device memory for the buffer (8 B per key)");
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->d_coll.p) (void)hipFree(c->d_coll.p);
+        c->d_coll.p = p;
+        c->d_coll.cap = bytes;
+    }
+    c->coll_cap = cap;
+    return PF_OK;
+}
+
+int pf_scan_collected(pf_ctx* c, int32_t* out_uid, float* out_score, int64_t out_cap, int64_t* n, int64_t* total) {
+    if (!c) return PF_EINVAL;
+    if (!n || !total || out_cap < 0 || (out_cap && (!out_uid || !out_score)))
+        return c->fail(PF_EINVAL, "scan collected: null argument");
+    if (!c->coll_set) return c->fail(PF_EINVAL, "scan collected: no collecting call has run");
+    *total = c->coll_total;
+    *n = (int64_t)c->coll_keys.size();
+    const int64_t m = std::min<int64_t>(out_cap, *n);
+    for (int64_t i = 0; i < m;) {  // pf_decode_keys' arithmetic, a slice at a time (its count is 32-bit)
+        const int32_t step = (int32_t)std::min<int64_t>(m - i, 1 << 20);
+        int32_t cnt = 0;
+        pf_decode_keys(c->coll_keys.data() + i, step, out_uid + i, out_score + i, &cnt);
+        i += step;
+    }
+    return PF_OK;
+}
+
 int pf_scan_keys_async(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, uint64_t* d_keys, void* stream) {
     if (!c || nq < 0 || topk <= 0 || topk > pf::kMaxTopK || (nq && (!q || !d_keys))) return PF_EINVAL;
     if (c->win.fields & pf::kWinCount)
         return c->fail(PF_EUNSUPP, "scan window: PF_WIN_COUNT with pf_scan_keys_async (a count needs a synchronous call)");
+    if (c->coll_cap > 0)
+        return c->fail(PF_EUNSUPP, "scan collect: pf_scan_keys_async reads no collector (a collect needs a synchronous call)");
     (void)hipSetDevice(c->device);
     hipStream_t s = (hipStream_t)stream;  // as given: NULL is the null stream
     std::vector<int32_t> idx, rows;

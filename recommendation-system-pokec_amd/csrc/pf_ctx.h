@@ -252,6 +252,18 @@ struct pf_ctx {
     // where the launches of the synchronous call in progress write their counts (row 0 of its current
     // chunk in d_totals); nullptr outside a counted call
     uint32_t* cur_totals = nullptr;
+    // collector of the all-candidates scans (pf_set_scan_collect; coll_cap == 0: none): the buffer a
+    // collecting call's one launch appends its window's keys to, the sort's output and scratch, and
+    // the last collecting call's result on the host (pf_scan_collected).  A collecting call sets
+    // kWinCollect | kWinCount in `win` for its own duration (CollectScope): collect_buf() is what its
+    // launches carry, nullptr for everybody else's.
+    int64_t coll_cap = 0;
+    DBuf d_coll, d_coll_sorted, d_coll_tmp;
+    std::vector<uint64_t> coll_keys;     // ranked; empty on overflow
+    int64_t coll_total = 0;
+    bool coll_set = false;
+    uint64_t* collect_buf() const { return (win.fields & pf::kWinCollect) ? static_cast<uint64_t*>(d_coll.p) : nullptr; }
+    uint32_t collect_cap_dev() const { return (win.fields & pf::kWinCollect) ? (uint32_t)coll_cap : 0u; }
     // pinned staging ring for the per-call query upload (a slot is reused only after
     // the copy that read it has completed)
     struct Stage {

@@ -16,6 +16,7 @@
 #include "pf_filter.h"
 #include "pf_select.h"
 #include "pf_types.h"
+#include "pf_collect.h"
 #include "pf_window.h"
 
 namespace pf {
@@ -92,6 +93,10 @@ struct GroupLaunch {
     // pass; a counted one writes the group's count to totals[0] (device, nullptr otherwise)
     const ScanWindow& win;
     uint32_t* totals;
+    // the context's collector (pf_collect.h) when win has kWinCollect: the buffer (device) and its cap
+    // in keys; nullptr / 0 otherwise.  One query per collecting launch.
+    uint64_t* collect;
+    uint32_t collect_cap;
 };
 hipError_t launch_group(const GroupLaunch& L);
 // resident workgroups per CU of a pass's instantiation at its LDS size

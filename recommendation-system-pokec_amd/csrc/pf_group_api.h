@@ -144,7 +144,8 @@ int group_scan(pf_ctx* c, const GroupPlan& P, int agg, int k, uint64_t* d_keys, 
                                     .tile_end = c->tile_end, .k = k, .blocks = blocks[p], .acc = c->d_scores.as<double>(),
                                     .parts = c->d_part.as<uint64_t>(), .out = d_keys,
                                     .sync = reinterpret_cast<pf::ScanSync*>(base + refs_b + offs_b), .s = c->stream,
-                                    .filt = c->filt, .sel = c->sel, .win = c->win, .totals = c->cur_totals}));
+                                    .filt = c->filt, .sel = c->sel, .win = c->win, .totals = c->cur_totals,
+                                    .collect = c->collect_buf(), .collect_cap = c->collect_cap_dev()}));
     if (timed) {
         HIPCHK(c, hipEventRecord(e1, c->stream));
         c->last_ev0 = e0;
@@ -171,8 +172,11 @@ int pf_recommend_group(pf_ctx* c, const pf_group_query* g, int32_t ng, int32_t t
     if (topk == 0) return PF_OK;
     HIPCHK(c, c->d_out.ensure((size_t)topk * sizeof(uint64_t)));
     std::vector<uint64_t> keys((size_t)topk);
+    CollectScope col(c);  // a collector in force: this call's window counts and appends
+    int crc = col.begin(ng);
+    if (crc != PF_OK) return crc;
     CountScope cnt(c, ng);  // a counted window: group i's count in row i (0 for G = 0)
-    const int crc = cnt.begin();
+    crc = cnt.begin();
     if (crc != PF_OK) return crc;
     for (int32_t i = 0; i < ng; ++i) {
         cnt.at((size_t)i);
@@ -186,7 +190,8 @@ int pf_recommend_group(pf_ctx* c, const pf_group_query* g, int32_t ng, int32_t t
         if (c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
         pf_decode_keys(keys.data(), topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
     }
-    return cnt.finish();
+    crc = cnt.finish();
+    return crc != PF_OK ? crc : col.finish();
 }
 
 int pf_group_scores(pf_ctx* c, const pf_group_query* g, const int32_t* b, int64_t n, const pf_field_select* s, float* out) {

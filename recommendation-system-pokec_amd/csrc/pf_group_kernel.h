@@ -53,7 +53,8 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_group_kernel(DevStore st,
                                                                  uint64_t* __restrict__ parts,
                                                                  ScanSync* __restrict__ sync,
                                                                  uint64_t* __restrict__ out, CandFilter F, FieldSel S,
-                                                                 ScanWindow WN, uint32_t* __restrict__ totals) {
+                                                                 ScanWindow WN, uint32_t* __restrict__ totals,
+                                                                 uint64_t* __restrict__ cbuf, uint32_t ccap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // stage the pass's images side by side (stage_query's copies, per image)
     for (int i = 0; i < A.nimg; ++i) {
@@ -150,6 +151,8 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_group_kernel(DevStore st,
         if (WN.fields != 0u) {
             if (!window_pass(key, WN)) key = ~0ull;
             if (WN.fields & kWinCount) wcnt += (uint32_t)__popcll(__ballot(key != ~0ull));
+            // a collecting launch keeps the aggregate's key (the wave is whole here: the tile is the wave's)
+            if (WN.fields & kWinCollect) collect_append(key, ~0ull, &sync->ccursor, cbuf, ccap, lane);
         }
         topk_push(list, key, A.k, lane);
     }
@@ -168,10 +171,12 @@ static GroupKernel group_kernel(bool packed, bool gtab) {
 hipError_t launch_group(const GroupLaunch& L) {
     if (L.pass.nimg <= 0) return hipSuccess;
     if ((L.win.fields & kWinCount) && !L.totals) return hipErrorInvalidValue;
+    if (!collect_launch_ok(L.win, 1, L.collect, L.collect_cap)) return hipErrorInvalidValue;
     const GroupArgs A{L.pass.img0, L.pass.nimg, L.pass.hits_off, L.hit_bytes, L.first ? 1 : 0, L.last ? 1 : 0, L.agg,
                       L.n_seeds, L.excl_img, L.tile_begin, L.tile_end, L.k};
     hipLaunchKernelGGL(group_kernel(L.st.packed, L.pass.gtab), dim3(L.blocks), dim3(kScanThreads), L.pass.lds, L.s, L.st,
-                       L.pool, L.refs_dev, L.off_dev, A, L.acc, L.parts, L.sync, L.out, L.filt, L.sel, L.win, L.totals);
+                       L.pool, L.refs_dev, L.off_dev, A, L.acc, L.parts, L.sync, L.out, L.filt, L.sel, L.win, L.totals,
+                       L.collect, L.collect_cap);
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 #include "pf_filter.h"
 #include "pf_select.h"
 #include "pf_types.h"
+#include "pf_collect.h"
 #include "pf_window.h"
 
 namespace pf {
@@ -53,6 +54,10 @@ struct ScanLaunch {
     // counted one (kWinCount) writes each query's count to totals[its row] (device, nullptr otherwise)
     const ScanWindow& win;
     uint32_t* totals;
+    // the context's collector (pf_collect.h) when win has kWinCollect: the buffer (device) and its cap
+    // in keys; nullptr / 0 otherwise.  One query per collecting launch.
+    uint64_t* collect;
+    uint32_t collect_cap;
 };
 hipError_t launch_scan(const ScanLaunch& L);
 // resident scan blocks per CU at this dynamic LDS size (HIP occupancy API)
@@ -104,6 +109,10 @@ struct PostLaunch {
     // A counted one (kWinCount) writes each query's count to totals[its row] (device, nullptr otherwise)
     const ScanWindow& win;
     uint32_t* totals;
+    // the context's collector (pf_collect.h) when win has kWinCollect: the buffer (device) and its cap
+    // in keys; nullptr / 0 otherwise.  One query per collecting launch.
+    uint64_t* collect;
+    uint32_t collect_cap;
 };
 hipError_t launch_post(const PostLaunch& L);
 // workgroups per CU of the instantiation launch_post takes for `claimed`, `filtered` (a filter is

@@ -872,6 +872,32 @@ __device__ __forceinline__ uint64_t merge_lists(At at, int nl, int k, uint64_t* 
 // barrier below, hence before the workgroup's ticket, as the last block's histogram record has; the
 // final merger reads the word after the last ticket and writes it to totals[row] before it zeroes the
 // struct.  A launch that does not count passes false and is the code it was.
+// The collector's append (a launch with kWinCollect, pf_window.h), by a whole wave at a keying point:
+// a ballot of the lanes whose key is in the window, one returning relaxed agent-scope add of its
+// popcount to the query's cursor word by the first lane, the base broadcast, and each in-window lane's
+// key stored at base + its rank among the ballot, only below cap: plain vector stores, none past the
+// buffer however many match.  A wave with no match issues nothing.  The add has returned before the
+// stores, hence before the workgroup's ticket and the final merger's zeroing of the word.  K5 calls
+// it with its block's two keys per lane under one add (key1; ~0 elsewhere).
+__device__ __forceinline__ void collect_append(uint64_t key0, uint64_t key1, unsigned int* cursor,
+                                               uint64_t* __restrict__ cbuf, uint32_t ccap, int lane) {
+    const uint64_t b0 = __ballot(key0 != ~0ull), b1 = __ballot(key1 != ~0ull);
+    if ((b0 | b1) == 0ull) return;
+    const uint32_t n0 = (uint32_t)__popcll(b0), n1 = (uint32_t)__popcll(b1);
+    uint32_t base = 0u;
+    if (lane == 0) base = __hip_atomic_fetch_add(cursor, n0 + n1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    const uint64_t below = (1ull << lane) - 1ull;
+    if (key0 != ~0ull) {
+        const uint32_t at = base + (uint32_t)__popcll(b0 & below);
+        if (at < ccap) cbuf[at] = key0;
+    }
+    if (key1 != ~0ull) {
+        const uint32_t at = base + n0 + (uint32_t)__popcll(b1 & below);
+        if (at < ccap) cbuf[at] = key1;
+    }
+}
+
 __device__ __forceinline__ void post_tail(uint64_t list, int k, uint64_t* sc, ScanSync* __restrict__ sync,
                                           uint64_t* __restrict__ parts, uint64_t* __restrict__ out,
                                           const int32_t* __restrict__ out_rows, int qy, int bx, int nbx,
@@ -938,7 +964,8 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_scan_kernel(DevStore st, 
                                                                 ScanSync* __restrict__ sync,
                                                                 uint64_t* __restrict__ out,
                                                                 const int32_t* __restrict__ out_rows, CandFilter F,
-                                                                FieldSel S, ScanWindow WN, uint32_t* __restrict__ totals) {
+                                                                FieldSel S, ScanWindow WN, uint32_t* __restrict__ totals,
+                                                                uint64_t* __restrict__ cbuf, uint32_t ccap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const QImageRef r = refs[blockIdx.y];
     char* scratch;
@@ -1017,6 +1044,8 @@ __global__ __launch_bounds__(kScanThreads, 4) void fas_scan_kernel(DevStore st, 
         if (WN.fields != 0u) {
             if (!window_pass(key, WN)) key = ~0ull;
             if (WN.fields & kWinCount) wcnt += (uint32_t)__popcll(__ballot(key != ~0ull));
+            // a collecting launch keeps the key (the wave is whole here: the tile is the wave's)
+            if (WN.fields & kWinCollect) collect_append(key, ~0ull, &sync[blockIdx.y].ccursor, cbuf, ccap, lane);
         }
         topk_push(list, key, k, lane);
     }
@@ -1340,7 +1369,8 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                                                               ScanSync* __restrict__ sync, uint64_t* __restrict__ out,
                                                               const int32_t* __restrict__ out_rows, uint32_t mode,
                                                               const uint8_t* __restrict__ qconst, CandFilter F,
-                                                              FieldSel S, ScanWindow W, uint32_t* __restrict__ totals) {
+                                                              FieldSel S, ScanWindow W, uint32_t* __restrict__ totals,
+                                                              uint64_t* __restrict__ cbuf, uint32_t ccap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int qy = XD ? 0 : (int)blockIdx.y;
     const int bx = (int)blockIdx.x;
@@ -2027,6 +2057,20 @@ __global__ __launch_bounds__(kPostThreads, PF_K5_MINB) void fas_post_kernel(Post
                 const uint32_t nin = (uint32_t)__popcll(__ballot(keys[0] != ~0ull)) + (uint32_t)__popcll(__ballot(keys[1] != ~0ull));
                 if (lane == 0 && nin != 0u) atomicAdd(&misc[6], nin);
             }
+            // a collecting launch keeps the block's in-window keys, with the uid in the id word (the
+            // header word the tail's idx -> uid step reads): the buffer holds uid keys whoever filled it
+            if (wl->fields & kWinCollect) {
+                uint64_t ck[kCandsPerThread];
+#pragma unroll
+                for (int kk = 0; kk < kCandsPerThread; ++kk) {
+                    ck[kk] = keys[kk];
+                    if (ck[kk] != ~0ull) {
+                        const uint32_t idx = (uint32_t)ck[kk] ^ 0x80000000u;
+                        ck[kk] = (ck[kk] & 0xFFFFFFFF00000000ull) | (ps.hdr[2 * (size_t)idx + 1].w ^ 0x80000000u);
+                    }
+                }
+                collect_append(ck[0], ck[1], &sync[qy].ccursor, cbuf, ccap, lane);
+            }
         }
         // the lane's 2 keys ascending, then pushed best-first: after the first push the
         // wave's threshold rejects most of the rest
@@ -2264,8 +2308,10 @@ static PostKernel post_kernel(bool claimed, bool filtered, bool selected, bool w
 hipError_t launch_scan(const ScanLaunch& L) {
     if (L.nq <= 0) return hipSuccess;
     if ((L.win.fields & kWinCount) && !L.totals) return hipErrorInvalidValue;
+    if (!collect_launch_ok(L.win, L.nq, L.collect, L.collect_cap)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(scan_kernel(L.st.packed, L.gtab), dim3(L.blocks, L.nq), dim3(kScanThreads), L.lds, L.s, L.st, L.pool,
-                       L.refs_dev, L.tile_begin, L.tile_end, L.k, L.parts, L.sync, L.out, L.out_rows, L.filt, L.sel, L.win, L.totals);
+                       L.refs_dev, L.tile_begin, L.tile_end, L.k, L.parts, L.sync, L.out, L.out_rows, L.filt, L.sel, L.win, L.totals,
+                       L.collect, L.collect_cap);
     return hipGetLastError();
 }
 
@@ -2340,6 +2386,7 @@ hipError_t launch_post(const PostLaunch& L) {
     // the claimed hand-out is the one-query instantiation's and nobody else's
     if (L.claimed && L.nq != 1) return hipErrorInvalidValue;
     if ((L.win.fields & kWinCount) && !L.totals) return hipErrorInvalidValue;
+    if (!collect_launch_ok(L.win, L.nq, L.collect, L.collect_cap)) return hipErrorInvalidValue;
     // + the filter's and the window's words (fas_post_kernel)
     const uint32_t lds = post_lds(L.var_lds) + (L.filt.fields ? kFiltLds : 0u) + (L.win.fields ? kWinLds : 0u);
     // timed launches (e0, e1 given): the kernel's own start and end timestamps, taken from its
@@ -2347,7 +2394,7 @@ hipError_t launch_post(const PostLaunch& L) {
     // selection travel in the launch's own arguments: a later pf_set_scan_filter / _select does not reach them
     hipExtLaunchKernelGGL(post_kernel(L.claimed, L.filt.fields != 0u, L.sel.on != 0u, L.win.fields != 0u), dim3(L.blocks, L.nq), dim3(kPostThreads),
                           lds, L.s, L.e0, L.e1, 0u, L.ps, L.pool, L.img_off, L.blk_begin, L.blk_end, L.k, L.parts, L.sync, L.out,
-                          L.out_rows, L.mode, L.qconst, L.filt, L.sel, L.win, L.totals);
+                          L.out_rows, L.mode, L.qconst, L.filt, L.sel, L.win, L.totals, L.collect, L.collect_cap);
 #ifdef PF_K5_BLOCKLOG
     {
         static int calls = 0;

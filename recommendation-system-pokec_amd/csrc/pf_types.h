@@ -156,7 +156,10 @@ struct ScanSync {
     // a counted launch's candidates in the window (pf_window.h): one add per wave or workgroup before
     // its ticket, written out by post_tail's final merger
     unsigned int wcount;
-    unsigned int pad1[14];
+    // a collecting launch's append cursor (pf_collect.h): one returning add per wave with in-window
+    // keys; zeroed with the rest by post_tail's final merger
+    unsigned int ccursor;
+    unsigned int pad1[13];
     unsigned int hist[784];
 };
 static_assert(sizeof(ScanSync) % 16 == 0, "post_tail zeroes ScanSync in 16-B stores");

@@ -44,7 +44,7 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_recommend_interest_profile", "pf_fas_profile_pairs", "pf_fas_profile_pairs_terms",
            "pf_recommend_interest_profile_terms",
            "pf_recommend_group", "pf_group_scores", "pf_group_plan_of", "pf_group_image_lds",
-           "pf_set_scan_window", "pf_scan_window_totals"]
+           "pf_set_scan_window", "pf_scan_window_totals", "pf_set_scan_collect", "pf_scan_collected"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
               "pf_dataset_profile_order", "pf_dataset_adj_order", "pf_dataset_profile_json", "pf_dataset_club_name",
@@ -188,6 +188,23 @@ def pages(call, k, window=None):
         w.fields |= PF_WIN_AFTER
         w.after_score = float(scores[-1])
         w.after_uid = int(ids[-1])
+
+
+def collect_all(call, window=None, cap=None):
+    """Every candidate of a score window in one pass: (ids, scores, total), ranked (score desc, uid
+    asc).  call(window, collect) makes one scan call of one query with its two arguments passed on as
+    window= and collect=, and returns (ids, scores, total): with collect=None the total of a counted
+    call (ids and scores are not read), else the collected list (FasEngine.collect_call wraps an
+    engine call so).  cap=None: one counted call sizes the buffer, then one collecting call with cap =
+    max(total, 1); a cap given: the one collecting call, whose ids are empty when total > cap.  The
+    collector in force before is restored by collect= itself.  Example:
+        ids, scores, total = collect_all(eng.collect_call(
+            lambda w, c: eng.recommend_group(seeds, 1, window=w, collect=c)), ScanWindow.make(min_score=0.4))"""
+    if cap is None:
+        w = ScanWindow() if window is None else window.copy()
+        w.fields |= PF_WIN_COUNT
+        cap = max(int(call(w, None)[2]), 1)
+    return call(window, int(cap))
 
 
 class PairTermsHead(ctypes.Structure):
@@ -416,6 +433,8 @@ def lib():
         L.pf_group_image_lds.argtypes = [V, ctypes.POINTER(GroupQuery), V, I32]
         L.pf_set_scan_window.argtypes = [V, ctypes.POINTER(ScanWindow)]
         L.pf_scan_window_totals.argtypes = [V, V, I32, ctypes.POINTER(I32)]
+        L.pf_set_scan_collect.argtypes = [V, I64]
+        L.pf_scan_collected.argtypes = [V, V, V, I64, ctypes.POINTER(I64), ctypes.POINTER(I64)]
         L.pf_merge_keys_async.argtypes = [V, V, I32, I32, I32, V, V]
         L.pf_decode_keys.argtypes = [V, I32, V, V, V]
         L.pf_decode_keys.restype = None
@@ -476,6 +495,7 @@ class FasEngine:
         self._filter = None  # the candidate filter in force (a CandFilter copy), None = none
         self._select = None  # the field selection in force (a FieldSelect copy), None = none
         self._window = None  # the score window in force (a ScanWindow copy), None = none
+        self._collect = 0    # the collector's cap in force, 0 = none
         rc = L.pf_open(desc_ptr, device, ctypes.byref(self.h))
         if rc != PF_OK:
             raise FasError(f"pf_open failed ({rc}): {L.pf_last_error(None).decode()}")
@@ -629,10 +649,10 @@ class FasEngine:
     recommend_friends_collab = recommend_collaborative
 
     @contextlib.contextmanager
-    def _scoped(self, filter=None, select=None, window=None):
-        """Set the given filter / selection / window for one call; those in force before it are
-        restored afterwards."""
-        prev, prev_sel, prev_win = self._filter, self._select, self._window
+    def _scoped(self, filter=None, select=None, window=None, collect=None):
+        """Set the given filter / selection / window / collector for one call; those in force before
+        it are restored afterwards."""
+        prev, prev_sel, prev_win, prev_col = self._filter, self._select, self._window, self._collect
         try:
             if filter is not None:
                 self.set_scan_filter(filter)
@@ -640,8 +660,12 @@ class FasEngine:
                 self.set_scan_select(select)
             if window is not None:
                 self.set_scan_window(window)
+            if collect is not None:
+                self.set_scan_collect(collect)
             yield
         finally:
+            if collect is not None:
+                self.set_scan_collect(prev_col)
             if filter is not None:
                 self.set_scan_filter(prev)
             if select is not None:
@@ -649,13 +673,15 @@ class FasEngine:
             if window is not None:
                 self.set_scan_window(prev_win)
 
-    def recommend_interest_all(self, users, topk, filter=None, select=None, explain=False, window=None):
+    def recommend_interest_all(self, users, topk, filter=None, select=None, explain=False, window=None, collect=None):
         """All-candidates interest scan.  filter (a CandFilter): rank only the candidates
         that pass it; select (a FieldSelect): score over the selected fields only; window (a
         ScanWindow): a floor, a paging cursor and a count (scan_window_totals).  The filter, the
         selection and the window in force before the call are restored afterwards.  explain: each
-        result is (ids, scores, PairTerms), the breakdown of every listed score (one more launch and copy)."""
-        with self._scoped(filter, select, window):
+        result is (ids, scores, PairTerms), the breakdown of every listed score (one more launch and copy).
+        collect (a cap in keys; one user only): the call also keeps the whole window, ranked, for
+        scan_collected(); the collector in force before is restored like the rest."""
+        with self._scoped(filter, select, window, collect):
             if explain:
                 return self._topk_terms(users, topk)
             return self.recommend_interest(users, topk, PF_MODE_ALL, 0)
@@ -688,13 +714,13 @@ class FasEngine:
         return [(ou[i * k:i * k + oc[i]].copy(), os_[i * k:i * k + oc[i]].copy(),
                  PairTerms(head[i * k:i * k + oc[i]], terms[i * k:i * k + oc[i]].copy())) for i in range(n)]
 
-    def recommend_profile(self, profiles, k, filter=None, select=None, explain=False, window=None):
+    def recommend_profile(self, profiles, k, filter=None, select=None, explain=False, window=None, collect=None):
         """The all-candidates top-k of each QueryProfile (one, or a list: one call), for people who are
         not users of the corpus.  filter / select / explain / window as in recommend_interest_all: the
         filter, selection and window in force before the call are restored afterwards (the window's
-        cursor is the way past result 64).  A profile's exclusions are its own `exclude` list and
-        nothing else."""
-        with self._scoped(filter, select, window):
+        cursor is the way past result 64; collect= keeps the whole window of one profile).  A profile's
+        exclusions are its own `exclude` list and nothing else."""
+        with self._scoped(filter, select, window, collect):
             return self._recommend_profile(profiles, k, explain)
 
     def fas_profile_pairs(self, profile, b_uid, select=None):
@@ -720,17 +746,19 @@ class FasEngine:
         return PairTerms(head, terms)
 
     # -- group query (pf_group_query): who is similar to a set of seed users
-    def recommend_group(self, seeds, k, agg="mean", exclude=(), exclude_adj=False, filter=None, select=None, window=None):
+    def recommend_group(self, seeds, k, agg="mean", exclude=(), exclude_adj=False, filter=None, select=None, window=None,
+                        collect=None):
         """The top-k users most similar to the seed users as a group: (ids, scores).  agg: "mean",
         "min" (similar to every seed) or "max" (similar to any seed).  The seeds and `exclude` are
         never returned; exclude_adj also drops every seed's adj_list row.  filter / select / window as
-        in recommend_interest_all: those in force before the call are restored afterwards."""
+        in recommend_interest_all: those in force before the call are restored afterwards.  collect (a
+        cap in keys): the group's whole window, ranked, for scan_collected()."""
         g = GroupQuery.make(seeds, agg, exclude, exclude_adj)
         k = max(int(k), 0)
         ou = np.zeros(max(k, 1), np.int32)
         os_ = np.zeros(max(k, 1), np.float32)
         oc = np.zeros(1, np.int32)
-        with self._scoped(filter, select, window):
+        with self._scoped(filter, select, window, collect):
             self._check(self._L.pf_recommend_group(self.h, ctypes.byref(g), 1, k, ou.ctypes.data, os_.ctypes.data,
                                                    oc.ctypes.data), "pf_recommend_group")
         return ou[:oc[0]].copy(), os_[:oc[0]].copy()
@@ -838,6 +866,38 @@ class FasEngine:
         out = np.zeros(max(n.value, 1), np.int64)
         self._check(self._L.pf_scan_window_totals(self.h, out.ctypes.data, n.value, ctypes.byref(n)), "pf_scan_window_totals")
         return out[:n.value].copy()
+
+    # -- collector of the all-candidates scans (pf_set_scan_collect): context state like the window
+    def set_scan_collect(self, cap):
+        """Collect every candidate of the window of the following one-query scan calls into a buffer
+        of cap keys (scan_collected); 0 or None clears."""
+        cap = int(cap or 0)
+        self._check(self._L.pf_set_scan_collect(self.h, cap), "pf_set_scan_collect")
+        self._collect = cap
+
+    def clear_scan_collect(self):
+        self.set_scan_collect(0)
+
+    def scan_collected(self):
+        """The last collecting call's (ids, scores, total): everyone in its window, ranked (score desc,
+        uid asc); ids and scores are empty when total exceeded the collector's cap."""
+        n, total = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._L.pf_scan_collected(self.h, None, None, 0, ctypes.byref(n), ctypes.byref(total)), "pf_scan_collected")
+        ids = np.zeros(max(n.value, 1), np.int32)
+        scores = np.zeros(max(n.value, 1), np.float32)
+        self._check(self._L.pf_scan_collected(self.h, ids.ctypes.data, scores.ctypes.data, n.value, ctypes.byref(n),
+                                              ctypes.byref(total)), "pf_scan_collected")
+        return ids[:n.value].copy(), scores[:n.value].copy(), int(total.value)
+
+    def collect_call(self, fn):
+        """fn(window, collect) makes one scan call of this engine with the two passed on as window= and
+        collect=; the callable returned is what collect_all takes."""
+        def call(window, collect):
+            fn(window, collect)
+            if collect is None:
+                return np.zeros(0, np.int32), np.zeros(0, np.float32), int(self.scan_window_totals()[0])
+            return self.scan_collected()
+        return call
 
     def scan_filter_count(self):
         """Candidates of this context's shard that pass the filter in force (all without one)."""
