@@ -461,6 +461,48 @@ public:
         return col.take();
     }
 
+    // Clubs by interest (pokec_fas.h "Clubs by interest"): club recommendations from the NEIGHBOURS of a
+    // user, of a profile given by value or of a group: the candidates of `window` in the all-candidates
+    // ranking (the first `neighbours` of them; 0 = all), each adding its score to every club it lists, in
+    // rank order; (club id, score) ranked (score desc, id asc).  No adj_list row is needed.  The query's
+    // own clubs (the seeds' clubs for a group) are left out unless keep_own.  A window that holds more
+    // than cap candidates throws std::length_error like collect_*; any other failure returns an empty
+    // list and last_error says why.  info (optional) receives the call's pf_clubs_info.
+    Ranked recommend_clubs_by_interest(int user, int topk, int neighbours = 0, const ScoreWindow& window = ScoreWindow(),
+                                       int64_t cap = 1 << 20, bool keep_own = false, pf_clubs_info* info = nullptr) const {
+        return clubs_(topk, neighbours, window, cap, keep_own, info, [&](detail::Engine& e, const pf_clubs_query* q, int k, int32_t* oc,
+                                                                       float* os, int32_t* n, pf_clubs_info* ci) {
+            return pf_recommend_clubs_interest(e.ctx, user, q, k, oc, os, n, ci);
+        });
+    }
+    Ranked recommend_clubs_by_profile(const Profile& A, int topk, int neighbours = 0, const ScoreWindow& window = ScoreWindow(),
+                                      int64_t cap = 1 << 20, bool keep_own = false, const std::vector<int>& exclude = {},
+                                      pf_clubs_info* info = nullptr) const {
+        return clubs_(topk, neighbours, window, cap, keep_own, info, [&](detail::Engine& e, const pf_clubs_query* q, int k, int32_t* oc,
+                                                                       float* os, int32_t* n, pf_clubs_info* ci) {
+            QueryHold h;
+            const pf_query_profile qp = query_of_(e.ctx, A, exclude, h);
+            return pf_recommend_clubs_profile(e.ctx, &qp, q, k, oc, os, n, ci);
+        });
+    }
+    Ranked recommend_clubs_for_group(const std::vector<int>& seeds, int topk, GroupAgg agg = GroupAgg::Mean, int neighbours = 0,
+                                     const ScoreWindow& window = ScoreWindow(), int64_t cap = 1 << 20, bool keep_own = false,
+                                     bool exclude_adj = false, const std::vector<int>& exclude = {}, pf_clubs_info* info = nullptr) const {
+        if (seeds.empty()) return Ranked();
+        return clubs_(topk, neighbours, window, cap, keep_own, info, [&](detail::Engine& e, const pf_clubs_query* q, int k, int32_t* oc,
+                                                                       float* os, int32_t* n, pf_clubs_info* ci) {
+            if (exclude_adj && adj_list)
+                for (int s : seeds) {
+                    const int rc = sync_row_(e, s);
+                    if (rc != PF_OK) return rc;
+                }
+            const std::vector<int32_t> sd(seeds.begin(), seeds.end()), ex(exclude.begin(), exclude.end());
+            const pf_group_query g{sd.data(), (int32_t)sd.size(), (int32_t)agg, exclude_adj ? PF_GROUP_EXCLUDE_ADJ : 0u,
+                                   ex.empty() ? nullptr : ex.data(), (int32_t)ex.size()};
+            return pf_recommend_clubs_group(e.ctx, &g, q, k, oc, os, n, ci);
+        });
+    }
+
     // The group's aggregate score of B, a profile of the map (NaN when B or every seed is not): how
     // well B fits the group.  No exclusion applies: a seed is scored like anyone else.
     float group_similarity(const std::vector<int>& seeds, const Profile& B, GroupAgg agg = GroupAgg::Mean) const {
@@ -558,6 +600,33 @@ private:
             return std::move(all);
         }
     };
+
+    // the three clubs-by-interest calls: call(engine, query, topk, out_club, out_score, out_count, info) -> rc
+    template <class Call>
+    Ranked clubs_(int topk, int neighbours, const ScoreWindow& window, int64_t cap, bool keep_own, pf_clubs_info* info, Call call) const {
+        Ranked out;
+        if (info) *info = pf_clubs_info{0, 0, 0, 0};
+        if (!profiles || topk <= 0) return out;
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return out;
+        pf_clubs_info ci{0, 0, 0, 0};
+        {
+            std::lock_guard<std::mutex> g(e->mu);
+            const pf_scan_window w = window.c_form();
+            const pf_clubs_query q{cap, neighbours, keep_own ? PF_CLUBS_KEEP_OWN : 0u, w.fields ? &w : nullptr};
+            topk = (int)std::min<int64_t>(topk, e->n_club_entries + 1);  // a result never holds more than every club entry
+            std::vector<int32_t> ids((size_t)topk);
+            std::vector<float> sc((size_t)topk);
+            int32_t n = 0;
+            if (call(*e, &q, topk, ids.data(), sc.data(), &n, &ci) != PF_OK) return fail_(e->ctx, out);
+            for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
+        }
+        if (info) *info = ci;
+        if (ci.total > cap)
+            throw std::length_error("clubs by interest: the window holds " + std::to_string(ci.total) + " candidates, above the cap of " +
+                                    std::to_string(cap));
+        return out;
+    }
 
     Ranked by_profile_(const Profile& A, int topk, const std::vector<int>& exclude, const pf_scan_window* window,
                        int64_t* total, Collect* col = nullptr) const {

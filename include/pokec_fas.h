@@ -541,6 +541,57 @@ int pf_set_scan_collect(pf_ctx* ctx, int64_t cap);
 int pf_scan_collected(pf_ctx* ctx, int32_t* out_uid, float* out_score, int64_t out_cap, int64_t* n, int64_t* total);
 
 /*
+ * Clubs by interest: club recommendations from a scan's neighbours ("which clubs", for a stored user,
+ * a profile given by value or a seed audience).  pf_recommend_clubs walks the adj_list; these calls
+ * need none: a user without an adj_list row, a profile that is not in the corpus and a group all get
+ * clubs.  The definition is recommender_clubs.cpp:30-44 and :66-72 (its phase 1) with "friends"
+ * replaced by "neighbours"; there is no reference function.
+ *   Neighbours   The candidates a collecting scan of the query collects ("Collect", "The set"): in the
+ *                shard, passing the context's filter, not excluded, inside `window`, ranked (score
+ *                desc, uid asc) as float scores under the context's field selection; for a group the
+ *                score is the group's aggregate.  With neighbours = M > 0 only the first M of that
+ *                ranking are used.
+ *   Own clubs    A stored user's clubs; a profile's club_ids; the union of a group's kept seeds' clubs.
+ *                Not scored unless PF_CLUBS_KEEP_OWN is set.
+ *   A score      double acc = 0; the neighbours in rank order, each with w = (double)score, skipped
+ *                when w <= 0.0; its club list in profile order, acc += w for every occurrence of the
+ *                club (a repeated club counts as often as it is listed).  The score is (float)acc.
+ *                The order of the adds is part of the contract.
+ *   The list     The clubs with at least one contribution as (club id, score), ordered (score desc,
+ *                club id asc), cut to topk (any topk >= 0; topk = 0 scans nothing and reports zeros).
+ *   info         total = the candidates in the window (exact, whatever cap is); used = the neighbours
+ *                that entered (min(M, total), or total); contributions = the adds made; clubs = the
+ *                clubs with at least one.  NULL is allowed.
+ *   Overflow     total > cap is no error: out_count = 0, info.total is exact and used = 0.
+ *   Empty        An unknown uid, a group with G = 0 and an empty window give out_count = 0.
+ *   State        The calls run the scan with a collector of `cap` keys and a counted window of their
+ *                own for their duration and give the context's window, collector, stored totals and
+ *                pf_scan_collected result back exactly as they found them.  The filter and selection
+ *                in force apply as they do to the scan.
+ *   Refusals     PF_EINVAL: a NULL context, query or out_count; NULL outputs with topk > 0; topk < 0;
+ *                cap <= 0 or above INT32_MAX; neighbours < 0; unknown bits in flags; a window the
+ *                window setter would refuse; what the profile or group call underneath refuses.
+ *                PF_EUNSUPP: a context sharded by pf_set_shard into more than one shard (partial sums
+ *                of shards cannot be merged in rank order); more than INT32_MAX contributions; what
+ *                the call underneath refuses.  PF_ENOMEM: a device buffer cannot be had.
+ */
+#define PF_CLUBS_KEEP_OWN 1u
+typedef struct pf_clubs_query {
+    int64_t  cap;          /* most candidates the window may hold; > 0, <= INT32_MAX            */
+    int32_t  neighbours;   /* M: the first M of the ranking enter; 0 = the whole window          */
+    uint32_t flags;
+    const pf_scan_window* window;   /* NULL = no window (every rankable candidate)               */
+} pf_clubs_query;
+typedef struct pf_clubs_info { int64_t total, used, contributions, clubs; } pf_clubs_info;
+
+int pf_recommend_clubs_interest(pf_ctx* ctx, int32_t uid, const pf_clubs_query* q, int32_t topk,
+                                int32_t* out_club, float* out_score, int32_t* out_count, pf_clubs_info* info);
+int pf_recommend_clubs_profile(pf_ctx* ctx, const pf_query_profile* profile, const pf_clubs_query* q, int32_t topk,
+                               int32_t* out_club, float* out_score, int32_t* out_count, pf_clubs_info* info);
+int pf_recommend_clubs_group(pf_ctx* ctx, const pf_group_query* group, const pf_clubs_query* q, int32_t topk,
+                             int32_t* out_club, float* out_score, int32_t* out_count, pf_clubs_info* info);
+
+/*
  * Device-resident all-candidates scan for the multi-GPU bench: scores the
  * queries against this context's shard and writes, per query, `topk` packed
  * 64-bit keys to DEVICE memory d_keys[nq*topk] on `stream` (a hipStream_t).

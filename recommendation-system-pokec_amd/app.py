@@ -29,6 +29,13 @@ and one route of the engine's own:
                                         "all": <cap> asks for the WHOLE window in one call (pokec_fas.h "Collect"): the
                                         reply's list is everyone in it, ranked, whatever topk is, and ends with
                                         "total"; a window above cap answers an empty list, "total" and "overflow": true.
+    POST /api/match and /api/group      "top_clubs": <topk> adds "clubs" to the reply's recommendations: the clubs of the
+                                        window's neighbours scored by their similarity (pokec_fas.h "Clubs by
+                                        interest"), with names; "neighbours": <M> uses only the first M of the ranking.
+                                        (In /api/match "clubs" is the profile's own club list, hence the other name.)
+    GET /api/clubs/{uid}?topk=20&min_score=&neighbours=&cap=
+                                        the api_cli JSON line for "CLUBS ...": club recommendations for a stored user
+                                        from its most similar users, whether or not it has an adj_list row.
 
 What differs, because the reference's file cannot run as written:
   * it has unresolved merge-conflict markers (app.py:38-42, 147-159); the start-up wait here
@@ -88,7 +95,44 @@ def window_words(body):
         if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 2**31 - 1:
             raise ValueError("all must be a cap between 1 and 2147483647")
         words.append("all=%d" % v)
+    return words + club_words(body)
+
+
+def club_words(body):
+    """The clubs-by-interest words of a /api/match or /api/group body: top_clubs (the "clubs" list's
+    topk) and neighbours (M, with top_clubs only)."""
+    words = []
+    v = body.get("top_clubs")
+    if v is not None:
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 1 << 20:
+            raise ValueError("top_clubs must be between 1 and 1048576")
+        words.append("topclubs=%d" % v)
+    m = body.get("neighbours")
+    if m is not None:
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= 2**31 - 1:
+            raise ValueError("neighbours must be between 0 and 2147483647")
+        if v is None:
+            raise ValueError("neighbours needs top_clubs")
+        words.append("m=%d" % m)
     return words
+
+
+def clubs_line(uid, topk=20, min_score=None, neighbours=None, cap=None):
+    """The api_cli "CLUBS ..." line of GET /api/clubs/{uid}; ValueError on a value out of range."""
+    for name, v, lo, hi in (("uid", uid, 0, 2**31 - 1), ("topk", topk, 0, 1 << 20), ("neighbours", neighbours, 0, 2**31 - 1),
+                            ("cap", cap, 1, 2**31 - 1)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi):
+            raise ValueError("%s must be between %d and %d" % (name, lo, hi))
+    words = ["CLUBS", str(topk), str(uid)]
+    if min_score is not None:
+        if isinstance(min_score, bool) or not isinstance(min_score, (int, float)) or min_score != min_score:
+            raise ValueError("min_score must be a number")
+        words.append("min=" + repr(float(min_score)))
+    if neighbours is not None:
+        words.append("m=%d" % neighbours)
+    if cap is not None:
+        words.append("cap=%d" % cap)
+    return " ".join(words)
 
 
 def match_line(body):
@@ -97,7 +141,7 @@ def match_line(body):
     if not isinstance(body, dict):
         raise ValueError("the body must be a JSON object")
     unknown = set(body) - {"topk", "public", "gender", "completion", "age", "region", "clubs", "friends", "exclude", "tokens",
-                           "min_score", "after", "count", "all"}
+                           "min_score", "after", "count", "all", "top_clubs", "neighbours"}
     if unknown:
         raise ValueError("unknown field: " + sorted(unknown)[0])
 
@@ -133,7 +177,8 @@ def group_line(body):
     "mean", "exclude": [...], "exclude_adj": false} and the window's fields (window_words); ValueError on a field of the wrong shape."""
     if not isinstance(body, dict):
         raise ValueError("the body must be a JSON object")
-    unknown = set(body) - {"seeds", "topk", "agg", "exclude", "exclude_adj", "min_score", "after", "count", "all"}
+    unknown = set(body) - {"seeds", "topk", "agg", "exclude", "exclude_adj", "min_score", "after", "count", "all",
+                           "top_clubs", "neighbours"}
     if unknown:
         raise ValueError("unknown field: " + sorted(unknown)[0])
 
@@ -324,6 +369,14 @@ def create_app(root, cli_cmd=None, load_users=None, ready_timeout=120.0, request
     def api_group(body: dict):
         try:
             line = group_line(body)
+        except (ValueError, TypeError) as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        return JSONResponse(cli_json(line))
+
+    @app.get("/api/clubs/{uid}")
+    def api_clubs(uid: int, topk: int = 20, min_score: float = None, neighbours: int = None, cap: int = None):
+        try:
+            line = clubs_line(uid, topk, min_score, neighbours, cap)
         except (ValueError, TypeError) as e:
             raise HTTPException(status_code=422, detail=str(e))
         return JSONResponse(cli_json(line))

@@ -12,6 +12,11 @@
 // GROUP <topk> <mean|min|max> <uid> <uid> ... [noadj] [exclude=<uid,uid,...>] is the group query
 // (pf_recommend_group): the users most similar to the listed seed users as a group; noadj also drops
 // every seed's adj_list row.  It answers {"recommendations":{"group":[..]}} or the same two errors.
+// MATCH and GROUP take topclubs=<topk> [m=<M>] (match_line.h): the reply's "recommendations" gain a
+// "clubs" list with names, the clubs of the line's window scored by its neighbours
+// (pf_recommend_clubs_profile / _group).  CLUBS <topk> <uid> [min=<float>] [m=<M>] [cap=<n>] is the same
+// for a stored user (pf_recommend_clubs_interest): {"recommendations":{"clubs":[..]},"total":N,"used":U}
+// and "overflow":true when the window holds more than cap (default 1048576) candidates.
 //
 //   pokec_api_cli [load_users] [--root DIR] [--device N] [--no-cap] [--cache PATH]
 //
@@ -133,6 +138,16 @@ struct CollectScope {
         return true;
     }
 };
+
+// The "clubs" list of a MATCH / GROUP line with topclubs=: the line's window (its count word plays no
+// part), its all=<cap> as the cap when given
+pf_clubs_query clubs_query(const pf_scan_window& win, int64_t collect, int32_t m) {
+    pf_clubs_query q{};
+    q.cap = collect > 0 ? collect : (int64_t)1 << 20;
+    q.neighbours = m > 0 ? m : 0;
+    q.window = win.fields ? &win : nullptr;
+    return q;
+}
 
 }  // namespace
 
@@ -269,9 +284,22 @@ int main(int argc, char** argv) {
                 std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
                 continue;
             }
+            List cl(m.club_topk > 0 ? m.club_topk : 1);
+            if (m.club_topk > 0) {
+                const pf_clubs_query cq = clubs_query(m.window, m.collect, m.club_m);
+                if (pf_recommend_clubs_profile(ctx, &q, &cq, m.club_topk, cl.id.data(), cl.score.data(), &cl.n, nullptr) != PF_OK) {
+                    std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
+                    std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
+                    continue;
+                }
+            }
             std::ostringstream os;
             os << "{\"recommendations\":{";
             write_list(os, "interest", r, nullptr);
+            if (m.club_topk > 0) {
+                os << ",";
+                write_list(os, "clubs", cl, ds);
+            }
             os << "}" << (m.collect > 0 ? tail : ws.tail(r, m.topk)) << "}";
             std::cout << os.str() << std::endl;
             continue;
@@ -286,6 +314,7 @@ int main(int argc, char** argv) {
             std::vector<int32_t> seeds, excl;
             pf_scan_window win{};
             int64_t collect = 0;
+            int32_t club_topk = 0, club_m = -1;
             uint32_t flags = 0;
             bool ok = !iss.fail() && topk >= 0 && (agg == "mean" || agg == "min" || agg == "max");
             auto number = [](const std::string& t, int32_t& v) {
@@ -300,10 +329,13 @@ int main(int argc, char** argv) {
                 int32_t v = 0;
                 const int ww = pokec::parse_window_word(w, win);
                 const int cw = ww == 0 ? pokec::parse_collect_word(w, collect) : 0;
+                const int kw = ww == 0 && cw == 0 ? pokec::parse_clubs_word(w, club_topk, club_m) : 0;
                 if (ww != 0) {
                     ok = ww > 0;
                 } else if (cw != 0) {
                     ok = cw > 0;
+                } else if (kw != 0) {
+                    ok = kw > 0;
                 } else if (w == "noadj") {
                     flags |= PF_GROUP_EXCLUDE_ADJ;
                 } else if (w.rfind("exclude=", 0) == 0) {
@@ -318,8 +350,9 @@ int main(int argc, char** argv) {
                     seeds.push_back(v);
                 }
             }
-            if (!ok || seeds.empty()) {
-                std::cout << "{\"error\":\"bad request\",\"detail\":\"GROUP <topk> <mean|min|max> <uid>... [noadj] [exclude=<uid,...>] [min=<float>] [after=<hex>:<uid>] [count] [all=<cap>]\"}"
+            if (!ok || seeds.empty() || (club_m >= 0 && club_topk == 0)) {
+                std::cout << "{\"error\":\"bad request\",\"detail\":\"GROUP <topk> <mean|min|max> <uid>... [noadj] [exclude=<uid,...>] [min=<float>] [after=<hex>:<uid>] [count] [all=<cap>]"
+                          << (club_topk > 0 || club_m >= 0 ? " [topclubs=<topk>] [m=<M>]" : "") << "\"}"
                           << std::endl;
                 continue;
             }
@@ -336,10 +369,60 @@ int main(int argc, char** argv) {
                 std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
                 continue;
             }
+            List cl(club_topk > 0 ? club_topk : 1);
+            if (club_topk > 0) {
+                const pf_clubs_query cq = clubs_query(win, collect, club_m);
+                if (pf_recommend_clubs_group(ctx, &q, &cq, club_topk, cl.id.data(), cl.score.data(), &cl.n, nullptr) != PF_OK) {
+                    std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
+                    std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
+                    continue;
+                }
+            }
             std::ostringstream os;
             os << "{\"recommendations\":{";
             write_list(os, "group", r, nullptr);
+            if (club_topk > 0) {
+                os << ",";
+                write_list(os, "clubs", cl, ds);
+            }
             os << "}" << (collect > 0 ? tail : ws.tail(r, topk)) << "}";
+            std::cout << os.str() << std::endl;
+            continue;
+        }
+        if (cmd == "CLUBS") {
+            // CLUBS <topk> <uid> [min=<float>] [m=<M>] [cap=<n>]
+            std::istringstream iss(line);
+            std::string w;
+            long long topk = -1, cu = -1, capv = (long long)1 << 20;
+            iss >> w >> topk >> cu;
+            pf_scan_window win{};
+            int32_t unused_topk = 0, cm = -1;
+            bool ok = !iss.fail() && topk >= 0 && topk <= (1 << 20) && cu >= 0 && cu <= 2147483647LL;
+            while (ok && iss >> w) {
+                if (w.rfind("min=", 0) == 0) ok = pokec::parse_window_word(w, win) > 0;
+                else if (w.rfind("m=", 0) == 0) ok = pokec::parse_clubs_word(w, unused_topk, cm) > 0;
+                else if (w.rfind("cap=", 0) == 0) ok = w.size() > 4 && w[4] != '+' && w[4] != '-' && pokec::match_detail::to_int(w.substr(4), 1, 2147483647LL, capv);
+                else ok = false;
+            }
+            if (!ok) {
+                std::cout << "{\"error\":\"bad request\",\"detail\":\"CLUBS <topk> <uid> [min=<float>] [m=<M>] [cap=<n>]\"}" << std::endl;
+                continue;
+            }
+            pf_clubs_query cq{};
+            cq.cap = (int64_t)capv;
+            cq.neighbours = cm > 0 ? cm : 0;
+            cq.window = win.fields ? &win : nullptr;
+            List cl(topk > 0 ? (int)topk : 1);
+            pf_clubs_info ci{};
+            if (pf_recommend_clubs_interest(ctx, (int32_t)cu, &cq, (int32_t)topk, cl.id.data(), cl.score.data(), &cl.n, &ci) != PF_OK) {
+                std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
+                std::cout << "{\"error\":\"engine failure\",\"detail\":\"" << json_escape(pf_last_error(ctx)) << "\"}" << std::endl;
+                continue;
+            }
+            std::ostringstream os;
+            os << "{\"recommendations\":{";
+            write_list(os, "clubs", cl, ds);
+            os << "},\"total\":" << ci.total << ",\"used\":" << ci.used << (ci.total > cq.cap ? ",\"overflow\":true" : "") << "}";
             std::cout << os.str() << std::endl;
             continue;
         }

@@ -12,6 +12,11 @@
 //         [all=<cap>]      1 <= cap <= 2147483647
 // The reply's list is then every candidate of the window, ranked, whatever topk is, and the reply ends
 // with "total":N; when N > cap the list is empty and "overflow":true follows.
+// The words of clubs by interest (pokec_fas.h "Clubs by interest"), on both commands:
+//         [topclubs=<topk>] [m=<M>]      1 <= topk <= 1048576, 0 <= M <= 2147483647
+// topclubs adds a "clubs" list to the reply: the clubs of the window's first M neighbours (m=0 or no m:
+// the whole window), scored by the neighbours' scores, with names.  (MATCH's clubs=<id,..> is the
+// profile's own club list, so the new word cannot be spelt clubs=.)  m without topclubs is malformed.
 //
 // A field that is not given is missing; an empty region part ("region=3,,27") is missing; c<t> is
 // text column t of the engine's list, as token ids (the text -> id ETL is not part of the engine).
@@ -36,6 +41,8 @@ struct MatchLine {
     std::vector<int32_t> exclude;
     pf_scan_window window{};  // fields == 0: the line has none of the window's words
     int64_t collect = 0;      // all=<cap>; 0: the line has no such word
+    int32_t club_topk = 0;    // topclubs=<topk>; 0: the line has no such word
+    int32_t club_m = -1;      // m=<M>; -1: the line has no such word
     std::vector<std::vector<std::pair<int32_t, int32_t>>> cols;  // [n_cols] (tid, tf) in the line's order
     // the C struct over this object's arrays (valid while the object lives and is not changed)
     std::vector<int64_t> off;
@@ -123,6 +130,18 @@ inline int parse_collect_word(const std::string& w, int64_t& cap) {
     cap = (int64_t)v;
     return 1;
 }
+// One word of a MATCH / GROUP / CLUBS line as a word of clubs by interest: 1 = taken, 0 = another word,
+// -1 = malformed (not a number, topclubs below 1 or above 2^20, m below 0 or above INT32_MAX)
+inline int parse_clubs_word(const std::string& w, int32_t& topk, int32_t& m) {
+    const bool is_top = w.rfind("topclubs=", 0) == 0;
+    if (!is_top && w.rfind("m=", 0) != 0) return 0;
+    const std::string val = w.substr(is_top ? 9 : 2);
+    long long v = 0;
+    if (val.empty() || val[0] == '+' || val[0] == '-' || !match_detail::to_int(val, is_top ? 1 : 0, is_top ? (1 << 20) : INT32_MAX, v))
+        return -1;
+    (is_top ? topk : m) = (int32_t)v;
+    return 1;
+}
 // the cursor token of a result: its score's float bits and its uid
 inline std::string window_cursor(float score, int32_t uid) {
     uint32_t bits = 0;
@@ -151,6 +170,9 @@ inline bool parse_match_line(const std::string& rest, int n_cols, MatchLine& m, 
         const int cw = parse_collect_word(w, m.collect);
         if (cw < 0) { why = "bad value: " + w; return false; }
         if (cw > 0) continue;
+        const int kw = parse_clubs_word(w, m.club_topk, m.club_m);
+        if (kw < 0) { why = "bad value: " + w; return false; }
+        if (kw > 0) continue;
         const size_t eq = w.find('=');
         if (eq == std::string::npos || eq == 0) { why = "not key=value: " + w; return false; }
         const std::string key = w.substr(0, eq), val = w.substr(eq + 1);
@@ -201,6 +223,7 @@ inline bool parse_match_line(const std::string& rest, int n_cols, MatchLine& m, 
         }
         if (!ok) { why = "bad value: " + w; return false; }
     }
+    if (m.club_m >= 0 && m.club_topk == 0) { why = "m= without topclubs="; return false; }
     return true;
 }
 

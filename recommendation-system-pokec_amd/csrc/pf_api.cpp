@@ -1665,6 +1665,7 @@ int pf_set_shard(pf_ctx* c, int32_t shard, int32_t nshards) {
     };
     c->tile_begin = bound(shard);
     c->tile_end = bound(shard + 1);
+    c->n_shards = nshards;
     // postings scan: contiguous block ranges of equal posting weight.  A block's cost is a
     // fixed part (headers, ranges, top-k: ~60 of ~210 us at cfg 2) plus
     // its share of the lists a query names, i.e. of the postings entries (tokens, clubs,
@@ -2012,3 +2013,4 @@ int pf_profile_read(pf_ctx* c, double* total_ms, int64_t* launches) {
 
 // ---------------------------------------------------------------- group query (pf_recommend_group ...)
 #include "pf_group_api.h"
+#include "pf_clubs_api.h"

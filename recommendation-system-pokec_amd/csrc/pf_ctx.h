@@ -22,39 +22,14 @@
 #include <unistd.h>
 
 #include "pf_batch.h"
+#include "pf_clubsum.h"
+#include "pf_dbuf.h"
 #include "pf_jobs.h"
 #include "pf_store.h"
 #include "pf_window.h"
 #include "pokec_fas.h"
 
 namespace pf {
-
-struct DBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max<size_t>(bytes, 4096);
-        want = want + want / 4;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    // per-call workspaces: grow to twice the request (at least 1 MiB), so the sizes of
-    // successive batches settle after a few calls instead of re-allocating (hipFree syncs)
-    hipError_t reserve(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        return ensure(std::max<size_t>(2 * bytes, 1u << 20));
-    }
-    ~DBuf() {
-        if (p) (void)hipFree(p);
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 // Pinned host buffer that only grows (contents are not initialised)
 struct PinBuf {
@@ -104,6 +79,7 @@ struct JobsState {
     std::unordered_map<int32_t, int32_t> xnode;  // uid -> node for adj_list uids without a profile
     std::vector<int32_t> dense_node;             // uid -> node (-1 none) when the uids are dense
     std::vector<int32_t> g_uid, g_len;           // host mirrors (new uids from pf_set_adj append nodes)
+    std::vector<int32_t> club_id;                // host mirror of js.club_id: dense club index -> club id, ascending
     bool nodes_dirty = false;
     ImgPlan img;                                 // per idx: the sizes of its query image (pf_jobs.h)
     std::vector<uint32_t> img_stamp;             // per idx: the layout pass that last gave it an image ...
@@ -262,6 +238,9 @@ struct pf_ctx {
     std::vector<uint64_t> coll_keys;     // ranked; empty on overflow
     int64_t coll_total = 0;
     bool coll_set = false;
+    // clubs by interest (pf_clubsum.h): the stage's workspaces, grown on demand
+    pf::ClubSumWs clubs_ws;
+    int32_t n_shards = 1;                // pf_set_shard's count (the clubs-by-interest calls refuse more than one)
     uint64_t* collect_buf() const { return (win.fields & pf::kWinCollect) ? static_cast<uint64_t*>(d_coll.p) : nullptr; }
     uint32_t collect_cap_dev() const { return (win.fields & pf::kWinCollect) ? (uint32_t)coll_cap : 0u; }
     // pinned staging ring for the per-call query upload (a slot is reused only after

@@ -280,6 +280,7 @@ int jobs_open(pf_ctx* c) {
     g.club_dense = J.d_club_dense.as<int32_t>();
     g.club_id = J.d_club_id.as<int32_t>();
     g.n_club_ids = (int32_t)club_id.size();
+    J.club_id = std::move(club_id);
     J.edited.clear();
     J.edit_gen = 1;
     J.view_gen = 0;

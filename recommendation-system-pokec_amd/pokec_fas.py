@@ -44,7 +44,8 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_recommend_interest_profile", "pf_fas_profile_pairs", "pf_fas_profile_pairs_terms",
            "pf_recommend_interest_profile_terms",
            "pf_recommend_group", "pf_group_scores", "pf_group_plan_of", "pf_group_image_lds",
-           "pf_set_scan_window", "pf_scan_window_totals", "pf_set_scan_collect", "pf_scan_collected"]
+           "pf_set_scan_window", "pf_scan_window_totals", "pf_set_scan_collect", "pf_scan_collected",
+           "pf_recommend_clubs_interest", "pf_recommend_clubs_profile", "pf_recommend_clubs_group"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
               "pf_dataset_profile_order", "pf_dataset_adj_order", "pf_dataset_profile_json", "pf_dataset_club_name",
@@ -349,6 +350,24 @@ class GroupQuery(ctypes.Structure):
         return g
 
 
+PF_CLUBS_KEEP_OWN = 1
+
+
+class ClubsQuery(ctypes.Structure):
+    """pf_clubs_query: the neighbours of a clubs-by-interest call (cap, M, flags, window)."""
+    _fields_ = [("cap", ctypes.c_int64), ("neighbours", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("window", ctypes.c_void_p)]
+
+
+class ClubsInfo(ctypes.Structure):
+    """pf_clubs_info: candidates in the window, neighbours that entered, adds made, clubs scored."""
+    _fields_ = [("total", ctypes.c_int64), ("used", ctypes.c_int64), ("contributions", ctypes.c_int64),
+                ("clubs", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {"total": self.total, "used": self.used, "contributions": self.contributions, "clubs": self.clubs}
+
+
 class GroupPlan(ctypes.Structure):
     """pf_group_plan: what a group scan launches (kept seeds, passes, global-memory images, bytes)."""
     _fields_ = [("n_seeds", ctypes.c_int32), ("n_passes", ctypes.c_int32), ("n_global", ctypes.c_int32),
@@ -434,6 +453,9 @@ def lib():
         L.pf_set_scan_window.argtypes = [V, ctypes.POINTER(ScanWindow)]
         L.pf_scan_window_totals.argtypes = [V, V, I32, ctypes.POINTER(I32)]
         L.pf_set_scan_collect.argtypes = [V, I64]
+        L.pf_recommend_clubs_interest.argtypes = [V, ctypes.c_int32, V, ctypes.c_int32, V, V, V, V]
+        L.pf_recommend_clubs_profile.argtypes = [V, V, V, ctypes.c_int32, V, V, V, V]
+        L.pf_recommend_clubs_group.argtypes = [V, V, V, ctypes.c_int32, V, V, V, V]
         L.pf_scan_collected.argtypes = [V, V, V, I64, ctypes.POINTER(I64), ctypes.POINTER(I64)]
         L.pf_merge_keys_async.argtypes = [V, V, I32, I32, I32, V, V]
         L.pf_decode_keys.argtypes = [V, I32, V, V, V]
@@ -762,6 +784,48 @@ class FasEngine:
             self._check(self._L.pf_recommend_group(self.h, ctypes.byref(g), 1, k, ou.ctypes.data, os_.ctypes.data,
                                                    oc.ctypes.data), "pf_recommend_group")
         return ou[:oc[0]].copy(), os_[:oc[0]].copy()
+
+    # -- clubs by interest (pf_clubs_query): club recommendations from a scan's neighbours
+    def _clubs_interest(self, fn, name, arg, k, neighbours, cap, window, keep_own, filter, select):
+        q = ClubsQuery()
+        q.cap, q.neighbours, q.flags = int(cap), int(neighbours), PF_CLUBS_KEEP_OWN if keep_own else 0
+        q.window = None if window is None else ctypes.addressof(window)
+        k = max(int(k), 0)
+        oc_ = np.zeros(max(k, 1), np.int32)
+        os_ = np.zeros(max(k, 1), np.float32)
+        n = np.zeros(1, np.int32)
+        info = ClubsInfo()
+        with self._scoped(filter, select):
+            self._check(fn(self.h, arg, ctypes.byref(q), k, oc_.ctypes.data, os_.ctypes.data, n.ctypes.data,
+                           ctypes.byref(info)), name)
+        return oc_[:n[0]].copy(), os_[:n[0]].copy(), info.as_dict()
+
+    def recommend_clubs_interest(self, uid, k, neighbours=0, cap=1 << 20, window=None, keep_own=False, filter=None,
+                                 select=None):
+        """Clubs by interest for a stored user: (club_ids, scores, info).  The neighbours are the
+        candidates of `window` (a ScanWindow; None = everyone rankable) in the all-candidates ranking,
+        the first `neighbours` of them (0 = all); each adds its score to every club it lists, in rank
+        order; the user's own clubs are left out unless keep_own.  cap: the most candidates the window
+        may hold (more: an empty list, info["total"] says how many).  filter / select as in
+        recommend_interest_all.  Nothing in force on the engine changes."""
+        return self._clubs_interest(self._L.pf_recommend_clubs_interest, "pf_recommend_clubs_interest", int(uid), k,
+                                    neighbours, cap, window, keep_own, filter, select)
+
+    def recommend_clubs_profile(self, profile, k, neighbours=0, cap=1 << 20, window=None, keep_own=False, filter=None,
+                                select=None):
+        """recommend_clubs_interest for a QueryProfile (a person who is not a user of the corpus); its
+        own clubs are its club list."""
+        ps, arr = self._profile_array(profile)
+        return self._clubs_interest(self._L.pf_recommend_clubs_profile, "pf_recommend_clubs_profile", ctypes.byref(arr), k,
+                                    neighbours, cap, window, keep_own, filter, select)
+
+    def recommend_clubs_group(self, seeds, k, agg="mean", exclude=(), exclude_adj=False, neighbours=0, cap=1 << 20,
+                              window=None, keep_own=False, filter=None, select=None):
+        """recommend_clubs_interest for a group of seed users (as recommend_group); the own clubs are
+        the union of the seeds' clubs."""
+        g = GroupQuery.make(seeds, agg, exclude, exclude_adj)
+        return self._clubs_interest(self._L.pf_recommend_clubs_group, "pf_recommend_clubs_group", ctypes.byref(g), k,
+                                    neighbours, cap, window, keep_own, filter, select)
 
     def group_scores(self, seeds, b_uid, agg="mean", select=None):
         """The group's aggregate score of each listed user (NaN for an unknown uid), with no filter and
