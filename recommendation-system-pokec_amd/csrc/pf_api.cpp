@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "pf_batch.h"
+#include "pf_collect.h"
 #include "pf_ctx.h"
 #include "pf_debug.h"
 #include "pf_kernels.h"
@@ -350,79 +351,79 @@ uint32_t post_image_lds(const pf::QPostHead* h) {
 }
 // LDS a filtered / windowed launch takes on top of an image's (the filter's and the window's words;
 // pf_kernels.h kFiltLds, kWinLds)
-uint32_t filt_lds(const pf_ctx* c) { return (c->filt.fields ? pf::kFiltLds : 0u) + (c->win.fields ? pf::kWinLds : 0u); }
+uint32_t filt_lds(const pf::ScanCall& C) { return (C.filt.fields ? pf::kFiltLds : 0u) + (C.win.fields ? pf::kWinLds : 0u); }
 
-// A counted synchronous call (a window with PF_WIN_COUNT): the launches write each query's count to
-// its row of d_totals, zeroed first (an unknown uid and an empty group stay 0); finish() brings the
-// rows to win_totals after the call's launches.  Not counted: every member function does nothing.
-struct CountScope {
+// One synchronous all-candidates call: by uid, by profile or by group, and the scan under a clubs
+// call.  begin() refuses what a collector cannot serve, readies the result rows and the count words
+// and makes the call's options a value (`call`, pf_scan_call.h), which the caller hands to its
+// launches; keys() brings rows back and decodes them; finish() reads the counts and, for a
+// collecting call, sorts the keys.  Rows: the launches get absolute result rows (row r of d_out,
+// count word r) and the base of the count words; a launch that counts one query into word 0 names
+// its row (scan_post_one, a group's passes).
+struct SyncScan {
     pf_ctx* c;
-    int n;
-    bool on;
-    CountScope(pf_ctx* ctx, int nq) : c(ctx), n(nq), on((ctx->win.fields & pf::kWinCount) != 0u && nq > 0) {}
-    ~CountScope() { c->cur_totals = nullptr; }
-    int begin() {
-        if (!on) return PF_OK;
-        HIPCHK(c, c->d_totals.ensure((size_t)n * sizeof(uint32_t)));
-        HIPCHK(c, hipMemsetAsync(c->d_totals.p, 0, (size_t)n * sizeof(uint32_t), c->stream));
-        c->cur_totals = c->d_totals.as<uint32_t>();
-        return PF_OK;
-    }
-    void at(size_t row0) { if (on) c->cur_totals = c->d_totals.as<uint32_t>() + row0; }
-    int finish() {
-        c->cur_totals = nullptr;
-        if (!on) return PF_OK;
-        std::vector<uint32_t> v((size_t)n);
-        HIPCHK(c, hipMemcpyAsync(v.data(), c->d_totals.p, v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->win_totals.assign(v.begin(), v.end());
-        c->win_totals_set = true;
-        return PF_OK;
-    }
-};
+    pf_scan_window win;   // the caller's own window (validated)
+    int64_t cap;          // the collector's cap in keys; 0: none
+    // the totals (only under the caller's own PF_WIN_COUNT) and the collected keys go to the context
+    // (pf_scan_window_totals, pf_scan_collected).  false (the clubs calls): the context keeps what
+    // it had; the total stays here and the sorted keys on the device (d_coll_sorted)
+    bool store;
+    pf::ScanCall call{};
+    int nq = 0;
+    int64_t total = 0;    // a collecting call's matches, after finish()
+    explicit SyncScan(pf_ctx* ctx) : c(ctx), win(ctx->win_pub), cap(ctx->coll_cap), store(true) {}
+    SyncScan(pf_ctx* ctx, const pf_scan_window& w, int64_t k) : c(ctx), win(w), cap(k), store(false) {}
 
-// A collecting synchronous call (pf_set_scan_collect in force, topk > 0): for its own duration the
-// context's window carries kWinCollect | kWinCount, so the call's one launch takes the windowed code,
-// holds K5's theta at the window's seed, counts, and appends (collect_buf()).  Constructed before the
-// call's CountScope, which then counts whether or not the caller asked for PF_WIN_COUNT; finish()
-// comes after the CountScope's: it takes the total, gives the caller's totals back when the count was
-// not theirs, sorts the keys when they fit and brings them to coll_keys.  No collector: every member
-// function does nothing.
-struct CollectScope {
-    pf_ctx* c;
-    bool on;
-    pf::ScanWindow saved;
-    std::vector<int64_t> saved_totals;
-    bool saved_totals_set = false;
-    explicit CollectScope(pf_ctx* ctx) : c(ctx), on(ctx->coll_cap > 0), saved(ctx->win) {}
-    ~CollectScope() { c->win = saved; }
-    int begin(int nq) {
-        if (nq == 0) on = false;  // a call of no queries scans nothing
-        if (!on) return PF_OK;
-        if (nq != 1) return c->fail(PF_EUNSUPP, "scan collect: one query (or group) per collecting call");
-        saved_totals = c->win_totals;
-        saved_totals_set = c->win_totals_set;
-        c->win.fields |= pf::kWinCollect | pf::kWinCount;
-        return PF_OK;
-    }
-    int finish() {
-        c->win = saved;
-        if (!on) return PF_OK;
-        const int64_t total = c->win_totals.empty() ? 0 : c->win_totals[0];
-        if (!(saved.fields & pf::kWinCount)) {
-            c->win_totals.swap(saved_totals);
-            c->win_totals_set = saved_totals_set;
+    // n queries (or groups) into `rows` rows of d_out, empty (0xFF) first when `fill`
+    int begin(int n, size_t rows, int topk, bool fill) {
+        nq = n;
+        if (n == 0) cap = 0;  // a call of no queries scans nothing
+        if (cap > 0 && n != 1) return c->fail(PF_EUNSUPP, "scan collect: one query (or group) per collecting call");
+        HIPCHK(c, c->d_out.ensure(rows * topk * sizeof(uint64_t)));
+        if (fill) HIPCHK(c, hipMemsetAsync(c->d_out.p, 0xFF, rows * topk * sizeof(uint64_t), c->stream));
+        // a collecting call counts whether or not the caller asked for it: the total is the count word.
+        // Zeroed first: an unknown uid and an empty group stay 0
+        const bool counted = n > 0 && ((win.fields & PF_WIN_COUNT) || cap > 0);
+        if (counted) {
+            HIPCHK(c, c->d_totals.ensure((size_t)n * sizeof(uint32_t)));
+            HIPCHK(c, hipMemsetAsync(c->d_totals.p, 0, (size_t)n * sizeof(uint32_t), c->stream));
         }
-        c->coll_keys.clear();
-        c->coll_total = total;
-        c->coll_set = true;
-        if (total == 0 || total > c->coll_cap) return PF_OK;
+        call = pf::make_scan_call(c->filt, c->sel, win, c->hc.uid.data(), c->hc.uid.size(), cap, c->d_coll.as<uint64_t>(),
+                                  counted ? c->d_totals.as<uint32_t>() : nullptr);
+        return PF_OK;
+    }
+    // rows [0, n) of d_out on the host, decoded; launched: a launch ran, whose events time the call
+    int keys(int n, int topk, bool launched, int32_t* ou, float* os, int32_t* oc) {
+        std::vector<uint64_t> host((size_t)n * topk);
+        HIPCHK(c, hipMemcpyAsync(host.data(), c->d_out.p, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (launched && c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
+        for (int i = 0; i < n; ++i) pf_decode_keys(&host[(size_t)i * topk], topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
+        return PF_OK;
+    }
+    int finish() {
+        if (!call.totals) return PF_OK;
+        std::vector<uint32_t> v((size_t)nq);
+        HIPCHK(c, hipMemcpyAsync(v.data(), call.totals, v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (store && (win.fields & PF_WIN_COUNT)) {
+            c->win_totals.assign(v.begin(), v.end());
+            c->win_totals_set = true;
+        }
+        if (cap <= 0) return PF_OK;
+        total = v[0];
+        if (store) {
+            c->coll_keys.clear();
+            c->coll_total = total;
+            c->coll_set = true;
+        }
+        if (total == 0 || total > cap) return PF_OK;
         size_t tmp_b = 0;
         HIPCHK(c, pf::collect_sort_bytes(total, &tmp_b));
         HIPCHK(c, c->d_coll_tmp.ensure(std::max<size_t>(tmp_b, 16)));
         HIPCHK(c, c->d_coll_sorted.ensure((size_t)total * sizeof(uint64_t)));
-        HIPCHK(c, pf::collect_sort(c->d_coll.as<uint64_t>(), c->d_coll_sorted.as<uint64_t>(), total, c->d_coll_tmp.p, tmp_b,
-                                   c->stream));
+        HIPCHK(c, pf::collect_sort(call.collect, c->d_coll_sorted.as<uint64_t>(), total, c->d_coll_tmp.p, tmp_b, c->stream));
+        if (!store) return PF_OK;
         c->coll_keys.resize((size_t)total);
         HIPCHK(c, hipMemcpyAsync(c->coll_keys.data(), c->d_coll_sorted.p, (size_t)total * sizeof(uint64_t),
                                  hipMemcpyDeviceToHost, c->stream));
@@ -593,14 +594,15 @@ int stage_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, 
 // launch's stop event.  place(ln, ls, Q) puts the query where the launch reads it and fills Q (its row
 // a zero: `out` is the row's address): scan_post uploads it, scan_post_resident points into the images.
 template <class Place>
-int scan_post_one(pf_ctx* c, uint32_t var_lds, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed, Place place) {
+int scan_post_one(pf_ctx* c, const pf::ScanCall& C, uint32_t var_lds, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed,
+                  Place place) {
     LaneUse lu;
     int rc = lane_begin(c, s, lu);
     if (rc != PF_OK) return rc;
     pf_ctx::ScanLane* ln = lu.ln;
     const hipStream_t ls = ln ? ln->st : s;
     const int blocks = std::max(1, std::min(c->wb_end - c->wb_begin,
-                                            one_query_grid(c, var_lds, c->filt.fields != 0u, c->sel.on != 0u, c->win.fields != 0u, ln != nullptr)));
+                                            one_query_grid(c, var_lds, C.filt.fields != 0u, C.sel.on != 0u, C.win.fields != 0u, ln != nullptr)));
     PostQueries Q;
     rc = place(ln, ls, Q);
     if (rc != PF_OK) return rc;
@@ -617,9 +619,7 @@ int scan_post_one(pf_ctx* c, uint32_t var_lds, int32_t row, int k, uint64_t* d_k
                                .blk_begin = c->wb_begin, .blk_end = c->wb_end, .k = k, .blocks = blocks,
                                .parts = part_buf.as<uint64_t>(), .out = ln ? lu.keys : dst, .sync = Q.sync,
                                .out_rows = Q.out_rows, .claimed = true, .mode = post_mode(true), .e0 = timed ? e0 : nullptr,
-                               .e1 = stop, .s = ls, .qconst = Q.qconst, .filt = c->filt, .sel = c->sel, .win = c->win_post(),
-                               .totals = c->cur_totals ? c->cur_totals + row : nullptr, .collect = c->collect_buf(),
-                               .collect_cap = c->collect_cap_dev()}));
+                               .e1 = stop, .s = ls, .qconst = Q.qconst, .x = C.k5(row)}));
     // the caller's stream: wait for the lane's launch (its stop event), copy its row out
     if (ln && (rc = lane_end(c, lu, stop, s, dst, k)) != PF_OK) return rc;
     if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
@@ -628,13 +628,13 @@ int scan_post_one(pf_ctx* c, uint32_t var_lds, int32_t row, int k, uint64_t* d_k
 
 // K5: the postings scan of prebuilt images (pf_types.h QPostHead layout) into d_keys rows
 // `rows`: one query by scan_post_one, a batch in one launch per occupancy class.
-int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, const std::vector<int32_t>& rows, int k,
-              uint64_t* d_keys, hipStream_t s, bool timed) {
+int scan_post(pf_ctx* c, const pf::ScanCall& C, const std::vector<const std::vector<uint8_t>*>& imgs,
+              const std::vector<int32_t>& rows, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
     const int nq = (int)imgs.size();
     if (nq == 0) return PF_OK;
     if (nq == 1) {  // its upload and launch on the lane's stream (or the caller's, without lanes)
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[0]->data() + sizeof(pf::QConst));
-        return scan_post_one(c, pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), rows[0], k, d_keys, s, timed,
+        return scan_post_one(c, C, pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), rows[0], k, d_keys, s, timed,
                              [&](pf_ctx::ScanLane* ln, hipStream_t ls, PostQueries& Q) {
                                  return stage_post(c, imgs, {0}, {0}, ln ? ln->pool : c->d_pool, ls, Q);
                              });
@@ -649,7 +649,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q]->data() + sizeof(pf::QConst));
         vl[q] = pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend);
         // the hand-out is the call's, not a launch's: a class of one query of a batch stays a batch launch
-        pcu[q] = pf::post_blocks_per_cu(vl[q], false, c->filt.fields != 0u, c->sel.on != 0u, c->win.fields != 0u);
+        pcu[q] = pf::post_blocks_per_cu(vl[q], false, C.filt.fields != 0u, C.sel.on != 0u, C.win.fields != 0u);
         order[q] = q;
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pcu[a] > pcu[b]; });
@@ -668,7 +668,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
     hipEvent_t e0, e1;
     rc = scan_events(c, timed, e0, e1);
     if (rc != PF_OK) return rc;
-    const pf::ScanWindow wpost = c->win_post();
+    const pf::ScanExtras x = C.k5();
     // one launch per class (timed: the first one's start and the last one's end time the call)
     for (int q0 = 0; q0 < nq;) {
         int q1 = q0;
@@ -679,8 +679,7 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
                                    .parts = c->d_part.as<uint64_t>() + (size_t)q0 * (blocks + 8) * k, .out = d_keys,
                                    .sync = Q.sync + q0, .out_rows = Q.out_rows + q0, .claimed = false, .mode = post_mode(false),
                                    .e0 = (timed && q0 == 0) ? e0 : nullptr, .e1 = (timed && q1 == nq) ? e1 : nullptr, .s = s,
-                                   .qconst = nullptr, .filt = c->filt, .sel = c->sel, .win = wpost, .totals = c->cur_totals,
-                                   .collect = c->collect_buf(), .collect_cap = c->collect_cap_dev()}));
+                                   .qconst = nullptr, .x = x}));
         q0 = q1;
     }
     if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
@@ -693,14 +692,14 @@ int scan_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, c
 // every launch (post_tail), and the merge writes the lane's result row.  HIP calls per step on a
 // caller's stream: the launch (its stop event bound to the dispatch), the caller's wait on it and
 // the row copy (+ one event record per ring group of eight rows).
-bool resident_ok(const pf_ctx* c, int32_t i) {
+bool resident_ok(const pf_ctx* c, const pf::ScanCall& C, int32_t i) {
     const auto& R = c->rp;
-    return R.on && R.var_lds[i] != 0 && !R.stale[i] && pf::post_lds(R.var_lds[i]) + filt_lds(c) <= kK5LdsCap;
+    return R.on && R.var_lds[i] != 0 && !R.stale[i] && pf::post_lds(R.var_lds[i]) + filt_lds(C) <= kK5LdsCap;
 }
 
-int scan_post_resident(pf_ctx* c, int32_t i, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
+int scan_post_resident(pf_ctx* c, const pf::ScanCall& C, int32_t i, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
     auto& R = c->rp;
-    return scan_post_one(c, R.var_lds[i], row, k, d_keys, s, timed, [&](pf_ctx::ScanLane* ln, hipStream_t ls, PostQueries& Q) {
+    return scan_post_one(c, C, R.var_lds[i], row, k, d_keys, s, timed, [&](pf_ctx::ScanLane* ln, hipStream_t ls, PostQueries& Q) {
         DBuf& sync_buf = ln ? ln->sync : R.d_sync;
         if (!sync_buf.p) {  // once: every launch leaves it zeroed
             HIPCHK(c, sync_buf.ensure(sizeof(pf::ScanSync)));
@@ -806,8 +805,8 @@ int build_resident_post(pf_ctx* c) {
 // One pinned staging buffer [refs | rows | sync | image pool] goes up in a single async copy.
 // build(q, qi) makes query q's K1 image (false: its hash table cannot be built).
 template <class Build>
-int scan_stream_images(pf_ctx* c, int nq, const std::vector<int32_t>& rows, int k, uint64_t* d_keys, hipStream_t s,
-                       bool timed, Build build) {
+int scan_stream_images(pf_ctx* c, const pf::ScanCall& C, int nq, const std::vector<int32_t>& rows, int k, uint64_t* d_keys,
+                       hipStream_t s, bool timed, Build build) {
     if (nq == 0) return PF_OK;
     Images im;
     pf::QImageHost qi;
@@ -846,8 +845,7 @@ int scan_stream_images(pf_ctx* c, int nq, const std::vector<int32_t>& rows, int 
     HIPCHK(c, pf::launch_scan({.st = c->ds, .pool = d_images, .refs_dev = d_refs, .lds = im.max_lds, .gtab = im.gtab, .nq = nq,
                                .tile_begin = c->tile_begin, .tile_end = c->tile_end, .k = k, .blocks = blocks,
                                .parts = c->d_part.as<uint64_t>(), .out = d_keys, .sync = d_sync, .out_rows = d_rows, .s = s,
-                               .filt = c->filt, .sel = c->sel, .win = c->win, .totals = c->cur_totals,
-                               .collect = c->collect_buf(), .collect_cap = c->collect_cap_dev()}));
+                               .x = C.k1()}));
     if (timed) {
         HIPCHK(c, hipEventRecord(e1, s));
         c->last_ev0 = e0;
@@ -856,10 +854,10 @@ int scan_stream_images(pf_ctx* c, int nq, const std::vector<int32_t>& rows, int 
     return PF_OK;
 }
 
-int scan_stream(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<int32_t>& rows, int k, uint64_t* d_keys,
-                hipStream_t s, bool timed) {
+int scan_stream(pf_ctx* c, const pf::ScanCall& C, const std::vector<int32_t>& idx, const std::vector<int32_t>& rows, int k,
+                uint64_t* d_keys, hipStream_t s, bool timed) {
     std::vector<int32_t> excl;
-    return scan_stream_images(c, (int)idx.size(), rows, k, d_keys, s, timed, [&](int q, pf::QImageHost& qi) {
+    return scan_stream_images(c, C, (int)idx.size(), rows, k, d_keys, s, timed, [&](int q, pf::QImageHost& qi) {
         const int32_t i = idx[q], u = c->hc.uid[i];
         excl.clear();
         auto it = c->hc.adj.find(u);
@@ -869,34 +867,39 @@ int scan_stream(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<in
     });
 }
 
-// The all-candidates scan of by-value profiles (pf_recommend_interest_profile) into d_keys rows 0 ..:
+// The all-candidates scan of by-value profiles (pf_recommend_interest_profile) into d_keys rows row0 ..:
 // scan_all's routing with the images built from the views and the call's exclusion lists; there is
 // no resident image to launch from, so one profile takes the upload path (stage_post, scan_post_one).
-int scan_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
+int scan_profiles(pf_ctx* c, const pf::ScanCall& C, const std::vector<pf::ProfileOwned>& ps, int32_t row0, int k, uint64_t* d_keys,
+                  hipStream_t s, bool timed) {
     const size_t nq = ps.size();
-    std::vector<int32_t> all_rows(nq);
-    for (size_t q = 0; q < nq; ++q) all_rows[q] = (int32_t)q;
+    std::vector<int32_t> all(nq);
+    for (size_t q = 0; q < nq; ++q) all[q] = (int32_t)q;
+    // `which` names profiles of ps (the builder below indexes ps by it); their result rows are those
+    // indices moved to this chunk's place in the call, row0
     auto stream = [&](const std::vector<int32_t>& which, bool tm) {
-        return scan_stream_images(c, (int)which.size(), which, k, d_keys, s, tm, [&](int q, pf::QImageHost& qi) {
+        std::vector<int32_t> rows(which);
+        for (int32_t& r : rows) r += row0;
+        return scan_stream_images(c, C, (int)which.size(), rows, k, d_keys, s, tm, [&](int q, pf::QImageHost& qi) {
             const pf::ProfileOwned& p = ps[(size_t)which[q]];
             return pf::build_query(c->hc, c->hs.packed, p.v, &p.excl, qi);
         });
     };
-    if (!c->use_post()) return stream(all_rows, timed);
+    if (!c->use_post()) return stream(all, timed);
     std::vector<std::vector<uint8_t>> imgs(nq);
     std::vector<uint8_t> fits(nq, 1);
     par_jobs(nq, [&](size_t q) {
         pf::build_query_post(c->hc, c->hp, ps[q].v, ps[q].excl, imgs[q]);
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q].data() + sizeof(pf::QConst));
-        fits[q] = post_image_lds(h) + filt_lds(c) <= kK5LdsCap;
+        fits[q] = post_image_lds(h) + filt_lds(C) <= kK5LdsCap;
     });
     std::vector<const std::vector<uint8_t>*> pi;
     std::vector<int32_t> prow, sidx;
     for (size_t q = 0; q < nq; ++q) {
-        if (fits[q]) { pi.push_back(&imgs[q]); prow.push_back((int32_t)q); }
+        if (fits[q]) { pi.push_back(&imgs[q]); prow.push_back(row0 + (int32_t)q); }
         else sidx.push_back((int32_t)q);
     }
-    const int rc = scan_post(c, pi, prow, k, d_keys, s, timed);
+    const int rc = scan_post(c, C, pi, prow, k, d_keys, s, timed);
     if (rc != PF_OK) return rc;
     return stream(sidx, timed && pi.empty());
 }
@@ -905,17 +908,17 @@ int scan_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps, int k, uin
 // scan (K5) serves every query whose lists fit one workgroup's LDS; a query naming more lists
 // (a user with ~15k friends or thousands of tokens) goes to the record-stream scan (K1) in a
 // launch of its own, so one heavy user never fails the batch.
-int scan_all(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<int32_t>& rows, int k, uint64_t* d_keys,
-             hipStream_t s, bool timed) {
+int scan_all(pf_ctx* c, const pf::ScanCall& C, const std::vector<int32_t>& idx, const std::vector<int32_t>& rows, int k,
+             uint64_t* d_keys, hipStream_t s, bool timed) {
     if (idx.empty()) return PF_OK;
-    if (!c->use_post()) return scan_stream(c, idx, rows, k, d_keys, s, timed);
+    if (!c->use_post()) return scan_stream(c, C, idx, rows, k, d_keys, s, timed);
     pf::HpLap lp;  // PF_DEBUG host_prof=1: image build / staging + launch clocks
     if (pf::host_prof().on) pf::host_prof().ns[pf::kHpScanCalls] += 1000000000LL;
     // one query from the resident images: on the context's stream or a scan lane (another stream
     // without lanes takes the upload path: the resident ScanSync of the context's stream is not
     // shared with a stream it is not ordered against)
-    if (idx.size() == 1 && resident_ok(c, idx[0]) && (s == c->stream || scan_lanes() >= 2)) {
-        const int rc = scan_post_resident(c, idx[0], rows[0], k, d_keys, s, timed);
+    if (idx.size() == 1 && resident_ok(c, C, idx[0]) && (s == c->stream || scan_lanes() >= 2)) {
+        const int rc = scan_post_resident(c, C, idx[0], rows[0], k, d_keys, s, timed);
         lp.lap(pf::kHpScanLaunch);
         return rc;
     }
@@ -930,7 +933,7 @@ int scan_all(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<int32
         ex.push_back(u);
         pf::build_query_post(c->hc, c->hp, i, ex, imgs[q]);
         const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q].data() + sizeof(pf::QConst));
-        fits[q] = post_image_lds(h) + filt_lds(c) <= kK5LdsCap;
+        fits[q] = post_image_lds(h) + filt_lds(C) <= kK5LdsCap;
     });
     std::vector<const std::vector<uint8_t>*> pi;
     std::vector<int32_t> prow, sidx, srow;
@@ -939,10 +942,10 @@ int scan_all(pf_ctx* c, const std::vector<int32_t>& idx, const std::vector<int32
         else { sidx.push_back(idx[q]); srow.push_back(rows[q]); }
     }
     lp.lap(pf::kHpScanImage);
-    int rc = scan_post(c, pi, prow, k, d_keys, s, timed);
+    int rc = scan_post(c, C, pi, prow, k, d_keys, s, timed);
     lp.lap(pf::kHpScanLaunch);
     if (rc != PF_OK) return rc;
-    return scan_stream(c, sidx, srow, k, d_keys, s, timed && pi.empty());
+    return scan_stream(c, C, sidx, srow, k, d_keys, s, timed && pi.empty());
 }
 
 // Bytes the postings scan (K5) reads for one query image over this context's blocks, by the
@@ -1366,19 +1369,13 @@ static int resolve_profiles(pf_ctx* c, const pf_query_profile* q, int32_t nq, st
     return PF_OK;
 }
 
-static int recommend_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps, int32_t topk, int32_t* ou, float* os,
-                              int32_t* oc) {
+static int recommend_profiles(pf_ctx* c, SyncScan& S, const std::vector<pf::ProfileOwned>& ps, int32_t topk, int32_t* ou,
+                              float* os, int32_t* oc) {
     const int32_t nq = (int32_t)ps.size();
-    CollectScope col(c);  // a collector in force: this call's window counts and appends
-    int crc = col.begin(nq);
-    if (crc != PF_OK) return crc;
-    HIPCHK(c, c->d_out.ensure((size_t)nq * topk * sizeof(uint64_t)));
-    CountScope cnt(c, nq);
-    crc = cnt.begin();
-    if (crc != PF_OK) return crc;
+    int rc = S.begin(nq, (size_t)nq, topk, false);
+    if (rc != PF_OK) return rc;
     const size_t chunk = 256;
     for (size_t b = 0; b < ps.size(); b += chunk) {
-        cnt.at(b);
         // a launch's share of a longer call: views of the same arrays
         std::vector<pf::ProfileOwned> part;
         const std::vector<pf::ProfileOwned>* use = &ps;
@@ -1390,16 +1387,29 @@ static int recommend_profiles(pf_ctx* c, const std::vector<pf::ProfileOwned>& ps
             }
             use = &part;
         }
-        const int rc = scan_profiles(c, *use, topk, c->d_out.as<uint64_t>() + b * (size_t)topk, c->stream, b == 0);
-        if (rc != PF_OK) return rc;
+        if ((rc = scan_profiles(c, S.call, *use, (int32_t)b, topk, c->d_out.as<uint64_t>(), c->stream, b == 0)) != PF_OK) return rc;
     }
-    std::vector<uint64_t> keys((size_t)nq * topk);
-    HIPCHK(c, hipMemcpyAsync(keys.data(), c->d_out.p, keys.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
-    for (int i = 0; i < nq; ++i) pf_decode_keys(&keys[(size_t)i * topk], topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
-    crc = cnt.finish();
-    return crc != PF_OK ? crc : col.finish();
+    if ((rc = S.keys(nq, topk, true, ou, os, oc)) != PF_OK) return rc;
+    return S.finish();
+}
+
+// pf_recommend_interest's all-candidates scan of up to 64 results per query, by uid
+static int recommend_uids(pf_ctx* c, SyncScan& S, const int32_t* q, int32_t nq, int32_t topk, int32_t* ou, float* os, int32_t* oc) {
+    std::vector<int32_t> idx, rows;
+    for (int i = 0; i < nq; ++i) {
+        int32_t x = c->hc.idx_of(q[i]);
+        if (x >= 0) { idx.push_back(x); rows.push_back(i); }
+    }
+    int rc = S.begin(nq, (size_t)nq, topk, (int)idx.size() < nq);  // rows of unknown users stay empty
+    if (rc != PF_OK) return rc;
+    const int chunk = 256;
+    for (size_t b = 0; b < idx.size(); b += chunk) {
+        std::vector<int32_t> ii(idx.begin() + b, idx.begin() + std::min(idx.size(), b + chunk));
+        std::vector<int32_t> rr(rows.begin() + b, rows.begin() + std::min(rows.size(), b + chunk));
+        if ((rc = scan_all(c, S.call, ii, rr, topk, c->d_out.as<uint64_t>(), c->stream, b == 0)) != PF_OK) return rc;
+    }
+    if ((rc = S.keys(nq, topk, !idx.empty(), ou, os, oc)) != PF_OK) return rc;
+    return S.finish();
 }
 
 static int profile_args(pf_ctx* c, const pf_query_profile* q, int32_t nq, int32_t topk, int32_t* ou, float* os, int32_t* oc) {
@@ -1419,7 +1429,8 @@ int pf_recommend_interest_profile(pf_ctx* c, const pf_query_profile* q, int32_t 
     if ((rc = resolve_profiles(c, q, nq, ps)) != PF_OK) return rc;
     for (int i = 0; i < nq; ++i) oc[i] = 0;
     if (topk == 0) return PF_OK;
-    return recommend_profiles(c, ps, topk, ou, os, oc);
+    SyncScan S(c);
+    return recommend_profiles(c, S, ps, topk, ou, os, oc);
 }
 
 // the slots of the stored B side of a profile's pairs (one group: the profile); unknown uids are left out
@@ -1484,7 +1495,8 @@ int pf_recommend_interest_profile_terms(pf_ctx* c, const pf_query_profile* q, in
     if ((rc = resolve_profiles(c, q, nq, ps)) != PF_OK) return rc;
     for (int i = 0; i < nq; ++i) oc[i] = 0;
     if (topk == 0) return PF_OK;
-    if ((rc = recommend_profiles(c, ps, topk, ou, os, oc)) != PF_OK) return rc;
+    SyncScan S(c);
+    if ((rc = recommend_profiles(c, S, ps, topk, ou, os, oc)) != PF_OK) return rc;
     // the (profile, winner) pairs, profile by profile: each has an image of its own
     for (int32_t i = 0; i < nq; ++i) {
         if (oc[i] <= 0) continue;
@@ -1508,34 +1520,8 @@ int pf_recommend_interest(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk,
     for (int i = 0; i < nq; ++i) oc[i] = 0;
     if (topk == 0 || nq == 0) return PF_OK;
     if (mode == PF_MODE_ALL && topk <= pf::kMaxTopK) {
-        std::vector<int32_t> idx, rows;
-        for (int i = 0; i < nq; ++i) {
-            int32_t x = c->hc.idx_of(q[i]);
-            if (x >= 0) { idx.push_back(x); rows.push_back(i); }
-        }
-        CollectScope col(c);  // a collector in force: this call's window counts and appends
-        int crc = col.begin(nq);
-        if (crc != PF_OK) return crc;
-        HIPCHK(c, c->d_out.ensure((size_t)nq * topk * sizeof(uint64_t)));
-        if ((int)idx.size() < nq)  // rows of unknown users stay empty
-            HIPCHK(c, hipMemsetAsync(c->d_out.p, 0xFF, (size_t)nq * topk * sizeof(uint64_t), c->stream));
-        CountScope cnt(c, nq);
-        crc = cnt.begin();
-        if (crc != PF_OK) return crc;
-        const int chunk = 256;
-        for (size_t b = 0; b < idx.size(); b += chunk) {
-            std::vector<int32_t> ii(idx.begin() + b, idx.begin() + std::min(idx.size(), b + chunk));
-            std::vector<int32_t> rr(rows.begin() + b, rows.begin() + std::min(rows.size(), b + chunk));
-            int rc = scan_all(c, ii, rr, topk, c->d_out.as<uint64_t>(), c->stream, b == 0);
-            if (rc != PF_OK) return rc;
-        }
-        std::vector<uint64_t> keys((size_t)nq * topk);
-        HIPCHK(c, hipMemcpyAsync(keys.data(), c->d_out.p, keys.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (!idx.empty() && c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
-        for (int i = 0; i < nq; ++i) pf_decode_keys(&keys[(size_t)i * topk], topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
-        crc = cnt.finish();
-        return crc != PF_OK ? crc : col.finish();
+        SyncScan S(c);
+        return recommend_uids(c, S, q, nq, topk, ou, os, oc);
     }
     if (mode == PF_MODE_ALL && c->coll_cap > 0)
         return c->fail(PF_EUNSUPP, "scan collect: topk above 64 runs in the job pipeline, which reads no collector");
@@ -1776,18 +1762,24 @@ static_assert(PF_WIN_MIN == pf::kWinMin && PF_WIN_AFTER == pf::kWinAfter && PF_W
               "pf_window.h restates the public window bits");
 static_assert(sizeof(pf_scan_window) == 24, "pf_scan_window is 24 B");
 
-int pf_set_scan_window(pf_ctx* c, const pf_scan_window* w) {
-    if (!c) return PF_EINVAL;
-    if (!w || w->fields == 0u) {
-        c->win_pub = pf_scan_window{};
-        c->win = pf::ScanWindow{};
-        return PF_OK;
-    }
+// a caller's window as a call's options take it (null or fields == 0: none), or PF_EINVAL with the reason
+static int make_window(pf_ctx* c, const pf_scan_window* w, pf_scan_window& d) {
+    d = pf_scan_window{};
+    if (!w || w->fields == 0u) return PF_OK;
     if ((w->fields & ~pf::kWinAllFields) || w->flags != 0u) return c->fail(PF_EINVAL, "scan window: unknown bits in fields / flags");
     if ((w->fields & PF_WIN_MIN) && std::isnan(w->min_score)) return c->fail(PF_EINVAL, "scan window: min_score is NaN");
     if ((w->fields & PF_WIN_AFTER) && std::isnan(w->after_score)) return c->fail(PF_EINVAL, "scan window: after_score is NaN");
-    c->win_pub = *w;
-    c->win = pf::window_make(w->fields, w->min_score, w->after_score, w->after_uid);
+    d = *w;
+    return PF_OK;
+}
+
+int pf_set_scan_window(pf_ctx* c, const pf_scan_window* w) {
+    if (!c) return PF_EINVAL;
+    pf_scan_window d;
+    const int rc = make_window(c, w, d);
+    if (rc != PF_OK) return rc;
+    c->win_pub = d;
+    c->win = pf::window_make(d.fields, d.min_score, d.after_score, d.after_uid);
     return PF_OK;
 }
 
@@ -1800,25 +1792,30 @@ int pf_scan_window_totals(pf_ctx* c, int64_t* out, int32_t cap, int32_t* n) {
     return PF_OK;
 }
 
+// The collector's buffer, grown to hold cap keys (it never shrinks): the new buffer first, so a refusal
+// leaves the one in force alone; then the stream's work on the old one ends, then it is freed.
+static int collect_reserve(pf_ctx* c, int64_t cap) {
+    const size_t bytes = (size_t)cap * sizeof(uint64_t);
+    if (bytes <= c->d_coll.cap) return PF_OK;
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return c->fail(PF_ENOMEM, "scan collect: no device memory for the buffer (8 B per key)");
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->d_coll.p) (void)hipFree(c->d_coll.p);
+    c->d_coll.p = p;
+    c->d_coll.cap = bytes;
+    return PF_OK;
+}
+
 int pf_set_scan_collect(pf_ctx* c, int64_t cap) {
     if (!c) return PF_EINVAL;
     if (cap < 0 || cap > (int64_t)INT32_MAX) return c->fail(PF_EINVAL, "scan collect: cap below 0 or above INT32_MAX");
-    if (cap == 0) {  // cleared; the buffers stay for the next collector
-        c->coll_cap = 0;
-        return PF_OK;
-    }
-    (void)hipSetDevice(c->device);
-    const size_t bytes = (size_t)cap * sizeof(uint64_t);
-    if (bytes > c->d_coll.cap) {  // the new buffer first: a refusal leaves the collector in force alone
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return c->fail(PF_ENOMEM, "scan collect: no device memory for the buffer (8 B per key)");
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_coll.p) (void)hipFree(c->d_coll.p);
-        c->d_coll.p = p;
-        c->d_coll.cap = bytes;
+    if (cap > 0) {  // 0: cleared; the buffers stay for the next collector
+        (void)hipSetDevice(c->device);
+        const int rc = collect_reserve(c, cap);
+        if (rc != PF_OK) return rc;
     }
     c->coll_cap = cap;
     return PF_OK;
@@ -1856,7 +1853,9 @@ int pf_scan_keys_async(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, ui
     }
     if ((int)idx.size() < nq)  // rows of unknown users stay empty
         HIPCHK(c, hipMemsetAsync(d_keys, 0xFF, (size_t)nq * topk * sizeof(uint64_t), s));
-    return scan_all(c, idx, rows, topk, d_keys, s, true);
+    // the call's options from the sticky state as it stands now
+    const pf::ScanCall call = pf::make_scan_call(c->filt, c->sel, c->win_pub, c->hc.uid.data(), c->hc.uid.size(), 0, nullptr, nullptr);
+    return scan_all(c, call, idx, rows, topk, d_keys, s, true);
 }
 
 int pf_merge_keys_async(pf_ctx* c, const uint64_t* d_parts, int32_t nparts, int32_t nq, int32_t topk, uint64_t* d_out,

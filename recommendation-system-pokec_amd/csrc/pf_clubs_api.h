@@ -1,38 +1,13 @@
 // pf_clubs_api.h — the host part of clubs by interest (pokec_fas.h "Clubs by interest"): the three
-// calls run the scan underneath with a collector and a window of their own, hand the ranked keys it
-// left on the device (d_coll_sorted) to the stage (pf_clubsum.h) and give the context back as it was.
-// Part of pf_api.cpp's translation unit (it uses its scopes and the group call's seed resolution);
-// included at its end, after pf_group_api.h.
+// calls run the scan underneath with options of their own (the query's window and cap, the context's
+// filter and selection; SyncScan with nothing stored in the context) and hand the ranked keys it
+// left on the device (d_coll_sorted) to the stage (pf_clubsum.h).
+// Part of pf_api.cpp's translation unit (it uses its synchronous scans and the group call's seed
+// resolution); included at its end, after pf_group_api.h.
 #pragma once
 #include "pf_clubsum.h"
 
 namespace {
-
-// The context's window, collector, stored totals and collected result for the duration of one call
-struct ClubsScope {
-    pf_ctx* c;
-    pf_scan_window win_pub;
-    pf::ScanWindow win;
-    int64_t coll_cap, coll_total;
-    bool coll_set, win_totals_set;
-    std::vector<uint64_t> coll_keys;
-    std::vector<int64_t> win_totals;
-    explicit ClubsScope(pf_ctx* ctx)
-        : c(ctx), win_pub(ctx->win_pub), win(ctx->win), coll_cap(ctx->coll_cap), coll_total(ctx->coll_total),
-          coll_set(ctx->coll_set), win_totals_set(ctx->win_totals_set), win_totals(ctx->win_totals) {
-        coll_keys.swap(ctx->coll_keys);
-    }
-    ~ClubsScope() {
-        c->win_pub = win_pub;
-        c->win = win;
-        c->coll_cap = coll_cap;  // its buffer only ever grew
-        c->coll_total = coll_total;
-        c->coll_set = coll_set;
-        c->coll_keys.swap(coll_keys);
-        c->win_totals.swap(win_totals);
-        c->win_totals_set = win_totals_set;
-    }
-};
 
 int clubs_args(pf_ctx* c, const pf_clubs_query* q, int32_t topk, const int32_t* oclub, const float* oscore, const int32_t* oc) {
     if (!c) return PF_EINVAL;
@@ -60,7 +35,7 @@ void own_of_idx(const pf_ctx* c, int32_t idx, std::vector<int32_t>& out) {
     own_dense(c, c->hc.clubs.data() + c->hc.club_off[(size_t)idx], c->hc.club_off[(size_t)idx + 1] - c->hc.club_off[(size_t)idx], out);
 }
 
-// scan(): the collecting call underneath, with the window and collector of this call in force
+// scan(S): the collecting scan underneath, with the window and collector of this call as its options
 template <class Scan>
 int clubs_run(pf_ctx* c, const pf_clubs_query* q, int32_t topk, const std::vector<int32_t>& own, Scan scan, int32_t* oclub,
               float* oscore, int32_t* oc, pf_clubs_info* info) {
@@ -68,17 +43,17 @@ int clubs_run(pf_ctx* c, const pf_clubs_query* q, int32_t topk, const std::vecto
     if (info) *info = pf_clubs_info{0, 0, 0, 0};
     if (topk == 0) return PF_OK;
     (void)hipSetDevice(c->device);
-    ClubsScope keep(c);
-    pf_scan_window w{};
+    pf_scan_window given{}, w;
     if (q->window) {
-        w = *q->window;
-        w.fields &= ~PF_WIN_COUNT;  // the collecting call counts for itself and leaves the stored totals alone
+        given = *q->window;
+        given.fields &= ~PF_WIN_COUNT;  // the collecting scan counts for itself and stores no totals
     }
-    int rc = pf_set_scan_window(c, &w);
+    int rc = make_window(c, &given, w);
     if (rc != PF_OK) return rc;
-    if ((rc = pf_set_scan_collect(c, q->cap)) != PF_OK) return rc;
-    if ((rc = scan()) != PF_OK) return rc;
-    const int64_t total = c->coll_total;
+    if ((rc = collect_reserve(c, q->cap)) != PF_OK) return rc;
+    SyncScan S(c, w, q->cap);
+    if ((rc = scan(S)) != PF_OK) return rc;
+    const int64_t total = S.total;
     if (info) info->total = total;
     if (total == 0 || total > q->cap) return PF_OK;
     const int64_t used = q->neighbours > 0 ? std::min<int64_t>(q->neighbours, total) : total;
@@ -124,10 +99,10 @@ int pf_recommend_clubs_interest(pf_ctx* c, int32_t uid, const pf_clubs_query* q,
     std::vector<int32_t> own;
     const int32_t idx = c->hc.idx_of(uid);
     if (idx >= 0) own_of_idx(c, idx, own);
-    return clubs_run(c, q, topk, own, [&]() {
+    return clubs_run(c, q, topk, own, [&](SyncScan& S) {
         int32_t u = 0, n = 0;
         float s = 0.f;
-        return pf_recommend_interest(c, &uid, 1, 1, PF_MODE_ALL, 0, &u, &s, &n);
+        return recommend_uids(c, S, &uid, 1, 1, &u, &s, &n);
     }, oclub, oscore, oc, info);
 }
 
@@ -138,10 +113,12 @@ int pf_recommend_clubs_profile(pf_ctx* c, const pf_query_profile* p, const pf_cl
     if (!p) return c->fail(PF_EINVAL, "clubs by interest: null profile");
     std::vector<int32_t> own;
     if (p->n_clubs > 0 && p->club_ids) own_dense(c, p->club_ids, p->n_clubs, own);
-    return clubs_run(c, q, topk, own, [&]() {
+    return clubs_run(c, q, topk, own, [&](SyncScan& S) {
         int32_t u = 0, n = 0;
         float s = 0.f;
-        return pf_recommend_interest_profile(c, p, 1, 1, &u, &s, &n);
+        std::vector<pf::ProfileOwned> ps;
+        const int prc = resolve_profiles(c, p, 1, ps);
+        return prc != PF_OK ? prc : recommend_profiles(c, S, ps, 1, &u, &s, &n);
     }, oclub, oscore, oc, info);
 }
 
@@ -153,10 +130,10 @@ int pf_recommend_clubs_group(pf_ctx* c, const pf_group_query* g, const pf_clubs_
     if ((rc = group_args(c, g)) != PF_OK) return rc;
     std::vector<int32_t> own;
     for (int32_t idx : group_seeds(c, *g)) own_of_idx(c, idx, own);
-    return clubs_run(c, q, topk, own, [&]() {
+    return clubs_run(c, q, topk, own, [&](SyncScan& S) {
         int32_t u = 0, n = 0;
         float s = 0.f;
-        return pf_recommend_group(c, g, 1, 1, &u, &s, &n);
+        return recommend_groups(c, S, g, 1, 1, &u, &s, &n);
     }, oclub, oscore, oc, info);
 }
 

@@ -5,21 +5,12 @@
 //                launch is a counting one (kWinCollect comes with kWinCount): the total is the count
 //                word, the cursor (ScanSync::ccursor) only hands out slots.
 //   the finish   collect_sort below, once the host has read the total and it fits the buffer.
-// The buffer and its cap travel by value with each launch, like the window.
+// The buffer and its cap travel by value with each launch, like the window (pf_scan_call.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "pf_window.h"
-
 namespace pf {
-
-// What the launchers ask of a collecting launch: one query, a counted window, a buffer and a cap that
-// fits the kernels' 32-bit slots.  A launch that does not collect passes a null buffer.
-inline bool collect_launch_ok(const ScanWindow& w, int nq, const uint64_t* buf, uint32_t cap) {
-    if (!(w.fields & kWinCollect)) return buf == nullptr;
-    return nq == 1 && (w.fields & kWinCount) && buf != nullptr && cap > 0u && cap <= (uint32_t)INT32_MAX;
-}
 
 // Temporary storage hipCUB's radix sort takes for n 64-bit keys
 hipError_t collect_sort_bytes(int64_t n, size_t* bytes);

@@ -210,29 +210,19 @@ struct pf_ctx {
     // field selection of the all-candidates scans (pf_set_scan_select; on == 0: none), in its device
     // form: taken by value like the filter, by every scan launch and every kDjAll chunk's pair stage
     pf::FieldSel sel{};
-    // score window of the all-candidates scans (pf_set_scan_window; fields == 0: none): the public
-    // struct as given (the cursor's score and uid, for K5's idx bound) and its uid-keyed device form,
-    // taken by value like the filter by every scan launch (never by a kDjAll chunk: topk > 64 under a
-    // window is refused).  A counted synchronous call fills win_totals, one value per query.
+    // score window of the all-candidates scans (pf_set_scan_window, their only writer; fields == 0:
+    // none): the public struct as given, which each call's options are built from (pf_scan_call.h;
+    // never a kDjAll chunk's: topk > 64 under a window is refused), and its uid-keyed device form.
+    // A counted synchronous call fills win_totals, one value per query.
     pf_scan_window win_pub{};
     pf::ScanWindow win{};
-    DBuf d_totals;                       // the counted launches' count words, one per result row
+    DBuf d_totals;                       // a counted call's count words, one per result row
     std::vector<int64_t> win_totals;     // the last counted call's values (pf_scan_window_totals)
     bool win_totals_set = false;
-    // K5's form of the window: the cursor's uid turned into the first idx whose uid exceeds it
-    pf::ScanWindow win_post() const {
-        if (!(win.fields & pf::kWinAfter)) return win;
-        const auto it = std::upper_bound(hc.uid.begin(), hc.uid.end(), win_pub.after_uid);
-        return pf::window_for_idx(win, win_pub.after_score, (uint32_t)(it - hc.uid.begin()));
-    }
-    // where the launches of the synchronous call in progress write their counts (row 0 of its current
-    // chunk in d_totals); nullptr outside a counted call
-    uint32_t* cur_totals = nullptr;
     // collector of the all-candidates scans (pf_set_scan_collect; coll_cap == 0: none): the buffer a
     // collecting call's one launch appends its window's keys to, the sort's output and scratch, and
-    // the last collecting call's result on the host (pf_scan_collected).  A collecting call sets
-    // kWinCollect | kWinCount in `win` for its own duration (CollectScope): collect_buf() is what its
-    // launches carry, nullptr for everybody else's.
+    // the last collecting call's result on the host (pf_scan_collected).  The buffer and the cap reach
+    // the launch in the call's options, nobody else's.
     int64_t coll_cap = 0;
     DBuf d_coll, d_coll_sorted, d_coll_tmp;
     std::vector<uint64_t> coll_keys;     // ranked; empty on overflow
@@ -241,8 +231,6 @@ struct pf_ctx {
     // clubs by interest (pf_clubsum.h): the stage's workspaces, grown on demand
     pf::ClubSumWs clubs_ws;
     int32_t n_shards = 1;                // pf_set_shard's count (the clubs-by-interest calls refuse more than one)
-    uint64_t* collect_buf() const { return (win.fields & pf::kWinCollect) ? static_cast<uint64_t*>(d_coll.p) : nullptr; }
-    uint32_t collect_cap_dev() const { return (win.fields & pf::kWinCollect) ? (uint32_t)coll_cap : 0u; }
     // pinned staging ring for the per-call query upload (a slot is reused only after
     // the copy that read it has completed)
     struct Stage {

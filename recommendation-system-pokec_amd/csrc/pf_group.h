@@ -13,11 +13,8 @@
 #include <cstdint>
 #include <vector>
 
-#include "pf_filter.h"
-#include "pf_select.h"
+#include "pf_scan_call.h"
 #include "pf_types.h"
-#include "pf_collect.h"
-#include "pf_window.h"
 
 namespace pf {
 
@@ -87,16 +84,7 @@ struct GroupLaunch {
     uint64_t *parts, *out;       // last pass: post_tail's lists ((blocks + 8) x k) and the result row
     ScanSync* sync;              // last pass: one zeroed rendezvous
     hipStream_t s;
-    const CandFilter& filt;
-    const FieldSel& sel;
-    // the context's score window (pf_window.h; uid-keyed), tested on the aggregate's key in the last
-    // pass; a counted one writes the group's count to totals[0] (device, nullptr otherwise)
-    const ScanWindow& win;
-    uint32_t* totals;
-    // the context's collector (pf_collect.h) when win has kWinCollect: the buffer (device) and its cap
-    // in keys; nullptr / 0 otherwise.  One query per collecting launch.
-    uint64_t* collect;
-    uint32_t collect_cap;
+    const ScanExtras& x;         // the call's filter, selection, uid-keyed window, count word and collector (pf_scan_call.h)
 };
 hipError_t launch_group(const GroupLaunch& L);
 // resident workgroups per CU of a pass's instantiation at its LDS size

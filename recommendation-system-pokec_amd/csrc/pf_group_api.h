@@ -105,9 +105,10 @@ int64_t group_pass_bytes(const pf_ctx* c) {
     return b + (int64_t)(c->tile_end - c->tile_begin) * pf::kTileSlots * 48;
 }
 
-// One group's passes on the context's stream, its k keys into d_keys.  One pinned staging buffer
-// [refs | offsets | sync | image pool] goes up in a single copy, as in scan_stream_images.
-int group_scan(pf_ctx* c, const GroupPlan& P, int agg, int k, uint64_t* d_keys, bool timed) {
+// One group's passes on the context's stream, its k keys into d_keys, with x the call's options for
+// this group (its own count word).  One pinned staging buffer [refs | offsets | sync | image pool] goes
+// up in a single copy, as in scan_stream_images.
+int group_scan(pf_ctx* c, const pf::ScanExtras& x, const GroupPlan& P, int agg, int k, uint64_t* d_keys, bool timed) {
     const size_t G = P.idx.size();
     const int tiles = c->tile_end - c->tile_begin;
     const size_t refs_b = (G * sizeof(pf::QImageRef) + 15) & ~(size_t)15;
@@ -144,14 +145,29 @@ int group_scan(pf_ctx* c, const GroupPlan& P, int agg, int k, uint64_t* d_keys, 
                                     .tile_end = c->tile_end, .k = k, .blocks = blocks[p], .acc = c->d_scores.as<double>(),
                                     .parts = c->d_part.as<uint64_t>(), .out = d_keys,
                                     .sync = reinterpret_cast<pf::ScanSync*>(base + refs_b + offs_b), .s = c->stream,
-                                    .filt = c->filt, .sel = c->sel, .win = c->win, .totals = c->cur_totals,
-                                    .collect = c->collect_buf(), .collect_cap = c->collect_cap_dev()}));
+                                    .x = x}));
     if (timed) {
         HIPCHK(c, hipEventRecord(e1, c->stream));
         c->last_ev0 = e0;
         c->last_ev1 = e1;
     }
     return PF_OK;
+}
+
+// pf_recommend_group's scans: group i's keys through row 0 of d_out, its count in word i (0 for G = 0);
+// last_scan_ms is the last scanned group's
+int recommend_groups(pf_ctx* c, SyncScan& S, const pf_group_query* g, int32_t ng, int32_t topk, int32_t* ou, float* os,
+                     int32_t* oc) {
+    int rc = S.begin(ng, 1, topk, false);
+    if (rc != PF_OK) return rc;
+    for (int32_t i = 0; i < ng; ++i) {
+        GroupPlan P;
+        if ((rc = group_plan(c, g[i], P)) != PF_OK) return rc;
+        if (P.idx.empty()) continue;
+        if ((rc = group_scan(c, S.call.group(i), P, g[i].agg, topk, c->d_out.as<uint64_t>(), true)) != PF_OK) return rc;
+        if ((rc = S.keys(1, topk, true, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i])) != PF_OK) return rc;
+    }
+    return S.finish();
 }
 
 }  // namespace
@@ -170,28 +186,8 @@ int pf_recommend_group(pf_ctx* c, const pf_group_query* g, int32_t ng, int32_t t
     (void)hipSetDevice(c->device);
     for (int32_t i = 0; i < ng; ++i) oc[i] = 0;
     if (topk == 0) return PF_OK;
-    HIPCHK(c, c->d_out.ensure((size_t)topk * sizeof(uint64_t)));
-    std::vector<uint64_t> keys((size_t)topk);
-    CollectScope col(c);  // a collector in force: this call's window counts and appends
-    int crc = col.begin(ng);
-    if (crc != PF_OK) return crc;
-    CountScope cnt(c, ng);  // a counted window: group i's count in row i (0 for G = 0)
-    crc = cnt.begin();
-    if (crc != PF_OK) return crc;
-    for (int32_t i = 0; i < ng; ++i) {
-        cnt.at((size_t)i);
-        GroupPlan P;
-        int rc = group_plan(c, g[i], P);
-        if (rc != PF_OK) return rc;
-        if (P.idx.empty()) continue;
-        if ((rc = group_scan(c, P, g[i].agg, topk, c->d_out.as<uint64_t>(), true)) != PF_OK) return rc;
-        HIPCHK(c, hipMemcpyAsync(keys.data(), c->d_out.p, keys.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
-        pf_decode_keys(keys.data(), topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
-    }
-    crc = cnt.finish();
-    return crc != PF_OK ? crc : col.finish();
+    SyncScan S(c);
+    return recommend_groups(c, S, g, ng, topk, ou, os, oc);
 }
 
 int pf_group_scores(pf_ctx* c, const pf_group_query* g, const int32_t* b, int64_t n, const pf_field_select* s, float* out) {

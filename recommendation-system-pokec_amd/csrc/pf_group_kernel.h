@@ -170,13 +170,12 @@ static GroupKernel group_kernel(bool packed, bool gtab) {
 
 hipError_t launch_group(const GroupLaunch& L) {
     if (L.pass.nimg <= 0) return hipSuccess;
-    if ((L.win.fields & kWinCount) && !L.totals) return hipErrorInvalidValue;
-    if (!collect_launch_ok(L.win, 1, L.collect, L.collect_cap)) return hipErrorInvalidValue;
+    if (!extras_ok(L.x, 1)) return hipErrorInvalidValue;
     const GroupArgs A{L.pass.img0, L.pass.nimg, L.pass.hits_off, L.hit_bytes, L.first ? 1 : 0, L.last ? 1 : 0, L.agg,
                       L.n_seeds, L.excl_img, L.tile_begin, L.tile_end, L.k};
     hipLaunchKernelGGL(group_kernel(L.st.packed, L.pass.gtab), dim3(L.blocks), dim3(kScanThreads), L.pass.lds, L.s, L.st,
-                       L.pool, L.refs_dev, L.off_dev, A, L.acc, L.parts, L.sync, L.out, L.filt, L.sel, L.win, L.totals,
-                       L.collect, L.collect_cap);
+                       L.pool, L.refs_dev, L.off_dev, A, L.acc, L.parts, L.sync, L.out, L.x.filt, L.x.sel, L.x.win, L.x.totals,
+                       L.x.collect, L.x.collect_cap);
     return hipGetLastError();
 }
 

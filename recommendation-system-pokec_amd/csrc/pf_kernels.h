@@ -2,11 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "pf_filter.h"
-#include "pf_select.h"
+#include "pf_scan_call.h"
 #include "pf_types.h"
-#include "pf_collect.h"
-#include "pf_window.h"
 
 namespace pf {
 
@@ -46,18 +43,7 @@ struct ScanLaunch {
     ScanSync* sync;
     const int32_t* out_rows;
     hipStream_t s;
-    const CandFilter& filt;  // by value in the launch's arguments (fields == 0: none): pf_filter.h
-    // by value likewise (on == 0: none): the context's field selection (pf_select.h), applied to
-    // each block's staged copy of its query's constants
-    const FieldSel& sel;
-    // by value likewise (fields == 0: none): the context's score window (pf_window.h), uid-keyed; a
-    // counted one (kWinCount) writes each query's count to totals[its row] (device, nullptr otherwise)
-    const ScanWindow& win;
-    uint32_t* totals;
-    // the context's collector (pf_collect.h) when win has kWinCollect: the buffer (device) and its cap
-    // in keys; nullptr / 0 otherwise.  One query per collecting launch.
-    uint64_t* collect;
-    uint32_t collect_cap;
+    const ScanExtras& x;  // the call's filter, selection, uid-keyed window, count words and collector (pf_scan_call.h)
 };
 hipError_t launch_scan(const ScanLaunch& L);
 // resident scan blocks per CU at this dynamic LDS size (HIP occupancy API)
@@ -98,21 +84,9 @@ struct PostLaunch {
     // nullptr (each image starts with its QConst) or, for a one-query launch from the resident images, the
     // user's QConst elsewhere (its K1' resident image); the image = the resident part's start minus sizeof(QConst)
     const uint8_t* qconst;
-    // by value in the launch's arguments (fields == 0: none): the context's candidate filter (pf_filter.h)
-    const CandFilter& filt;
-    // by value likewise (on == 0: none): the context's field selection (pf_select.h); a selected
-    // launch takes the SEL instantiation, which patches its staged copy of the query's constants and
-    // leaves the deselected columns and set lists out of its tables.  It needs no LDS of its own.
-    const FieldSel& sel;
-    // by value likewise (fields == 0: none): the context's score window (pf_window.h) with its cursor
-    // in idx space (window_for_idx); a windowed launch takes the WIN instantiation and kWinLds bytes.
-    // A counted one (kWinCount) writes each query's count to totals[its row] (device, nullptr otherwise)
-    const ScanWindow& win;
-    uint32_t* totals;
-    // the context's collector (pf_collect.h) when win has kWinCollect: the buffer (device) and its cap
-    // in keys; nullptr / 0 otherwise.  One query per collecting launch.
-    uint64_t* collect;
-    uint32_t collect_cap;
+    // the call's filter, selection, idx-keyed window, count words and collector (pf_scan_call.h): the
+    // filter, the selection and the window each pick an instantiation (FILT, SEL, WIN)
+    const ScanExtras& x;
 };
 hipError_t launch_post(const PostLaunch& L);
 // workgroups per CU of the instantiation launch_post takes for `claimed`, `filtered` (a filter is

@@ -2307,11 +2307,10 @@ static PostKernel post_kernel(bool claimed, bool filtered, bool selected, bool w
 
 hipError_t launch_scan(const ScanLaunch& L) {
     if (L.nq <= 0) return hipSuccess;
-    if ((L.win.fields & kWinCount) && !L.totals) return hipErrorInvalidValue;
-    if (!collect_launch_ok(L.win, L.nq, L.collect, L.collect_cap)) return hipErrorInvalidValue;
+    if (!extras_ok(L.x, L.nq)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(scan_kernel(L.st.packed, L.gtab), dim3(L.blocks, L.nq), dim3(kScanThreads), L.lds, L.s, L.st, L.pool,
-                       L.refs_dev, L.tile_begin, L.tile_end, L.k, L.parts, L.sync, L.out, L.out_rows, L.filt, L.sel, L.win, L.totals,
-                       L.collect, L.collect_cap);
+                       L.refs_dev, L.tile_begin, L.tile_end, L.k, L.parts, L.sync, L.out, L.out_rows, L.x.filt, L.x.sel, L.x.win, L.x.totals,
+                       L.x.collect, L.x.collect_cap);
     return hipGetLastError();
 }
 
@@ -2385,16 +2384,15 @@ hipError_t launch_post(const PostLaunch& L) {
     if (L.nq <= 0) return hipSuccess;
     // the claimed hand-out is the one-query instantiation's and nobody else's
     if (L.claimed && L.nq != 1) return hipErrorInvalidValue;
-    if ((L.win.fields & kWinCount) && !L.totals) return hipErrorInvalidValue;
-    if (!collect_launch_ok(L.win, L.nq, L.collect, L.collect_cap)) return hipErrorInvalidValue;
+    if (!extras_ok(L.x, L.nq)) return hipErrorInvalidValue;
     // + the filter's and the window's words (fas_post_kernel)
-    const uint32_t lds = post_lds(L.var_lds) + (L.filt.fields ? kFiltLds : 0u) + (L.win.fields ? kWinLds : 0u);
+    const uint32_t lds = post_lds(L.var_lds) + (L.x.filt.fields ? kFiltLds : 0u) + (L.x.win.fields ? kWinLds : 0u);
     // timed launches (e0, e1 given): the kernel's own start and end timestamps, taken from its
     // dispatch (hipExtLaunchKernelGGL), instead of two marker packets around it.  The filter and the field
     // selection travel in the launch's own arguments: a later pf_set_scan_filter / _select does not reach them
-    hipExtLaunchKernelGGL(post_kernel(L.claimed, L.filt.fields != 0u, L.sel.on != 0u, L.win.fields != 0u), dim3(L.blocks, L.nq), dim3(kPostThreads),
+    hipExtLaunchKernelGGL(post_kernel(L.claimed, L.x.filt.fields != 0u, L.x.sel.on != 0u, L.x.win.fields != 0u), dim3(L.blocks, L.nq), dim3(kPostThreads),
                           lds, L.s, L.e0, L.e1, 0u, L.ps, L.pool, L.img_off, L.blk_begin, L.blk_end, L.k, L.parts, L.sync, L.out,
-                          L.out_rows, L.mode, L.qconst, L.filt, L.sel, L.win, L.totals, L.collect, L.collect_cap);
+                          L.out_rows, L.mode, L.qconst, L.x.filt, L.x.sel, L.x.win, L.x.totals, L.x.collect, L.x.collect_cap);
 #ifdef PF_K5_BLOCKLOG
     {
         static int calls = 0;

@@ -11,8 +11,8 @@ namespace pf {
 constexpr uint32_t kWinMin = 1u, kWinAfter = 2u, kWinCount = 4u;  // = PF_WIN_* (pf_api.cpp asserts it)
 constexpr uint32_t kWinAllFields = kWinMin | kWinAfter | kWinCount;
 // device-only: the launch appends every in-window key to the context's collector (pf_collect.h).  Never
-// taken from the public struct (pf_set_scan_window refuses it); a collecting call sets it, with
-// kWinCount, for its own launches.
+// taken from the public struct (pf_set_scan_window refuses it); a collecting call's options carry it,
+// with kWinCount (pf_scan_call.h make_scan_call, the one place that sets it).
 constexpr uint32_t kWinCollect = 8u;
 
 // What a launch carries, by value in its arguments.  A key (pf_types.h score_key: ascending key =
