@@ -1,994 +1,37 @@
-// pf_api.cpp — the C ABI (include/pokec_fas.h): context lifetime, device upload,
-// query-image packing, and the host orchestration of the reference's recommenders
-// (recommender_graph.cpp:10-237, recommender_clubs.cpp:10-73) around the gfx950
-// kernels.  The FAS arithmetic itself runs only on the GPU; there is no CPU path.
+// pf_api.cpp — the C ABI (include/pokec_fas.h): context lifetime and device upload, the setters
+// with their validation, argument checks, and the entry points over the host orchestration of the
+// reference's recommenders (recommender_graph.cpp:10-237, recommender_clubs.cpp:10-73): the scans
+// in pf_scan_host.cpp, the pairs in pf_pairs_host.cpp, the job pipeline in pf_jobs_plan.cpp (the
+// group and clubs entry points: pf_group_api.cpp, pf_clubs_api.cpp).  The FAS arithmetic itself runs
+// only on the GPU; there is no CPU path.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include "pf_batch.h"
-#include "pf_collect.h"
 #include "pf_ctx.h"
 #include "pf_debug.h"
+#include "pf_host.h"
 #include "pf_kernels.h"
 #include "pf_store.h"
 #include "pokec_fas.h"
-
-using pf::DBuf;
-using pf::PinBuf;
-using pf::Ranked;
-using pf::par_jobs;
-using pf::rank;
 
 namespace {
 
 thread_local std::string g_open_error;
 
-constexpr uint32_t kLdsLimit = 64 * 1024;  // query images above this probe from global memory
-constexpr uint32_t kK5LdsCap = 160u * 1024u;  // one K5 workgroup's LDS (gfx950: 160 KB per CU)
-constexpr size_t kProfCap = 1u << 16;      // profiling event pairs kept (pf_profile_*)
-
 }  // namespace
 
 namespace pf {
+
 void set_open_error(const std::string& m) { g_open_error = m; }
-}  // namespace pf
-
-namespace {
-
-// Query images -> one byte pool + refs.
-struct Images {
-    std::vector<uint8_t> pool;
-    std::vector<pf::QImageRef> refs;
-    uint32_t max_lds = 0;  // dynamic LDS a 256-thread block needs for the largest image
-    bool gtab = false;     // some image probes its table in global memory
-    uint32_t max_img = 0;  // the largest staged keys + vals (plan_images): K1t's LDS past the QConst
-};
-
-constexpr uint32_t kStageLimit = 48 * 1024;   // keys+vals above this are probed in global memory
-
-// PF_DEBUG stage_limit (bytes) lowers the LDS staging limit; tests use it to force the
-// global-memory table variant on small corpora.
-uint32_t stage_limit() {
-    static const uint32_t lim = (uint32_t)pf::debug_long("stage_limit", kStageLimit);
-    return lim;
-}
-constexpr uint32_t kBlockThreads = 256;
-
-void add_image(Images& im, const pf::QImageHost& q) {
-    auto align = [&](size_t a) { while (im.pool.size() % a) im.pool.push_back(0); };
-    align(16);
-    pf::QImageRef r{};
-    const size_t start = im.pool.size();
-    r.const_off = (uint32_t)(start / 16);
-    const uint8_t* cp = reinterpret_cast<const uint8_t*>(&q.c);
-    im.pool.insert(im.pool.end(), cp, cp + sizeof(pf::QConst));
-    r.keys_off = (uint32_t)(im.pool.size() - start);
-    const uint8_t* kp = reinterpret_cast<const uint8_t*>(q.keys.data());
-    im.pool.insert(im.pool.end(), kp, kp + q.keys.size() * 8);
-    align(16);
-    r.vals_off = (uint32_t)(im.pool.size() - start);
-    const uint8_t* vp = reinterpret_cast<const uint8_t*>(q.vals.data());
-    im.pool.insert(im.pool.end(), vp, vp + q.vals.size() * sizeof(pf::QVal));
-    const size_t kv = q.keys.size() * 8 + q.vals.size() * sizeof(pf::QVal);
-    r.lds_bytes = kv <= stage_limit() ? (uint32_t)kv : 0u;
-    im.gtab = im.gtab || r.lds_bytes == 0;
-    // QConst | staged tables | hit lists | hit counts | merge scratch (stage_query's carve)
-    const uint32_t need = (uint32_t)sizeof(pf::QConst) + r.lds_bytes + q.c.n_hits_max * kBlockThreads +
-                          4u * kBlockThreads + 2048u;
-    im.max_lds = std::max(im.max_lds, need);
-    im.refs.push_back(r);
-}
-constexpr uint32_t kPairThreads = (uint32_t)pf::kPairThreads;
-
-// Many images at once: refs and offsets first (returns the pool bytes), then fill_images
-// copies them on threads into `dst` (pinned; a few thousand images per chunk).
-size_t plan_images(Images& im, const std::vector<pf::QImageHost>& qs) {
-    auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t o = 0;
-    for (const auto& q : qs) {
-        pf::QImageRef r{};
-        r.const_off = (uint32_t)(o / 16);
-        r.keys_off = (uint32_t)sizeof(pf::QConst);
-        r.vals_off = (uint32_t)a16(r.keys_off + q.keys.size() * 8);
-        o = a16(o + r.vals_off + q.vals.size() * sizeof(pf::QVal));
-        const size_t kv = q.keys.size() * 8 + q.vals.size() * sizeof(pf::QVal);
-        r.lds_bytes = kv <= stage_limit() ? (uint32_t)kv : 0u;
-        im.gtab = im.gtab || r.lds_bytes == 0;
-        const uint32_t need = (uint32_t)sizeof(pf::QConst) + r.lds_bytes + q.c.n_hits_max * kPairThreads +
-                              4u * kPairThreads + 2048u;
-        im.max_lds = std::max(im.max_lds, need);
-        im.refs.push_back(r);
-        im.max_img = std::max(im.max_img, r.lds_bytes);
-    }
-    return o;
-}
-
-void fill_images(const Images& im, const std::vector<pf::QImageHost>& qs, uint8_t* dst, size_t total) {
-    par_jobs(qs.size(), [&](size_t i) {
-        const pf::QImageHost& q = qs[i];
-        const pf::QImageRef& r = im.refs[i];
-        const size_t b = (size_t)r.const_off * 16;  // byte offsets from the pool start
-        const size_t ko = b + r.keys_off, vo = b + r.vals_off;
-        const size_t kend = ko + q.keys.size() * 8, vend = vo + q.vals.size() * sizeof(pf::QVal);
-        const size_t next = i + 1 < qs.size() ? (size_t)im.refs[i + 1].const_off * 16 : total;
-        std::memcpy(dst + b, &q.c, sizeof(pf::QConst));
-        if (!q.keys.empty()) std::memcpy(dst + ko, q.keys.data(), q.keys.size() * 8);
-        std::memset(dst + kend, 0, vo - kend);
-        if (!q.vals.empty()) std::memcpy(dst + vo, q.vals.data(), q.vals.size() * sizeof(pf::QVal));
-        std::memset(dst + vend, 0, next - vend);
-    }, 64);
-}
-
-pf::AdjView plain_view(const pf_ctx* c) {
-    pf::AdjView v;
-    v.base = &c->hc.adj;
-    return v;
-}
-
-// One chunk of pair groups as its kernel finds it: the images in c->d_pool / d_refs, the candidate
-// slots in c->d_slots (group g0 + i's from gf[i]; gf[g1 - g0] = npairs) and the pair blocks in
-// c->d_blocks, all queued on the context's stream.
-struct PairChunk {
-    size_t g0, g1;
-    const std::vector<size_t>& gf;
-    size_t npairs;
-    const Images& im;
-    int nblocks;
-    pf::HpLap& hl;
-};
-
-// Pairs (A = qidx[g], B = slots[g][j]) of every group g, to the GPU in chunks (<= 4096 distinct
-// queries, <= max_pairs pairs per launch); each distinct query's image is built once per chunk, on host
-// threads.  A group's pairs are cut into blocks of block_pairs (a PairBlock's count).  run(chunk)
-// launches the chunk's kernel, fetches its results and synchronises the stream before it returns
-// (the pinned buffers are reused by the next chunk).
-// pv (optional): the A side of every group is this by-value profile, not a stored user (qidx then
-// only groups the pairs); its image is built by the same builder and staged in the same pool.
-template <class Run>
-int pair_chunks(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
-                uint32_t block_pairs, size_t max_pairs, const pf::ProfileView* pv, Run&& run) {
-    size_t g0 = 0;
-    while (g0 < qidx.size()) {
-        // chunk [g0, g1)
-        std::unordered_map<int32_t, int32_t> img_of;
-        std::vector<int32_t> uq;
-        size_t g1 = g0, pairs = 0;
-        for (; g1 < qidx.size(); ++g1) {
-            if (slots[g1].empty()) continue;
-            const bool fresh = !img_of.count(qidx[g1]);
-            if (g1 > g0 && ((fresh && uq.size() >= 4096) || pairs + slots[g1].size() > max_pairs)) break;
-            if (fresh) {
-                img_of.emplace(qidx[g1], (int32_t)uq.size());
-                uq.push_back(qidx[g1]);
-            }
-            pairs += slots[g1].size();
-        }
-        if (pairs == 0) { g0 = g1; continue; }
-        std::vector<pf::QImageHost> qi(uq.size());
-        std::vector<uint8_t> ok(uq.size(), 1);
-        pf::HpLap hl;
-        {
-            const int th = (int)std::min<size_t>(16, std::max<size_t>(1, uq.size() / 16));
-            std::vector<std::thread> ts;
-            for (int w = 0; w < th; ++w)
-                ts.emplace_back([&, w]() {
-                    for (size_t i = (size_t)w; i < uq.size(); i += (size_t)th)
-                        ok[i] = (pv ? pf::build_query(c->hc, c->hs.packed, *pv, nullptr, qi[i])
-                                    : pf::build_query(c->hc, c->hs.packed, uq[i], nullptr, qi[i])) ? 1 : 0;
-                });
-            for (auto& t : ts) t.join();
-        }
-        for (uint8_t x : ok)
-            if (!x) return c->fail(PF_EUNSUPP, "query hash table too large");
-        hl.lap(pf::kHpImages);
-        Images im;
-        std::vector<pf::PairBlock> blocks;
-        const size_t pool_bytes = plan_images(im, qi);
-        // per group: first block and first pair (serial, O(groups)); then the copies on threads
-        std::vector<size_t> gb(g1 - g0 + 1), gf(g1 - g0 + 1);
-        for (size_t g = g0; g < g1; ++g) {
-            gb[g - g0 + 1] = gb[g - g0] + (slots[g].size() + block_pairs - 1) / block_pairs;
-            gf[g - g0 + 1] = gf[g - g0] + slots[g].size();
-        }
-        const size_t npairs = gf.back();
-        HIPCHK(c, c->h_pool.ensure(pool_bytes));
-        HIPCHK(c, c->h_slots.ensure(npairs * sizeof(int32_t)));
-        fill_images(im, qi, c->h_pool.as<uint8_t>(), pool_bytes);
-        blocks.resize(gb.back());
-        int32_t* flat = c->h_slots.as<int32_t>();
-        par_jobs(g1 - g0, [&](size_t i) {
-            const size_t g = g0 + i;
-            if (slots[g].empty()) return;
-            const int32_t img = img_of.at(qidx[g]);
-            std::memcpy(flat + gf[i], slots[g].data(), slots[g].size() * sizeof(int32_t));
-            for (size_t b = 0, x = gb[i]; b < slots[g].size(); b += block_pairs, ++x)
-                blocks[x] = pf::PairBlock{img, (int32_t)(gf[i] + b), (int32_t)std::min<size_t>(block_pairs, slots[g].size() - b),
-                                           (int32_t)(gf[i] + b)};
-        }, 256);
-        hl.lap(pf::kHpPack);
-        // pinned buffers: async copies; they are reused only after this chunk's synchronize
-        HIPCHK(c, c->d_pool.ensure(std::max<size_t>(pool_bytes, 16)));
-        HIPCHK(c, hipMemcpyAsync(c->d_pool.p, c->h_pool.p, pool_bytes, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, upload(c, c->d_refs, im.refs));
-        HIPCHK(c, upload(c, c->d_blocks, blocks));
-        HIPCHK(c, c->d_slots.ensure(npairs * sizeof(int32_t)));
-        HIPCHK(c, hipMemcpyAsync(c->d_slots.p, flat, npairs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        const int rc = run(PairChunk{g0, g1, gf, npairs, im, (int)blocks.size(), hl});
-        if (rc != PF_OK) return rc;
-        g0 = g1;
-    }
-    return PF_OK;
-}
-
-// FAS(A = qidx[g], B = slots[g][j]) for every group g, on the GPU (K1').
-// keep (optional): every chunk's scores stay on the device in one buffer, group g at
-// (*goff)[g] (the collaborative sums read their matrix rows there)
-// sel (on == 0: none): a field selection every pair is scored under (pf_fas_pairs_select)
-int run_pairs(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
-              std::vector<std::vector<float>>& out, DBuf* keep = nullptr, std::vector<int64_t>* goff = nullptr,
-              const pf::FieldSel& sel = pf::FieldSel{}, const pf::ProfileView* pv = nullptr) {
-    out.assign(qidx.size(), {});
-    if (keep) {
-        size_t tot = 0;
-        goff->assign(qidx.size(), 0);
-        for (size_t g = 0; g < qidx.size(); ++g) {
-            (*goff)[g] = (int64_t)tot;
-            tot += slots[g].size();
-        }
-        HIPCHK(c, keep->ensure(std::max<size_t>(tot, 1) * sizeof(float)));
-    }
-    for (size_t g = 0; g < qidx.size(); ++g) out[g].assign(slots[g].size(), 0.f);
-    return pair_chunks(c, qidx, slots, kPairThreads, (size_t)8u << 20, pv, [&](const PairChunk& k) -> int {
-        HIPCHK(c, c->h_scores.ensure(k.npairs * sizeof(float)));
-        float* dsc = nullptr;
-        if (keep) {
-            dsc = keep->as<float>() + (*goff)[k.g0];  // groups are laid out in order, chunk after chunk
-        } else {
-            HIPCHK(c, c->d_scores.ensure(k.npairs * sizeof(float)));
-            dsc = c->d_scores.as<float>();
-        }
-        HIPCHK(c, pf::launch_pairs({.st = c->ds, .pool = c->d_pool.as<uint8_t>(), .refs_dev = c->d_refs.as<pf::QImageRef>(),
-                                    .max_lds = k.im.max_lds, .gtab = k.im.gtab, .blocks = c->d_blocks.as<pf::PairBlock>(),
-                                    .nblocks = k.nblocks, .order = nullptr, .slots = c->d_slots.as<int32_t>(),
-                                    .out = dsc, .s = c->stream, .sel = sel}));
-        c->jb.n_dispatch += k.nblocks != 0;  // pf_jobs_stats.pair_dispatches counts every K1' dispatch
-        const float* res = c->h_scores.as<float>();
-        HIPCHK(c, hipMemcpyAsync(c->h_scores.p, dsc, k.npairs * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        k.hl.lap(pf::kHpGpu);
-        par_jobs(k.g1 - k.g0, [&](size_t i) {
-            const size_t g = k.g0 + i;
-            if (!slots[g].empty()) std::memcpy(out[g].data(), res + k.gf[i], slots[g].size() * sizeof(float));
-        }, 256);
-        k.hl.lap(pf::kHpUnpack);
-        return PF_OK;
-    });
-}
-
-// The breakdown of the same pairs (K1t, pf_terms.hip): pair j of group g writes head[dest[g][j]] and
-// the row (W = 7 + T doubles) terms + dest[g][j] * W.  sel as in run_pairs.  A launch's rows are kept
-// to 256 MB (a row is up to 71 doubles where a score is one float).
-int run_pair_terms(pf_ctx* c, const std::vector<int32_t>& qidx, const std::vector<std::vector<int32_t>>& slots,
-                   const std::vector<std::vector<int64_t>>& dest, pf_pair_terms_head* head, double* terms,
-                   const pf::FieldSel& sel, const pf::ProfileView* pv = nullptr) {
-    const size_t W = (size_t)(pf::kNumFixed + c->hc.T);
-    const size_t max_pairs = ((size_t)256u << 20) / (W * sizeof(double));
-    return pair_chunks(c, qidx, slots, (uint32_t)pf::kTermsPairs, max_pairs, pv, [&](const PairChunk& k) -> int {
-        const size_t hb = k.npairs * sizeof(pf_pair_terms_head), tb = k.npairs * W * sizeof(double);
-        HIPCHK(c, c->d_thead.ensure(hb));
-        HIPCHK(c, c->d_terms.ensure(tb));
-        HIPCHK(c, c->h_thead.ensure(hb));
-        HIPCHK(c, c->h_terms.ensure(tb));
-        HIPCHK(c, pf::launch_terms({.st = c->ds, .pool = c->d_pool.as<uint8_t>(), .refs_dev = c->d_refs.as<pf::QImageRef>(),
-                                    .lds = (uint32_t)sizeof(pf::QConst) + k.im.max_img, .gtab = k.im.gtab,
-                                    .blocks = c->d_blocks.as<pf::PairBlock>(), .nblocks = k.nblocks,
-                                    .slots = c->d_slots.as<int32_t>(), .head = c->d_thead.as<pf_pair_terms_head>(),
-                                    .terms = c->d_terms.as<double>(), .s = c->stream, .sel = sel}));
-        HIPCHK(c, hipMemcpyAsync(c->h_thead.p, c->d_thead.p, hb, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_terms.p, c->d_terms.p, tb, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        k.hl.lap(pf::kHpGpu);
-        const pf_pair_terms_head* rh = c->h_thead.as<pf_pair_terms_head>();
-        const double* rt = c->h_terms.as<double>();
-        par_jobs(k.g1 - k.g0, [&](size_t i) {
-            const size_t g = k.g0 + i;
-            for (size_t j = 0; j < slots[g].size(); ++j) {
-                head[dest[g][j]] = rh[k.gf[i] + j];
-                std::memcpy(terms + (size_t)dest[g][j] * W, rt + (k.gf[i] + j) * W, W * sizeof(double));
-            }
-        }, 256);
-        k.hl.lap(pf::kHpUnpack);
-        return PF_OK;
-    });
-}
-
-// K5 mode word (pf_kernels.h): flags only; the block hand-out is launch_post's `claimed`, true for
-// the one-query launches (scan_post with a batch of one, scan_post_resident) and false for batches.
-uint32_t post_mode(bool claimed) {
-    // both instantiations drop candidates that cannot reach the query's shared score threshold
-    // (pf_prune.h): k5_prune=0 off, 1 at block starts only, 2 (default) at round ends too (A/B; the
-    // results are the same bits); k5_prune_batch=0 turns only the batches off (the one-build A/B of
-    // cfg 4); k5_prune_stats=1 counts them (pf_scan_prune_stats)
-    static const long pr = pf::debug_long("k5_prune", 2);
-    static const bool prb = pf::debug_long("k5_prune_batch", 1) != 0;
-    static const bool prs = pf::debug_long("k5_prune_stats", 0) != 0;
-    const uint32_t p = pr <= 0 ? 0u : (pf::kPostPrune | (pr == 1 ? pf::kPostPruneBlockOnly : 0u) | (prs ? pf::kPostPruneStats : 0u));
-    // filtered launches (pf_set_scan_filter): k5_filter_blockout=0 runs the blocks in which no
-    // candidate passes to their end (A/B of the whole-block early-out; the results are the same bits)
-    static const bool fko = pf::debug_long("k5_filter_blockout", 1) == 0;
-    const uint32_t f = fko ? pf::kPostFiltKeepBlocks : 0u;
-    return ((claimed || prb) ? p : 0u) | f;
-}
-
-// Blocks per workgroup of a batched postings scan: a workgroup stages its query's tables once
-// for them (blocks w, w + n/4, ... of one query, so the query's neighbouring blocks still run
-// side by side and share its lists in L2).  cfg 4, r2bs: 1 -> 9.36e9, 2 -> 9.62e9, 4 -> 9.87e9
-// candidates/s.  Round 4 (static block rounds with a claimed tail, a hand-out since retired; the
-// rounds table built once per block): r4t/r4v, one box: 2 -> 1.07e10, 4 -> 1.11e10, 8 -> 1.14e10, 16 -> 1.162e10,
-// 32 -> 1.162e10, 64 -> 1.14e10, 128 -> 1.09e10.  Round 5 final tree (r8q, one box, alternating):
-// 8 -> 1.411e10, 16 -> 1.424-1.428e10, 24 -> 1.435e10, 32 -> 1.432-1.438e10.
-constexpr int kBatchBlocksPerWgDefault = 32;
-// PF_DEBUG k5_batch_blocks=N (A/B)
-int batch_blocks_per_wg() {
-    static const int n = (int)std::max(1L, pf::debug_long("k5_batch_blocks", kBatchBlocksPerWgDefault));
-    return n;
-}
-
-// dynamic LDS of one image's postings scan (K5)
-uint32_t post_image_lds(const pf::QPostHead* h) {
-    return pf::post_lds(pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend));
-}
-// LDS a filtered / windowed launch takes on top of an image's (the filter's and the window's words;
-// pf_kernels.h kFiltLds, kWinLds)
-uint32_t filt_lds(const pf::ScanCall& C) { return (C.filt.fields ? pf::kFiltLds : 0u) + (C.win.fields ? pf::kWinLds : 0u); }
-
-// One synchronous all-candidates call: by uid, by profile or by group, and the scan under a clubs
-// call.  begin() refuses what a collector cannot serve, readies the result rows and the count words
-// and makes the call's options a value (`call`, pf_scan_call.h), which the caller hands to its
-// launches; keys() brings rows back and decodes them; finish() reads the counts and, for a
-// collecting call, sorts the keys.  Rows: the launches get absolute result rows (row r of d_out,
-// count word r) and the base of the count words; a launch that counts one query into word 0 names
-// its row (scan_post_one, a group's passes).
-struct SyncScan {
-    pf_ctx* c;
-    pf_scan_window win;   // the caller's own window (validated)
-    int64_t cap;          // the collector's cap in keys; 0: none
-    // the totals (only under the caller's own PF_WIN_COUNT) and the collected keys go to the context
-    // (pf_scan_window_totals, pf_scan_collected).  false (the clubs calls): the context keeps what
-    // it had; the total stays here and the sorted keys on the device (d_coll_sorted)
-    bool store;
-    pf::ScanCall call{};
-    int nq = 0;
-    int64_t total = 0;    // a collecting call's matches, after finish()
-    explicit SyncScan(pf_ctx* ctx) : c(ctx), win(ctx->win_pub), cap(ctx->coll_cap), store(true) {}
-    SyncScan(pf_ctx* ctx, const pf_scan_window& w, int64_t k) : c(ctx), win(w), cap(k), store(false) {}
-
-    // n queries (or groups) into `rows` rows of d_out, empty (0xFF) first when `fill`
-    int begin(int n, size_t rows, int topk, bool fill) {
-        nq = n;
-        if (n == 0) cap = 0;  // a call of no queries scans nothing
-        if (cap > 0 && n != 1) return c->fail(PF_EUNSUPP, "scan collect: one query (or group) per collecting call");
-        HIPCHK(c, c->d_out.ensure(rows * topk * sizeof(uint64_t)));
-        if (fill) HIPCHK(c, hipMemsetAsync(c->d_out.p, 0xFF, rows * topk * sizeof(uint64_t), c->stream));
-        // a collecting call counts whether or not the caller asked for it: the total is the count word.
-        // Zeroed first: an unknown uid and an empty group stay 0
-        const bool counted = n > 0 && ((win.fields & PF_WIN_COUNT) || cap > 0);
-        if (counted) {
-            HIPCHK(c, c->d_totals.ensure((size_t)n * sizeof(uint32_t)));
-            HIPCHK(c, hipMemsetAsync(c->d_totals.p, 0, (size_t)n * sizeof(uint32_t), c->stream));
-        }
-        call = pf::make_scan_call(c->filt, c->sel, win, c->hc.uid.data(), c->hc.uid.size(), cap, c->d_coll.as<uint64_t>(),
-                                  counted ? c->d_totals.as<uint32_t>() : nullptr);
-        return PF_OK;
-    }
-    // rows [0, n) of d_out on the host, decoded; launched: a launch ran, whose events time the call
-    int keys(int n, int topk, bool launched, int32_t* ou, float* os, int32_t* oc) {
-        std::vector<uint64_t> host((size_t)n * topk);
-        HIPCHK(c, hipMemcpyAsync(host.data(), c->d_out.p, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (launched && c->last_ev0) HIPCHK(c, hipEventElapsedTime(&c->last_scan_ms, c->last_ev0, c->last_ev1));
-        for (int i = 0; i < n; ++i) pf_decode_keys(&host[(size_t)i * topk], topk, ou + (size_t)i * topk, os + (size_t)i * topk, &oc[i]);
-        return PF_OK;
-    }
-    int finish() {
-        if (!call.totals) return PF_OK;
-        std::vector<uint32_t> v((size_t)nq);
-        HIPCHK(c, hipMemcpyAsync(v.data(), call.totals, v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (store && (win.fields & PF_WIN_COUNT)) {
-            c->win_totals.assign(v.begin(), v.end());
-            c->win_totals_set = true;
-        }
-        if (cap <= 0) return PF_OK;
-        total = v[0];
-        if (store) {
-            c->coll_keys.clear();
-            c->coll_total = total;
-            c->coll_set = true;
-        }
-        if (total == 0 || total > cap) return PF_OK;
-        size_t tmp_b = 0;
-        HIPCHK(c, pf::collect_sort_bytes(total, &tmp_b));
-        HIPCHK(c, c->d_coll_tmp.ensure(std::max<size_t>(tmp_b, 16)));
-        HIPCHK(c, c->d_coll_sorted.ensure((size_t)total * sizeof(uint64_t)));
-        HIPCHK(c, pf::collect_sort(call.collect, c->d_coll_sorted.as<uint64_t>(), total, c->d_coll_tmp.p, tmp_b, c->stream));
-        if (!store) return PF_OK;
-        c->coll_keys.resize((size_t)total);
-        HIPCHK(c, hipMemcpyAsync(c->coll_keys.data(), c->d_coll_sorted.p, (size_t)total * sizeof(uint64_t),
-                                 hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return PF_OK;
-    }
-};
-
-int scan_lanes();
-
-// Workgroups of a one-query postings scan: one resident round, or seven eighths of one on the
-// scan lanes, where consecutive queries' launches share the CUs and a launch of fewer workgroups
-// lets the next one start sooner.  Over 200-step lines three quarters read best (cfg 2 1.209 /
-// 1.205 / 1.200e10 at 1,024 -> 1.216 / 1.229 / 1.214e10 at 768 with three lanes, r9j; 896: 1.224 /
-// 1.202e10), but in the driver's 20-step line, where the first and last launches of the timed
-// region run with no neighbour, 768 lost 1.5 % (r9zf) and 896 is the best of 1,024 / 896 / two
-// lanes of 1,024 (1.199 vs 1.190 / 1.196e10, six runs each, r9zg).  PF_DEBUG k5_wgs=N overrides it.
-// More lanes (more hardware queues, scan_lanes) take smaller launches still: 15 lanes of 192 (3/16 of
-// a round) 1.273 / 1.277e10, of 256 1.238-1.267e10, of 320 1.256 / 1.265e10; 7 lanes of 512 or 384
-// 1.235-1.251e10 (r9x-r9z, tools/hwq_probe.sh).
-int one_query_wgs(int resident, bool lanes) {
-    static const long n = pf::debug_long("k5_wgs", 0);
-    if (n > 0) return (int)n;
-    if (!lanes) return resident;
-    const int nl = scan_lanes();
-    const int w = nl >= 12 ? resident * 3 / 16 : (nl >= 6 ? resident / 2 : (nl >= 3 ? resident * 7 / 8 : resident));
-    return std::max(8, w & ~7);
-}
-
-// Timing events of one scan launch (the profiling pool when pf_profile_reset is on).  A
-// launch the caller passes timed = false, or that sampling skips, records nothing and clears
-// last_ev0/last_ev1, so pf_last_scan_ms never reports another launch's time.
-int scan_events(pf_ctx* c, bool& timed, hipEvent_t& e0, hipEvent_t& e1) {
-    e0 = c->ev0;
-    e1 = c->ev1;
-    const auto untimed = [&] {
-        timed = false;
-        c->last_ev0 = c->last_ev1 = nullptr;
-        return (int)PF_OK;
-    };
-    if (!timed) return untimed();
-    if (c->prof_on) {
-        // a timed launch costs ~9 us of stream time (two timestamped events, measured at
-        // 231 vs 222 us per single-query step): sampled launches only when asked
-        if (c->prof_seen++ % c->prof_every != 0) return untimed();
-        if (c->prof_used == c->prof_ev.size()) {
-            if (c->prof_ev.size() >= kProfCap) return untimed();  // pool full: the launch runs untimed
-            hipEvent_t a, b;
-            HIPCHK(c, pf::timing_event(&a));
-            HIPCHK(c, pf::timing_event(&b));
-            c->prof_ev.emplace_back(a, b);
-        }
-        e0 = c->prof_ev[c->prof_used].first;
-        e1 = c->prof_ev[c->prof_used].second;
-        ++c->prof_used;
-    }
-    return PF_OK;
-}
-
-// A single query on a caller's stream runs on the next scan lane (pf_ctx.h ScanLane).  lane_begin
-// picks the lane and its next result row (the lane's stream waits for the copies of a ring group
-// only when it wraps back to it); lane_end has the caller's stream wait for the launch's stop event
-// and copy the row out, and records the group's freed event after its last row's copy.
-struct LaneUse {
-    pf_ctx::ScanLane* ln = nullptr;
-    int row = 0;
-    uint64_t* keys = nullptr;  // the lane's result row
-};
-
-int scan_lanes() {
-    // three by default (the context's stream and both aux streams): 1.204 / 1.205 / 1.206e10 vs
-    // 1.202 / 1.195 / 1.192e10 with two, alternating on one box (r9d, resident images).  More lanes run
-    // on streams of their own and need a process with more hardware queues (GPU_MAX_HW_QUEUES): 15
-    // lanes on 16 queues read +3-5 % over 200 steps but degrade as the backlog grows (1,000 steps
-    // 1.17e10, 2,000 1.06-1.08e10, against 1.24e10 for three lanes on four queues at either length,
-    // r9zd / r9ze; past 16 queues the process oversubscribes the hardware queue slots, r9za), so
-    // they stay an A/B (PF_DEBUG scan_lanes=N, up to 16)
-    static const int n = (int)std::min((long)pf_ctx::kMaxLanes, pf::debug_long("scan_lanes", 3));
-    return n;
-}
-
-int lane_begin(pf_ctx* c, hipStream_t caller, LaneUse& u) {
-    u = LaneUse{};
-    const int nlanes = scan_lanes();
-    if (nlanes < 2 || caller == c->stream) return PF_OK;
-    const int li = c->lane_cur;
-    pf_ctx::ScanLane* ln = &c->lane[li];
-    c->lane_cur = (li + 1) % nlanes;
-    if (!ln->done) {
-        HIPCHK(c, hipEventCreate(&ln->done));  // a launch's stop event (bound to its dispatch)
-        for (hipEvent_t& e : ln->freed) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    // the lanes run on the context's stream and the job pipeline's aux streams (created at open):
-    // streams of their own would share the process's four hardware queues with them
-    const hipStream_t ls[3] = {c->stream, c->jb.aux, c->jb.aux2};
-    ln->st = li < 3 ? ls[li] : c->lane_st[li];
-    if (!ln->st) ln->st = c->stream;
-    const int r = ln->row;
-    ln->row = (r + 1) % pf_ctx::kLaneRows;
-    const int g = r / pf_ctx::kLaneGroupRows;
-    if (r % pf_ctx::kLaneGroupRows == 0 && ln->used[g]) HIPCHK(c, hipStreamWaitEvent(ln->st, ln->freed[g], 0));
-    HIPCHK(c, ln->keys.ensure((size_t)pf_ctx::kLaneRows * pf::kMaxTopK * sizeof(uint64_t)));  // once
-    u.ln = ln;
-    u.row = r;
-    u.keys = ln->keys.as<uint64_t>() + (size_t)r * pf::kMaxTopK;
-    return PF_OK;
-}
-
-int lane_end(pf_ctx* c, const LaneUse& u, hipEvent_t stop, hipStream_t caller, uint64_t* dst, int k) {
-    HIPCHK(c, hipStreamWaitEvent(caller, stop, 0));
-    HIPCHK(c, hipMemcpyAsync(dst, u.keys, (size_t)k * sizeof(uint64_t), hipMemcpyDeviceToDevice, caller));
-    if (u.row % pf_ctx::kLaneGroupRows == pf_ctx::kLaneGroupRows - 1) {
-        const int g = u.row / pf_ctx::kLaneGroupRows;
-        HIPCHK(c, hipEventRecord(u.ln->freed[g], caller));
-        u.ln->used[g] = true;
-    }
-    return PF_OK;
-}
-
-// Workgroups of a one-query K5 launch before the clamp to the shard's blocks (the launches, pf_scan_bytes)
-int one_query_grid(const pf_ctx* c, uint32_t var_lds, bool filtered, bool selected, bool windowed, bool lanes) {
-    return one_query_wgs(c->num_cus * pf::post_blocks_per_cu(var_lds, true, filtered, selected, windowed), lanes);
-}
-
-// Where a K5 launch reads its queries: image q at pool + img_off[q] (its QConst there, or at qconst
-// for a resident image), its ScanSync sync[q], its result row out_rows[q]
-struct PostQueries {
-    const uint8_t *pool, *qconst;
-    const uint32_t* img_off;
-    pf::ScanSync* sync;
-    const int32_t* out_rows;
-};
-
-// Prebuilt images in the order `order` with result rows orows, staged as [image offsets | rows |
-// sync | images] and sent to pool_buf in one async copy on s
-int stage_post(pf_ctx* c, const std::vector<const std::vector<uint8_t>*>& imgs, const std::vector<int>& order,
-               const std::vector<int32_t>& orows, DBuf& pool_buf, hipStream_t s, PostQueries& Q) {
-    const size_t nq = order.size();
-    std::vector<uint32_t> offs;
-    size_t pool_b = 0;
-    for (size_t i = 0; i < nq; ++i) {
-        offs.push_back((uint32_t)pool_b);
-        pool_b += imgs[order[i]]->size();
-    }
-    const size_t offs_b = (nq * 4 + 15) & ~(size_t)15, rows_b = offs_b, sync_b = nq * sizeof(pf::ScanSync);
-    const size_t total = offs_b + rows_b + sync_b + pool_b;
-    pf::HpLap lw;
-    uint8_t* h = c->stage_acquire(total);
-    lw.lap(pf::kHpScanStageWait);
-    if (!h) return c->fail(PF_ENOMEM, "pinned staging allocation failed");
-    std::memcpy(h, offs.data(), nq * 4);
-    std::memcpy(h + offs_b, orows.data(), nq * 4);
-    std::memset(h + offs_b + rows_b, 0, sync_b);
-    for (size_t i = 0; i < nq; ++i)
-        std::memcpy(h + offs_b + rows_b + sync_b + offs[i], imgs[order[i]]->data(), imgs[order[i]]->size());
-    HIPCHK(c, pool_buf.ensure(total));
-    HIPCHK(c, hipMemcpyAsync(pool_buf.p, h, total, hipMemcpyHostToDevice, s));
-    HIPCHK(c, c->stage_release(s));
-    uint8_t* base = pool_buf.as<uint8_t>();
-    Q = PostQueries{base + offs_b + rows_b + sync_b, nullptr, reinterpret_cast<const uint32_t*>(base),
-                    reinterpret_cast<pf::ScanSync*>(base + offs_b + rows_b), reinterpret_cast<const int32_t*>(base + offs_b)};
-    return PF_OK;
-}
-
-// K5 for one query, into row `row` of d_keys: one resident round of workgroups claims the blocks.  A
-// query on a caller's stream goes to the next scan lane: `place` and the launch run on the lane's
-// stream ls with the lane's buffers, and the row is copied out on the caller's stream after the
-// launch's stop event.  place(ln, ls, Q) puts the query where the launch reads it and fills Q (its row
-// a zero: `out` is the row's address): scan_post uploads it, scan_post_resident points into the images.
-template <class Place>
-int scan_post_one(pf_ctx* c, const pf::ScanCall& C, uint32_t var_lds, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed,
-                  Place place) {
-    LaneUse lu;
-    int rc = lane_begin(c, s, lu);
-    if (rc != PF_OK) return rc;
-    pf_ctx::ScanLane* ln = lu.ln;
-    const hipStream_t ls = ln ? ln->st : s;
-    const int blocks = std::max(1, std::min(c->wb_end - c->wb_begin,
-                                            one_query_grid(c, var_lds, C.filt.fields != 0u, C.sel.on != 0u, C.win.fields != 0u, ln != nullptr)));
-    PostQueries Q;
-    rc = place(ln, ls, Q);
-    if (rc != PF_OK) return rc;
-    DBuf& part_buf = ln ? ln->part : c->d_part;
-    HIPCHK(c, part_buf.ensure((size_t)(blocks + 8) * k * sizeof(uint64_t)));  // + 8 group lists (post_tail)
-    hipEvent_t e0, e1;
-    rc = scan_events(c, timed, e0, e1);
-    if (rc != PF_OK) return rc;
-    // timed: the events ride in the kernel's dispatch (its own start / end; r2ff: 1.8 us less per
-    // launch than two marker packets around it); a lane's stop event is bound to the dispatch likewise
-    const hipEvent_t stop = timed ? e1 : (ln ? ln->done : nullptr);
-    uint64_t* dst = d_keys + (size_t)row * k;
-    HIPCHK(c, pf::launch_post({.ps = c->ps, .pool = Q.pool, .img_off = Q.img_off, .var_lds = var_lds, .nq = 1,
-                               .blk_begin = c->wb_begin, .blk_end = c->wb_end, .k = k, .blocks = blocks,
-                               .parts = part_buf.as<uint64_t>(), .out = ln ? lu.keys : dst, .sync = Q.sync,
-                               .out_rows = Q.out_rows, .claimed = true, .mode = post_mode(true), .e0 = timed ? e0 : nullptr,
-                               .e1 = stop, .s = ls, .qconst = Q.qconst, .x = C.k5(row)}));
-    // the caller's stream: wait for the lane's launch (its stop event), copy its row out
-    if (ln && (rc = lane_end(c, lu, stop, s, dst, k)) != PF_OK) return rc;
-    if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
-    return PF_OK;
-}
-
-// K5: the postings scan of prebuilt images (pf_types.h QPostHead layout) into d_keys rows
-// `rows`: one query by scan_post_one, a batch in one launch per occupancy class.
-int scan_post(pf_ctx* c, const pf::ScanCall& C, const std::vector<const std::vector<uint8_t>*>& imgs,
-              const std::vector<int32_t>& rows, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
-    const int nq = (int)imgs.size();
-    if (nq == 0) return PF_OK;
-    if (nq == 1) {  // its upload and launch on the lane's stream (or the caller's, without lanes)
-        const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[0]->data() + sizeof(pf::QConst));
-        return scan_post_one(c, C, pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend), rows[0], k, d_keys, s, timed,
-                             [&](pf_ctx::ScanLane* ln, hipStream_t ls, PostQueries& Q) {
-                                 return stage_post(c, imgs, {0}, {0}, ln ? ln->pool : c->d_pool, ls, Q);
-                             });
-    }
-    // LDS classes: a launch's workgroups all take the LDS of its largest query, so the batch goes
-    // out in one launch per occupancy class (workgroups per CU), the queries of a class contiguous
-    // in the staged arrays; one query with thousands of friends no longer runs every query of a
-    // batch at one workgroup per CU
-    std::vector<uint32_t> vl(nq);
-    std::vector<int> pcu(nq), order(nq);
-    for (int q = 0; q < nq; ++q) {
-        const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q]->data() + sizeof(pf::QConst));
-        vl[q] = pf::post_var_lds(h->n_tok, h->n_tok + h->n_club + h->n_friend);
-        // the hand-out is the call's, not a launch's: a class of one query of a batch stays a batch launch
-        pcu[q] = pf::post_blocks_per_cu(vl[q], false, C.filt.fields != 0u, C.sel.on != 0u, C.win.fields != 0u);
-        order[q] = q;
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pcu[a] > pcu[b]; });
-    std::vector<int32_t> orows(nq);
-    for (int i = 0; i < nq; ++i) orows[i] = rows[order[i]];
-    // A few blocks per workgroup (batch_blocks_per_wg), so the resident workgroups (dispatched
-    // x-fastest) cover a few queries at a time and share their lists and cells in L2; with one
-    // resident round looping over every query's range instead, as for one query, 256 queries run
-    // at once and L2 hits collapse (per-query time 0.2 ms at 4 queries per launch, 0.68 ms at 1024).
-    const int nwb = c->wb_end - c->wb_begin;
-    const int blocks = std::max(1, (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg());
-    PostQueries Q;
-    int rc = stage_post(c, imgs, order, orows, c->d_pool, s, Q);
-    if (rc != PF_OK) return rc;
-    HIPCHK(c, c->d_part.ensure((size_t)nq * (blocks + 8) * k * sizeof(uint64_t)));  // + 8 group lists (post_tail)
-    hipEvent_t e0, e1;
-    rc = scan_events(c, timed, e0, e1);
-    if (rc != PF_OK) return rc;
-    const pf::ScanExtras x = C.k5();
-    // one launch per class (timed: the first one's start and the last one's end time the call)
-    for (int q0 = 0; q0 < nq;) {
-        int q1 = q0;
-        uint32_t vmax = 0;
-        while (q1 < nq && pcu[order[q1]] == pcu[order[q0]]) vmax = std::max(vmax, vl[order[q1++]]);
-        HIPCHK(c, pf::launch_post({.ps = c->ps, .pool = Q.pool, .img_off = Q.img_off + q0, .var_lds = vmax, .nq = q1 - q0,
-                                   .blk_begin = c->wb_begin, .blk_end = c->wb_end, .k = k, .blocks = blocks,
-                                   .parts = c->d_part.as<uint64_t>() + (size_t)q0 * (blocks + 8) * k, .out = d_keys,
-                                   .sync = Q.sync + q0, .out_rows = Q.out_rows + q0, .claimed = false, .mode = post_mode(false),
-                                   .e0 = (timed && q0 == 0) ? e0 : nullptr, .e1 = (timed && q1 == nq) ? e1 : nullptr, .s = s,
-                                   .qconst = nullptr, .x = x}));
-        q0 = q1;
-    }
-    if (timed) { c->last_ev0 = e0; c->last_ev1 = e1; }
-    return PF_OK;
-}
-
-// K5 for ONE query from the resident images (pf_ctx.h ResidentPost): no host image build and no
-// upload.  The image part and its QConst (the user's resident K1' image) are already in HBM, the
-// ScanSync is the lane's own (or the context's, on its own stream), zeroed once and left zeroed by
-// every launch (post_tail), and the merge writes the lane's result row.  HIP calls per step on a
-// caller's stream: the launch (its stop event bound to the dispatch), the caller's wait on it and
-// the row copy (+ one event record per ring group of eight rows).
-bool resident_ok(const pf_ctx* c, const pf::ScanCall& C, int32_t i) {
-    const auto& R = c->rp;
-    return R.on && R.var_lds[i] != 0 && !R.stale[i] && pf::post_lds(R.var_lds[i]) + filt_lds(C) <= kK5LdsCap;
-}
-
-int scan_post_resident(pf_ctx* c, const pf::ScanCall& C, int32_t i, int32_t row, int k, uint64_t* d_keys, hipStream_t s, bool timed) {
-    auto& R = c->rp;
-    return scan_post_one(c, C, R.var_lds[i], row, k, d_keys, s, timed, [&](pf_ctx::ScanLane* ln, hipStream_t ls, PostQueries& Q) {
-        DBuf& sync_buf = ln ? ln->sync : R.d_sync;
-        if (!sync_buf.p) {  // once: every launch leaves it zeroed
-            HIPCHK(c, sync_buf.ensure(sizeof(pf::ScanSync)));
-            HIPCHK(c, hipMemsetAsync(sync_buf.p, 0, sizeof(pf::ScanSync), ls));
-        }
-        Q = PostQueries{R.d_pool.as<uint8_t>() + R.off[i] - sizeof(pf::QConst), c->jb.d_pimg.as<uint8_t>() + c->jb.pimg_off[i],
-                        R.d_zero.as<uint32_t>(), sync_buf.as<pf::ScanSync>(), R.d_zero.as<int32_t>()};
-        return (int)PF_OK;
-    });
-}
-
-// Every user's K5 image part (ResidentPost) built once at open: host threads write the parts of a
-// chunk of users into a pinned buffer (build_query_post_part, the per-call builder's own code, so
-// the bytes equal a per-call image's), one async copy per chunk, two buffers in turn.  Needs the
-// job pipeline's resident K1' images (their QConst) and the postings store; when the parts do not
-// fit a third of the free HBM, or PF_DEBUG resident_post=0, every call builds its image as before.
-int build_resident_post(pf_ctx* c) {
-    auto& R = c->rp;
-    R.on = false;
-    const auto& hc = c->hc;
-    const auto& J = c->jb;
-    if (!c->hp.ok || !J.pimg || pf::debug_long("resident_post", 1) == 0 || hc.n == 0) return PF_OK;
-    const int32_t n = hc.n;
-    std::vector<const std::vector<int32_t>*> adj((size_t)n, nullptr);
-    std::vector<int64_t> off((size_t)n + 1, 0);
-    par_jobs((size_t)n, [&](size_t i) {
-        auto it = hc.adj.find(hc.uid[i]);
-        if (it != hc.adj.end()) adj[i] = &it->second;
-        // users without a resident K1' image (outside the device tables' limits) get none either
-        off[i + 1] = J.img.lg[i] ? (int64_t)pf::post_part_bound(hc, (int32_t)i, (adj[i] ? adj[i]->size() : 0) + 1) : 0;
-    }, 1 << 14);
-    off[0] = sizeof(pf::QConst);  // the first image's QConst-sized lead stays inside the pool
-    for (int32_t i = 0; i < n; ++i) off[i + 1] += off[i];
-    const size_t total = (size_t)off[n];
-    size_t freeb = 0, totb = 0;
-    if (hipMemGetInfo(&freeb, &totb) != hipSuccess || total > freeb / 3) return PF_OK;
-    if (R.d_pool.p) (void)hipFree(R.d_pool.p);
-    R.d_pool.p = nullptr;
-    R.d_pool.cap = 0;
-    if (hipMalloc(&R.d_pool.p, total) != hipSuccess) {  // no room after all: every call builds its image
-        R.d_pool.p = nullptr;
-        (void)hipGetLastError();
-        return PF_OK;
-    }
-    R.d_pool.cap = total;
-    R.var_lds.assign((size_t)n, 0);
-    R.stale.assign((size_t)n, 0);
-    constexpr size_t kChunkBytes = (size_t)256 << 20;
-    PinBuf pin[2];
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (auto& e : ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    int rc = PF_OK;
-    std::atomic<int> bad{0};
-    int b = 0;
-    for (int32_t i0 = 0; i0 < n && rc == PF_OK; b ^= 1) {
-        int32_t i1 = i0 + 1;
-        while (i1 < n && (size_t)(off[i1 + 1] - off[i0]) <= kChunkBytes) ++i1;
-        const size_t bytes = (size_t)(off[i1] - off[i0]);
-        if (hipEventSynchronize(ev[b]) != hipSuccess || pin[b].ensure(std::max<size_t>(bytes, 16)) != hipSuccess) {
-            rc = PF_ENOMEM;  // pinned staging refused: the resident images stay off (below)
-            break;
-        }
-        uint8_t* h = pin[b].as<uint8_t>();
-        par_jobs((size_t)(i1 - i0), [&](size_t j) {
-            const int32_t i = i0 + (int32_t)j;
-            const size_t cap = (size_t)(off[i + 1] - off[i]);
-            if (cap == 0) return;
-            std::vector<int32_t> ex;
-            if (adj[i]) ex = *adj[i];
-            ex.push_back(hc.uid[i]);
-            uint8_t* dst = h + (off[i] - off[i0]);
-            if (pf::build_query_post_part(hc, c->hp, i, ex, dst, cap) == 0) {
-                bad.fetch_add(1);
-                return;
-            }
-            pf::QPostHead hd;
-            std::memcpy(&hd, dst, sizeof hd);
-            R.var_lds[(size_t)i] = pf::post_var_lds(hd.n_tok, hd.n_tok + hd.n_club + hd.n_friend);
-        }, 256);
-        if (hipMemcpyAsync(R.d_pool.as<uint8_t>() + off[i0], h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipEventRecord(ev[b], c->stream) != hipSuccess)
-            rc = c->fail(PF_ENODEV, "resident postings images: upload failed");
-        i0 = i1;
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PF_OK) rc = c->fail(PF_ENODEV, "resident postings images");
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    if (rc == PF_ENOMEM) {  // not fatal: the per-call images serve every query
-        (void)hipFree(R.d_pool.p);
-        R.d_pool.p = nullptr;
-        R.d_pool.cap = 0;
-        return PF_OK;
-    }
-    if (rc != PF_OK) return rc;
-    if (bad.load()) return c->fail(PF_EINTERNAL, "resident postings image larger than its bound");
-    HIPCHK(c, R.d_zero.ensure(64));
-    HIPCHK(c, hipMemset(R.d_zero.p, 0, 64));
-    R.off.swap(off);
-    R.on = true;
-    return PF_OK;
-}
-
-// K1: the record-stream scan for `idx` (valid query indices) into d_keys rows `rows`.
-// One pinned staging buffer [refs | rows | sync | image pool] goes up in a single async copy.
-// build(q, qi) makes query q's K1 image (false: its hash table cannot be built).
-template <class Build>
-int scan_stream_images(pf_ctx* c, const pf::ScanCall& C, int nq, const std::vector<int32_t>& rows, int k, uint64_t* d_keys,
-                       hipStream_t s, bool timed, Build build) {
-    if (nq == 0) return PF_OK;
-    Images im;
-    pf::QImageHost qi;
-    for (int q = 0; q < nq; ++q) {
-        if (!build(q, qi)) return c->fail(PF_EUNSUPP, "query hash table too large");
-        add_image(im, qi);
-    }
-    const int tiles = c->tile_end - c->tile_begin;
-    // one resident round of blocks over the batch: tiles come from a per-query queue, so
-    // the waves that exist balance the work themselves
-    const int per_cu = pf::scan_blocks_per_cu(c->hs.packed, im.gtab, im.max_lds);
-    const int blocks = std::max(1, std::min((tiles + 3) / 4, std::max(1, c->num_cus * per_cu / nq)));
-    const size_t refs_b = (size_t)nq * sizeof(pf::QImageRef);
-    const size_t rows_b = ((size_t)nq * sizeof(int32_t) + 15) & ~(size_t)15;
-    const size_t sync_b = (size_t)nq * sizeof(pf::ScanSync);  // zeros: the per-launch rendezvous
-    const size_t total = refs_b + rows_b + sync_b + im.pool.size();
-    uint8_t* h = c->stage_acquire(total);
-    if (!h) return c->fail(PF_ENOMEM, "pinned staging allocation failed");
-    std::memcpy(h, im.refs.data(), refs_b);
-    std::memcpy(h + refs_b, rows.data(), (size_t)nq * sizeof(int32_t));
-    std::memset(h + refs_b + rows_b, 0, sync_b);
-    std::memcpy(h + refs_b + rows_b + sync_b, im.pool.data(), im.pool.size());
-    HIPCHK(c, c->d_pool.ensure(total));
-    HIPCHK(c, hipMemcpyAsync(c->d_pool.p, h, total, hipMemcpyHostToDevice, s));
-    HIPCHK(c, c->stage_release(s));
-    uint8_t* base = c->d_pool.as<uint8_t>();
-    const pf::QImageRef* d_refs = reinterpret_cast<const pf::QImageRef*>(base);
-    const int32_t* d_rows = reinterpret_cast<const int32_t*>(base + refs_b);
-    pf::ScanSync* d_sync = reinterpret_cast<pf::ScanSync*>(base + refs_b + rows_b);
-    const uint8_t* d_images = base + refs_b + rows_b + sync_b;
-    HIPCHK(c, c->d_part.ensure((size_t)nq * (blocks + 8) * k * sizeof(uint64_t)));  // + 8 group lists (post_tail)
-    hipEvent_t e0, e1;
-    int rc = scan_events(c, timed, e0, e1);
-    if (rc != PF_OK) return rc;
-    if (timed) HIPCHK(c, hipEventRecord(e0, s));
-    HIPCHK(c, pf::launch_scan({.st = c->ds, .pool = d_images, .refs_dev = d_refs, .lds = im.max_lds, .gtab = im.gtab, .nq = nq,
-                               .tile_begin = c->tile_begin, .tile_end = c->tile_end, .k = k, .blocks = blocks,
-                               .parts = c->d_part.as<uint64_t>(), .out = d_keys, .sync = d_sync, .out_rows = d_rows, .s = s,
-                               .x = C.k1()}));
-    if (timed) {
-        HIPCHK(c, hipEventRecord(e1, s));
-        c->last_ev0 = e0;
-        c->last_ev1 = e1;
-    }
-    return PF_OK;
-}
-
-int scan_stream(pf_ctx* c, const pf::ScanCall& C, const std::vector<int32_t>& idx, const std::vector<int32_t>& rows, int k,
-                uint64_t* d_keys, hipStream_t s, bool timed) {
-    std::vector<int32_t> excl;
-    return scan_stream_images(c, C, (int)idx.size(), rows, k, d_keys, s, timed, [&](int q, pf::QImageHost& qi) {
-        const int32_t i = idx[q], u = c->hc.uid[i];
-        excl.clear();
-        auto it = c->hc.adj.find(u);
-        if (it != c->hc.adj.end()) excl = it->second;
-        excl.push_back(u);
-        return pf::build_query(c->hc, c->hs.packed, i, &excl, qi);
-    });
-}
-
-// The all-candidates scan of by-value profiles (pf_recommend_interest_profile) into d_keys rows row0 ..:
-// scan_all's routing with the images built from the views and the call's exclusion lists; there is
-// no resident image to launch from, so one profile takes the upload path (stage_post, scan_post_one).
-int scan_profiles(pf_ctx* c, const pf::ScanCall& C, const std::vector<pf::ProfileOwned>& ps, int32_t row0, int k, uint64_t* d_keys,
-                  hipStream_t s, bool timed) {
-    const size_t nq = ps.size();
-    std::vector<int32_t> all(nq);
-    for (size_t q = 0; q < nq; ++q) all[q] = (int32_t)q;
-    // `which` names profiles of ps (the builder below indexes ps by it); their result rows are those
-    // indices moved to this chunk's place in the call, row0
-    auto stream = [&](const std::vector<int32_t>& which, bool tm) {
-        std::vector<int32_t> rows(which);
-        for (int32_t& r : rows) r += row0;
-        return scan_stream_images(c, C, (int)which.size(), rows, k, d_keys, s, tm, [&](int q, pf::QImageHost& qi) {
-            const pf::ProfileOwned& p = ps[(size_t)which[q]];
-            return pf::build_query(c->hc, c->hs.packed, p.v, &p.excl, qi);
-        });
-    };
-    if (!c->use_post()) return stream(all, timed);
-    std::vector<std::vector<uint8_t>> imgs(nq);
-    std::vector<uint8_t> fits(nq, 1);
-    par_jobs(nq, [&](size_t q) {
-        pf::build_query_post(c->hc, c->hp, ps[q].v, ps[q].excl, imgs[q]);
-        const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q].data() + sizeof(pf::QConst));
-        fits[q] = post_image_lds(h) + filt_lds(C) <= kK5LdsCap;
-    });
-    std::vector<const std::vector<uint8_t>*> pi;
-    std::vector<int32_t> prow, sidx;
-    for (size_t q = 0; q < nq; ++q) {
-        if (fits[q]) { pi.push_back(&imgs[q]); prow.push_back(row0 + (int32_t)q); }
-        else sidx.push_back((int32_t)q);
-    }
-    const int rc = scan_post(c, C, pi, prow, k, d_keys, s, timed);
-    if (rc != PF_OK) return rc;
-    return stream(sidx, timed && pi.empty());
-}
-
-// All-candidates scan for `idx` (valid query indices) into d_keys rows `rows`.  The postings
-// scan (K5) serves every query whose lists fit one workgroup's LDS; a query naming more lists
-// (a user with ~15k friends or thousands of tokens) goes to the record-stream scan (K1) in a
-// launch of its own, so one heavy user never fails the batch.
-int scan_all(pf_ctx* c, const pf::ScanCall& C, const std::vector<int32_t>& idx, const std::vector<int32_t>& rows, int k,
-             uint64_t* d_keys, hipStream_t s, bool timed) {
-    if (idx.empty()) return PF_OK;
-    if (!c->use_post()) return scan_stream(c, C, idx, rows, k, d_keys, s, timed);
-    pf::HpLap lp;  // PF_DEBUG host_prof=1: image build / staging + launch clocks
-    if (pf::host_prof().on) pf::host_prof().ns[pf::kHpScanCalls] += 1000000000LL;
-    // one query from the resident images: on the context's stream or a scan lane (another stream
-    // without lanes takes the upload path: the resident ScanSync of the context's stream is not
-    // shared with a stream it is not ordered against)
-    if (idx.size() == 1 && resident_ok(c, C, idx[0]) && (s == c->stream || scan_lanes() >= 2)) {
-        const int rc = scan_post_resident(c, C, idx[0], rows[0], k, d_keys, s, timed);
-        lp.lap(pf::kHpScanLaunch);
-        return rc;
-    }
-    // the query images (host, ~35 us each) on threads for a batch
-    std::vector<std::vector<uint8_t>> imgs(idx.size());
-    std::vector<uint8_t> fits(idx.size(), 1);
-    par_jobs(idx.size(), [&](size_t q) {
-        const int32_t i = idx[q], u = c->hc.uid[i];
-        std::vector<int32_t> ex;
-        auto it = c->hc.adj.find(u);
-        if (it != c->hc.adj.end()) ex = it->second;
-        ex.push_back(u);
-        pf::build_query_post(c->hc, c->hp, i, ex, imgs[q]);
-        const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[q].data() + sizeof(pf::QConst));
-        fits[q] = post_image_lds(h) + filt_lds(C) <= kK5LdsCap;
-    });
-    std::vector<const std::vector<uint8_t>*> pi;
-    std::vector<int32_t> prow, sidx, srow;
-    for (size_t q = 0; q < idx.size(); ++q) {
-        if (fits[q]) { pi.push_back(&imgs[q]); prow.push_back(rows[q]); }
-        else { sidx.push_back(idx[q]); srow.push_back(rows[q]); }
-    }
-    lp.lap(pf::kHpScanImage);
-    int rc = scan_post(c, C, pi, prow, k, d_keys, s, timed);
-    lp.lap(pf::kHpScanLaunch);
-    if (rc != PF_OK) return rc;
-    return scan_stream(c, C, sidx, srow, k, d_keys, s, timed && pi.empty());
-}
-
-// Bytes the postings scan (K5) reads for one query image over this context's blocks, by the
-// kernel's own access pattern (fas_post_kernel): per block, 32 B of header per candidate, two
-// cell words per list, and every entry of the list's cell-rounded range (4 B; token entries
-// also their 8-B norm); per block the exclusion list (whole when <= 256 entries); per
-// workgroup the staged image.
-int64_t post_query_bytes(const pf_ctx* c, const std::vector<uint8_t>& img, int wgs) {
-    const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(img.data() + sizeof(pf::QConst));
-    const pf::QTok* toks = reinterpret_cast<const pf::QTok*>(img.data() + h->tok_off);
-    const pf::PList* sets = reinterpret_cast<const pf::PList*>(img.data() + h->set_off);
-    const uint32_t B = (uint32_t)c->ps.bsize, n = (uint32_t)c->ps.n;
-    const uint32_t* cells = c->hp.cells.data();
-    int64_t bytes = 0;
-    auto list_bytes = [&](const pf::PList& L, int per) {
-        for (int32_t blk = c->wb_begin; blk < c->wb_end; ++blk) {
-            const uint32_t c0 = (uint32_t)blk * B, c1 = std::min(c0 + B, n) - 1;
-            const uint32_t lo = cells[L.cell_off + (c0 >> L.shift)], hi = cells[L.cell_off + (c1 >> L.shift) + 1];
-            bytes += (int64_t)(hi - lo) * per + 8;
-        }
-    };
-    for (int j = 0; j < h->n_tok; ++j) list_bytes(toks[j].l, 12);
-    for (int j = 0; j < h->n_club + h->n_friend; ++j) list_bytes(sets[j], 4);
-    const int64_t nb = c->wb_end - c->wb_begin;
-    const int64_t cands = std::max<int64_t>(0, std::min<int64_t>((int64_t)c->wb_end * B, n) - (int64_t)c->wb_begin * B);
-    bytes += cands * 32;
-    bytes += nb * 4 * (int64_t)std::min(h->n_excl, (int32_t)pf::kPostThreads);
-    bytes += (int64_t)std::min<int64_t>(nb, wgs) * (int64_t)img.size();
-    return bytes;
-}
-
-int emit_jobs(pf_ctx* c, std::vector<pf::Job>& jobs, int topk, int32_t* ou, float* os, int32_t* oc) {
-    for (size_t i = 0; i < jobs.size(); ++i) oc[i] = 0;
-    if (topk == 0 || jobs.empty()) return PF_OK;
-    const int rc = pf::run_jobs(c, jobs);
-    if (rc != PF_OK) return rc;
-    for (size_t i = 0; i < jobs.size(); ++i) pf::emit(jobs[i].out, (int)i, topk, ou, os, oc);
-    return PF_OK;
-}
-
-}  // namespace
-
-namespace pf {
 
 const std::unordered_map<int32_t, std::vector<int32_t>>& base_adj(const pf_ctx* c) { return c->hc.adj; }
 
@@ -1018,49 +61,66 @@ HostProf& host_prof() {
     return h;
 }
 
+// The device form of a public selection: PF_EINVAL for unknown bits; NULL, or one that leaves out
+// nothing of this engine's T columns, is no selection (on == 0).
+int make_select(const pf_ctx* c, const pf_field_select* s, pf::FieldSel& d) {
+    d = pf::FieldSel{};
+    if (!s) return PF_OK;
+    if ((s->fixed & ~pf::kSelFixedAll) || s->flags != 0u) return PF_EINVAL;
+    if (pf::select_is_all(s->fixed, s->cols, c->hc.T)) return PF_OK;
+    d.fixed = s->fixed;
+    d.on = 1u;
+    d.cols = s->cols & pf::select_low(c->hc.T);
+    return PF_OK;
+}
+
+// a caller's window as a call's options take it (null or fields == 0: none), or PF_EINVAL with the reason
+int make_window(pf_ctx* c, const pf_scan_window* w, pf_scan_window& d) {
+    d = pf_scan_window{};
+    if (!w || w->fields == 0u) return PF_OK;
+    if ((w->fields & ~pf::kWinAllFields) || w->flags != 0u) return c->fail(PF_EINVAL, "scan window: unknown bits in fields / flags");
+    if ((w->fields & PF_WIN_MIN) && std::isnan(w->min_score)) return c->fail(PF_EINVAL, "scan window: min_score is NaN");
+    if ((w->fields & PF_WIN_AFTER) && std::isnan(w->after_score)) return c->fail(PF_EINVAL, "scan window: after_score is NaN");
+    d = *w;
+    return PF_OK;
+}
+
 }  // namespace pf
 
-extern "C" {
+namespace {
 
-int pf_abi_version(void) { return PF_ABI_VERSION; }
-
-int pf_open(const pf_corpus_desc* desc, int device, pf_ctx** out) {
-    if (!out) { g_open_error = "null out"; return PF_EINVAL; }
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        g_open_error = "no HIP device (the FAS engine has no CPU fallback)";
-        return PF_ENODEV;
+// PF_DEBUG host_prof=1: pf_open stage clocks on stderr
+struct OpenClock {
+    const bool prof = pf::host_prof().on;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        const auto t1 = std::chrono::steady_clock::now();
+        if (prof) fprintf(stderr, "[pf_open] %s %.3f s\n", what, std::chrono::duration<double>(t1 - t0).count());
+        t0 = t1;
     }
-    if (device < 0 || device >= ndev) { g_open_error = "bad device ordinal"; return PF_EINVAL; }
-    pf_ctx* c = new pf_ctx();
+};
+
+// pf_open's stages, in the order they run; a failing one leaves its reason in c->err
+int open_device(pf_ctx* c, int device) {
     c->device = device;
-    auto bail = [&](int rc) {
-        g_open_error = c->err;
-        delete c;
-        return rc;
-    };
-    if (hipSetDevice(device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(PF_ENODEV); }
+    if (hipSetDevice(device) != hipSuccess) { c->err = "hipSetDevice failed"; return PF_ENODEV; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
         c->num_cus = prop.multiProcessorCount;
         if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
             c->err = std::string("device is ") + prop.gcnArchName + ", the kernels are built for gfx950";
-            return bail(PF_ENODEV);
+            return PF_ENODEV;
         }
     }
-    const bool prof = pf::host_prof().on;
-    auto t0 = std::chrono::steady_clock::now();
-    auto stage = [&](const char* what) {  // PF_DEBUG host_prof=1: pf_open stage clocks on stderr
-        const auto t1 = std::chrono::steady_clock::now();
-        if (prof) fprintf(stderr, "[pf_open] %s %.3f s\n", what, std::chrono::duration<double>(t1 - t0).count());
-        t0 = t1;
-    };
+    return PF_OK;
+}
+
+int open_host_builds(pf_ctx* c, const pf_corpus_desc* desc, OpenClock& stage) {
     int rc = pf::build_host_corpus(desc, c->hc, c->err);
-    if (rc != PF_OK) return bail(rc);
+    if (rc != PF_OK) return rc;
     stage("host corpus (sorted rows, idf, norms)");
     rc = pf::build_store(c->hc, c->hs, c->err);
-    if (rc != PF_OK) return bail(rc);
+    if (rc != PF_OK) return rc;
     stage("tile store");
     pf::build_postings(c->hc, c->hp);  // hp.ok = false: the stream scan serves every query
     stage("postings store");
@@ -1070,6 +130,10 @@ int pf_open(const pf_corpus_desc* desc, int device, pf_ctx** out) {
         if (!strcmp(sk, "stream")) c->scan_kind = PF_SCAN_STREAM;
         else if (!strcmp(sk, "postings") && c->hp.ok) c->scan_kind = PF_SCAN_POSTINGS;
     }
+    return PF_OK;
+}
+
+int open_streams(pf_ctx* c) {
     // the job pipeline's two aux streams are created here with the context's own, so the three
     // take consecutive hardware queues whatever streams the host process creates later (created
     // at the first job call, after a torch stream pool, they ran the cfg-3 sub-record of the
@@ -1079,13 +143,17 @@ int pf_open(const pf_corpus_desc* desc, int device, pf_ctx** out) {
         hipStreamCreateWithFlags(&c->jb.aux2, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
         c->err = "stream/event creation failed";
-        return bail(PF_ENODEV);
+        return PF_ENODEV;
     }
-    for (int l = 3; l < scan_lanes(); ++l)  // lanes past the context's and the aux streams
+    for (int l = 3; l < pf::scan_lanes(); ++l)  // lanes past the context's and the aux streams
         if (hipStreamCreateWithFlags(&c->lane_st[l], hipStreamNonBlocking) != hipSuccess) {
             c->err = "stream creation failed";
-            return bail(PF_ENODEV);
+            return PF_ENODEV;
         }
+    return PF_OK;
+}
+
+int upload_stores(pf_ctx* c) {
     auto& hs = c->hs;
     hipError_t e = hipSuccess;
     if (e == hipSuccess) e = upload(c, c->d_stream, hs.stream);
@@ -1109,30 +177,17 @@ int pf_open(const pf_corpus_desc* desc, int device, pf_ctx** out) {
         if (e == hipSuccess) e = upload(c, c->d_cells, hp.cells);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    stage("upload");
-    if (e != hipSuccess) {
-        c->hip_fail(e, "corpus upload");
-        return bail(e == hipErrorOutOfMemory ? PF_ENOMEM : PF_ENODEV);
-    }
-    c->ds.row_pad = c->d_rowstore.as<uint4>() + hs.row_off[c->hc.n];  // build_store's trailing padding line
+    if (e == hipSuccess) return PF_OK;
+    c->hip_fail(e, "corpus upload");
+    return e == hipErrorOutOfMemory ? PF_ENOMEM : PF_ENODEV;
+}
+
+// the device views of the stores (c->ds, c->ps), the byte figures and the whole-corpus shard
+void bind_stores(pf_ctx* c) {
+    auto& hs = c->hs;
     c->stream_bytes = (int64_t)hs.stream.size() * 16;
     c->norm_bytes = (int64_t)hs.norms.size() * 8;
-    if (c->hp.ok) {
-        c->post_bytes = (int64_t)c->hp.hdr.size() * 16 + (int64_t)c->hp.post.size() * 4 +
-                        (int64_t)c->hp.pnorm.size() * 8 + (int64_t)c->hp.cells.size() * 4;
-        c->ps.n_post = (uint32_t)c->hp.post.size();
-        c->ps.n_tok_entries = (uint32_t)c->hp.pnorm.size();
-        c->ps.n_cells = (uint32_t)c->hp.cells.size();
-    }
-    // the host copies of the device stores (~5 GB at 1.63M users) are returned to the system on a
-    // detached thread: unmapping them takes ~0.6 s that pf_open need not wait for
-    try {
-        std::thread([a = std::move(hs.stream), b = std::move(hs.norms), r = std::move(hs.rows),
-                     p = std::move(c->hp.post), q = std::move(c->hp.pnorm)]() mutable {}).detach();
-    } catch (...) {  // no thread to be had: free them here (no exception crosses the C ABI)
-        hs.stream.clear(); hs.norms.clear(); hs.rows.clear(); c->hp.post.clear(); c->hp.pnorm.clear();
-    }
-    std::vector<uint64_t>().swap(hs.row_off);
+    c->ds.row_pad = c->d_rowstore.as<uint4>() + hs.row_off[c->hc.n];  // build_store's trailing padding line
     c->ds.stream = c->d_stream.as<uint4>();
     c->ds.tile_off = c->d_tile_off.as<uint64_t>();
     c->ds.tile_steps = c->d_tile_steps.as<uint32_t>();
@@ -1152,31 +207,128 @@ int pf_open(const pf_corpus_desc* desc, int device, pf_ctx** out) {
     c->ds.n_cols = c->hc.T;
     c->tile_begin = 0;
     c->tile_end = c->ds.n_tiles;
-    if (c->hp.ok) {
-        auto& hp = c->hp;
-        std::vector<uint4>().swap(hp.hdr);
-        // hp.post / hp.pnorm went with the host stores above
-        // hp.cells stays on the host too: pf_scan_bytes reads the lists' cell ranges
-        c->ps.hdr = c->d_phdr.as<uint4>();
-        c->ps.post = c->d_post.as<uint32_t>();
-        c->ps.pnorm = c->d_pnorm.as<double>();
-        c->ps.cells = c->d_cells.as<uint32_t>();
-        c->ps.n = c->hc.n;
-        // block size: the LDS capacity.  Sizing blocks to fill whole waves of resident
-        // workgroups (798 at 1.6M) measured slower (258 vs 244 us): per-block costs dominate
-        // the half-empty last wave.  PF_DEBUG k5_block overrides it (tests).
-        {
-            const int64_t b = pf::debug_long("k5_block", pf::kBlockCands);
-            c->ps.bsize = (int32_t)std::max<int64_t>(64, std::min<int64_t>(pf::kBlockCands, b));
-        }
-        c->ps.n_blocks = (c->hc.n + c->ps.bsize - 1) / c->ps.bsize;
-        c->wb_begin = 0;
-        c->wb_end = c->ps.n_blocks;
+    if (!c->hp.ok) return;
+    auto& hp = c->hp;
+    c->post_bytes = (int64_t)hp.hdr.size() * 16 + (int64_t)hp.post.size() * 4 + (int64_t)hp.pnorm.size() * 8 +
+                    (int64_t)hp.cells.size() * 4;
+    c->ps.n_post = (uint32_t)hp.post.size();
+    c->ps.n_tok_entries = (uint32_t)hp.pnorm.size();
+    c->ps.n_cells = (uint32_t)hp.cells.size();
+    c->ps.hdr = c->d_phdr.as<uint4>();
+    c->ps.post = c->d_post.as<uint32_t>();
+    c->ps.pnorm = c->d_pnorm.as<double>();
+    c->ps.cells = c->d_cells.as<uint32_t>();
+    c->ps.n = c->hc.n;
+    // block size: the LDS capacity.  Sizing blocks to fill whole waves of resident
+    // workgroups (798 at 1.6M) measured slower (258 vs 244 us): per-block costs dominate
+    // the half-empty last wave.  PF_DEBUG k5_block overrides it (tests).
+    const int64_t b = pf::debug_long("k5_block", pf::kBlockCands);
+    c->ps.bsize = (int32_t)std::max<int64_t>(64, std::min<int64_t>(pf::kBlockCands, b));
+    c->ps.n_blocks = (c->hc.n + c->ps.bsize - 1) / c->ps.bsize;
+    c->wb_begin = 0;
+    c->wb_end = c->ps.n_blocks;
+}
+
+// The host copies of the device stores (~5 GB at 1.63M users) are returned to the system on a
+// detached thread: unmapping them takes ~0.6 s that pf_open need not wait for.  hp.cells stays on
+// the host: pf_scan_bytes reads the lists' cell ranges.
+void release_host_stores(pf_ctx* c) {
+    auto& hs = c->hs;
+    try {
+        std::thread([a = std::move(hs.stream), b = std::move(hs.norms), r = std::move(hs.rows),
+                     p = std::move(c->hp.post), q = std::move(c->hp.pnorm)]() mutable {}).detach();
+    } catch (...) {  // no thread to be had: free them here (no exception crosses the C ABI)
+        hs.stream.clear(); hs.norms.clear(); hs.rows.clear(); c->hp.post.clear(); c->hp.pnorm.clear();
     }
+    std::vector<uint64_t>().swap(hs.row_off);
+    std::vector<uint4>().swap(c->hp.hdr);
+}
+
+pf::AdjView plain_view(const pf_ctx* c) {
+    pf::AdjView v;
+    v.base = &c->hc.adj;
+    return v;
+}
+
+// nq calls of one recommender, one per uid of q, under the engine's own adjacency
+std::vector<pf::Job> make_jobs(const pf_ctx* c, int kind, const int32_t* q, int32_t nq, int32_t topk, int32_t limit,
+                               bool all_candidates) {
+    std::vector<pf::Job> jobs((size_t)nq);
+    for (int32_t i = 0; i < nq; ++i) {
+        jobs[i].kind = kind;
+        jobs[i].uid = q[i];
+        jobs[i].topk = topk;
+        jobs[i].limit = limit;
+        jobs[i].all_candidates = all_candidates;
+        jobs[i].view = plain_view(c);
+    }
+    return jobs;
+}
+
+int emit_jobs(pf_ctx* c, std::vector<pf::Job> jobs, int topk, int32_t* ou, float* os, int32_t* oc) {
+    for (size_t i = 0; i < jobs.size(); ++i) oc[i] = 0;
+    if (topk == 0 || jobs.empty()) return PF_OK;
+    const int rc = pf::run_jobs(c, jobs);
+    if (rc != PF_OK) return rc;
+    for (size_t i = 0; i < jobs.size(); ++i) pf::emit(jobs[i].out, (int)i, topk, ou, os, oc);
+    return PF_OK;
+}
+
+// FAS of the pairs (a[i], b[i]) (a == nullptr: of the profile pv with every b[i]); an unknown uid's is NaN
+int scored_pairs(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, float* out, const pf::FieldSel& sel,
+                 const pf::ProfileView* pv) {
+    pf::PairGroups pg(true);  // one float per pair: where[i] = (group, position), no per-group destinations
+    pf::group_pairs(c, a, b, 0, n, pg);
+    for (int64_t i = 0; i < n; ++i) out[i] = NAN;
+    std::vector<std::vector<float>> res;
+    const int rc = pf::run_pairs(c, pg.qidx, pg.slots, res, nullptr, nullptr, sel, pv);
+    if (rc != PF_OK) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        if (pg.where[(size_t)i].first >= 0) out[i] = res[pg.where[(size_t)i].first][pg.where[(size_t)i].second];
+    return PF_OK;
+}
+
+// an unknown uid's breakdown: NaN, nothing present, the row all 0.0 (W doubles)
+void blank_terms(pf_pair_terms_head* head, double* terms, int64_t n, size_t W) {
+    for (int64_t i = 0; i < n; ++i) head[i] = pf_pair_terms_head{NAN, 0u, 0ull};
+    std::fill(terms, terms + (size_t)n * W, 0.0);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pf_abi_version(void) { return PF_ABI_VERSION; }
+
+int pf_open(const pf_corpus_desc* desc, int device, pf_ctx** out) {
+    if (!out) { g_open_error = "null out"; return PF_EINVAL; }
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        g_open_error = "no HIP device (the FAS engine has no CPU fallback)";
+        return PF_ENODEV;
+    }
+    if (device < 0 || device >= ndev) { g_open_error = "bad device ordinal"; return PF_EINVAL; }
+    pf_ctx* c = new pf_ctx();
+    auto bail = [&](int rc) {
+        g_open_error = c->err;
+        delete c;
+        return rc;
+    };
+    int rc = open_device(c, device);
+    if (rc != PF_OK) return bail(rc);
+    OpenClock stage;
+    if ((rc = open_host_builds(c, desc, stage)) != PF_OK) return bail(rc);
+    if ((rc = open_streams(c)) != PF_OK) return bail(rc);
+    rc = upload_stores(c);
+    stage("upload");
+    if (rc != PF_OK) return bail(rc);
+    bind_stores(c);
+    release_host_stores(c);
     rc = pf::jobs_open(c);  // device graph + image-builder tables (the recommenders' pipeline)
     if (rc != PF_OK) return bail(rc);
     stage("job pipeline (graph, image tables)");
-    rc = build_resident_post(c);  // every user's K5 image part (the one-query scans' resident images)
+    rc = pf::build_resident_post(c);  // every user's K5 image part (the one-query scans' resident images)
     if (rc != PF_OK) return bail(rc);
     stage(c->rp.on ? ("resident postings images, " + std::to_string(c->rp.d_pool.cap >> 20) + " MiB").c_str()
                    : "resident postings images (off)");
@@ -1232,109 +384,42 @@ static_assert(PF_SEL_FIXED_ALL == pf::kSelFixedAll && (1u << PF_F_PUBLIC) == pf:
               "pf_select.h restates the public field bits");
 static_assert(sizeof(pf_field_select) == 16 && sizeof(pf_field_select) == sizeof(pf::FieldSel), "pf_field_select is 16 B");
 
-// The device form of a public selection: PF_EINVAL for unknown bits; NULL, or one that leaves out
-// nothing of this engine's T columns, is no selection (on == 0).
-static int make_select(const pf_ctx* c, const pf_field_select* s, pf::FieldSel& d) {
-    d = pf::FieldSel{};
-    if (!s) return PF_OK;
-    if ((s->fixed & ~pf::kSelFixedAll) || s->flags != 0u) return PF_EINVAL;
-    if (pf::select_is_all(s->fixed, s->cols, c->hc.T)) return PF_OK;
-    d.fixed = s->fixed;
-    d.on = 1u;
-    d.cols = s->cols & pf::select_low(c->hc.T);
-    return PF_OK;
-}
-
 int pf_set_scan_select(pf_ctx* c, const pf_field_select* s) {
     if (!c) return PF_EINVAL;
     pf::FieldSel d;
-    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "scan select: unknown bits in fixed / flags");
+    if (pf::make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "scan select: unknown bits in fixed / flags");
     c->sel = d;
     return PF_OK;
 }
 
-static int fas_pairs(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, float* out, const pf::FieldSel& sel);
-
 int pf_fas_pairs(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, float* out) {
     if (!c || n < 0 || (n && (!a || !b || !out))) return PF_EINVAL;
-    return fas_pairs(c, a, b, n, out, pf::FieldSel{});
+    (void)hipSetDevice(c->device);
+    return scored_pairs(c, a, b, n, out, pf::FieldSel{}, nullptr);
 }
 
 int pf_fas_pairs_select(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, const pf_field_select* s, float* out) {
     if (!c || n < 0 || (n && (!a || !b || !out))) return PF_EINVAL;
     pf::FieldSel d;
-    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "pairs select: unknown bits in fixed / flags");
-    return fas_pairs(c, a, b, n, out, d);
-}
-
-static int fas_pairs(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, float* out, const pf::FieldSel& sel) {
+    if (pf::make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "pairs select: unknown bits in fixed / flags");
     (void)hipSetDevice(c->device);
-    std::unordered_map<int32_t, int32_t> group;  // query idx -> group
-    std::vector<int32_t> qidx;
-    std::vector<std::vector<int32_t>> slots;
-    std::vector<std::pair<int32_t, int32_t>> where(n, {-1, -1});
-    for (int64_t i = 0; i < n; ++i) {
-        out[i] = NAN;
-        int32_t ia = c->hc.idx_of(a[i]), ib = c->hc.idx_of(b[i]);
-        if (ia < 0 || ib < 0) continue;
-        auto it = group.find(ia);
-        if (it == group.end()) {
-            it = group.emplace(ia, (int32_t)qidx.size()).first;
-            qidx.push_back(ia);
-            slots.emplace_back();
-        }
-        where[i] = {it->second, (int32_t)slots[it->second].size()};
-        slots[it->second].push_back(c->hs.slot_of_idx[ib]);
-    }
-    std::vector<std::vector<float>> res;
-    int rc = run_pairs(c, qidx, slots, res, nullptr, nullptr, sel);
-    if (rc != PF_OK) return rc;
-    for (int64_t i = 0; i < n; ++i)
-        if (where[i].first >= 0) out[i] = res[where[i].first][where[i].second];
-    return PF_OK;
+    return scored_pairs(c, a, b, n, out, d, nullptr);
 }
 
 static_assert(sizeof(pf_pair_terms_head) == 16, "pf_pair_terms_head is 16 B");
 
 int32_t pf_num_cols(const pf_ctx* c) { return c ? c->hc.T : 0; }
 
-// pairs grouped by their query, each remembering where its head and row go
-struct TermGroups {
-    std::unordered_map<int32_t, int32_t> group;  // query idx -> group
-    std::vector<int32_t> qidx;
-    std::vector<std::vector<int32_t>> slots;
-    std::vector<std::vector<int64_t>> dest;
-    void add(int32_t ia, int32_t slot, int64_t to) {
-        auto it = group.find(ia);
-        if (it == group.end()) {
-            it = group.emplace(ia, (int32_t)qidx.size()).first;
-            qidx.push_back(ia);
-            slots.emplace_back();
-            dest.emplace_back();
-        }
-        slots[it->second].push_back(slot);
-        dest[it->second].push_back(to);
-    }
-};
-
 int pf_fas_pairs_terms(pf_ctx* c, const int32_t* a, const int32_t* b, int64_t n, const pf_field_select* s,
                        pf_pair_terms_head* head, double* terms) {
     if (!c || n < 0 || (n && (!a || !b || !head || !terms))) return PF_EINVAL;
     pf::FieldSel d;
-    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "pairs terms: unknown bits in fixed / flags");
+    if (pf::make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "pairs terms: unknown bits in fixed / flags");
     (void)hipSetDevice(c->device);
     const size_t W = (size_t)(PF_NUM_FIXED + c->hc.T);
-    TermGroups tg;
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t ia = c->hc.idx_of(a[i]), ib = c->hc.idx_of(b[i]);
-        if (ia < 0 || ib < 0) {  // an unknown uid: NaN, nothing present, the row all 0.0
-            head[i] = pf_pair_terms_head{NAN, 0u, 0ull};
-            std::fill(terms + (size_t)i * W, terms + (size_t)(i + 1) * W, 0.0);
-            continue;
-        }
-        tg.add(ia, c->hs.slot_of_idx[ib], i);
-    }
-    return run_pair_terms(c, tg.qidx, tg.slots, tg.dest, head, terms, d);
+    pf::PairGroups tg;
+    pf::group_pairs(c, a, b, 0, n, tg, [&](int64_t i) { blank_terms(head + i, terms + (size_t)i * W, 1, W); });
+    return pf::run_pair_terms(c, tg.qidx, tg.slots, tg.dest, head, terms, d);
 }
 
 int pf_recommend_interest_all_terms(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, int32_t* ou, float* os,
@@ -1344,7 +429,7 @@ int pf_recommend_interest_all_terms(pf_ctx* c, const int32_t* q, int32_t nq, int
     const int rc = pf_recommend_interest(c, q, nq, topk, PF_MODE_ALL, 0, ou, os, oc);
     if (rc != PF_OK) return rc;
     // the (query, winner) pairs, formed on the host from the list the scan returned
-    TermGroups tg;
+    pf::PairGroups tg;
     for (int32_t i = 0; i < nq; ++i) {
         if (oc[i] <= 0) continue;
         const int32_t ia = c->hc.idx_of(q[i]);
@@ -1354,62 +439,7 @@ int pf_recommend_interest_all_terms(pf_ctx* c, const int32_t* q, int32_t nq, int
             tg.add(ia, c->hs.slot_of_idx[ib], (int64_t)i * topk + j);
         }
     }
-    return run_pair_terms(c, tg.qidx, tg.slots, tg.dest, head, terms, c->sel);
-}
-
-// the by-value profiles of a call, checked and resolved against the engine's corpus
-static int resolve_profiles(pf_ctx* c, const pf_query_profile* q, int32_t nq, std::vector<pf::ProfileOwned>& ps) {
-    ps.clear();
-    ps.resize((size_t)nq);  // sized once: the views point into their own elements
-    for (int32_t i = 0; i < nq; ++i) {
-        std::string why;
-        const int rc = pf::make_profile_view(c->hc, c->hs.packed, q[i], ps[(size_t)i], why);
-        if (rc != PF_OK) return c->fail(rc, why);
-    }
-    return PF_OK;
-}
-
-static int recommend_profiles(pf_ctx* c, SyncScan& S, const std::vector<pf::ProfileOwned>& ps, int32_t topk, int32_t* ou,
-                              float* os, int32_t* oc) {
-    const int32_t nq = (int32_t)ps.size();
-    int rc = S.begin(nq, (size_t)nq, topk, false);
-    if (rc != PF_OK) return rc;
-    const size_t chunk = 256;
-    for (size_t b = 0; b < ps.size(); b += chunk) {
-        // a launch's share of a longer call: views of the same arrays
-        std::vector<pf::ProfileOwned> part;
-        const std::vector<pf::ProfileOwned>* use = &ps;
-        if (ps.size() > chunk) {
-            part.resize(std::min(ps.size(), b + chunk) - b);
-            for (size_t i = 0; i < part.size(); ++i) {
-                part[i].v = ps[b + i].v;
-                part[i].excl = ps[b + i].excl;
-            }
-            use = &part;
-        }
-        if ((rc = scan_profiles(c, S.call, *use, (int32_t)b, topk, c->d_out.as<uint64_t>(), c->stream, b == 0)) != PF_OK) return rc;
-    }
-    if ((rc = S.keys(nq, topk, true, ou, os, oc)) != PF_OK) return rc;
-    return S.finish();
-}
-
-// pf_recommend_interest's all-candidates scan of up to 64 results per query, by uid
-static int recommend_uids(pf_ctx* c, SyncScan& S, const int32_t* q, int32_t nq, int32_t topk, int32_t* ou, float* os, int32_t* oc) {
-    std::vector<int32_t> idx, rows;
-    for (int i = 0; i < nq; ++i) {
-        int32_t x = c->hc.idx_of(q[i]);
-        if (x >= 0) { idx.push_back(x); rows.push_back(i); }
-    }
-    int rc = S.begin(nq, (size_t)nq, topk, (int)idx.size() < nq);  // rows of unknown users stay empty
-    if (rc != PF_OK) return rc;
-    const int chunk = 256;
-    for (size_t b = 0; b < idx.size(); b += chunk) {
-        std::vector<int32_t> ii(idx.begin() + b, idx.begin() + std::min(idx.size(), b + chunk));
-        std::vector<int32_t> rr(rows.begin() + b, rows.begin() + std::min(rows.size(), b + chunk));
-        if ((rc = scan_all(c, S.call, ii, rr, topk, c->d_out.as<uint64_t>(), c->stream, b == 0)) != PF_OK) return rc;
-    }
-    if ((rc = S.keys(nq, topk, !idx.empty(), ou, os, oc)) != PF_OK) return rc;
-    return S.finish();
+    return pf::run_pair_terms(c, tg.qidx, tg.slots, tg.dest, head, terms, c->sel);
 }
 
 static int profile_args(pf_ctx* c, const pf_query_profile* q, int32_t nq, int32_t topk, int32_t* ou, float* os, int32_t* oc) {
@@ -1426,22 +456,11 @@ int pf_recommend_interest_profile(pf_ctx* c, const pf_query_profile* q, int32_t 
     if (rc != PF_OK || nq == 0) return rc;
     (void)hipSetDevice(c->device);
     std::vector<pf::ProfileOwned> ps;
-    if ((rc = resolve_profiles(c, q, nq, ps)) != PF_OK) return rc;
+    if ((rc = pf::resolve_profiles(c, q, nq, ps)) != PF_OK) return rc;
     for (int i = 0; i < nq; ++i) oc[i] = 0;
     if (topk == 0) return PF_OK;
-    SyncScan S(c);
-    return recommend_profiles(c, S, ps, topk, ou, os, oc);
-}
-
-// the slots of the stored B side of a profile's pairs (one group: the profile); unknown uids are left out
-static void profile_pair_slots(const pf_ctx* c, const int32_t* b, int64_t n, std::vector<int32_t>& slots,
-                               std::vector<int64_t>& dest) {
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t ib = c->hc.idx_of(b[i]);
-        if (ib < 0) continue;
-        slots.push_back(c->hs.slot_of_idx[ib]);
-        dest.push_back(i);
-    }
+    pf::SyncScan S(c);
+    return pf::recommend_profiles(c, S, ps, topk, ou, os, oc);
 }
 
 int pf_fas_profile_pairs(pf_ctx* c, const pf_query_profile* a, const int32_t* b, int64_t n, const pf_field_select* s,
@@ -1449,19 +468,12 @@ int pf_fas_profile_pairs(pf_ctx* c, const pf_query_profile* a, const int32_t* b,
     if (!c) return PF_EINVAL;
     if (n < 0 || !a || (n && (!b || !out))) return c->fail(PF_EINVAL, "profile pairs: null argument");
     pf::FieldSel d;
-    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "profile pairs: unknown bits in fixed / flags");
+    if (pf::make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "profile pairs: unknown bits in fixed / flags");
     (void)hipSetDevice(c->device);
     std::vector<pf::ProfileOwned> ps;
-    int rc = resolve_profiles(c, a, 1, ps);
+    int rc = pf::resolve_profiles(c, a, 1, ps);
     if (rc != PF_OK) return rc;
-    std::vector<std::vector<int32_t>> slots(1);
-    std::vector<int64_t> dest;
-    profile_pair_slots(c, b, n, slots[0], dest);
-    for (int64_t i = 0; i < n; ++i) out[i] = NAN;
-    std::vector<std::vector<float>> res;
-    if ((rc = run_pairs(c, {0}, slots, res, nullptr, nullptr, d, &ps[0].v)) != PF_OK) return rc;
-    for (size_t j = 0; j < dest.size(); ++j) out[dest[j]] = res[0][j];
-    return PF_OK;
+    return scored_pairs(c, nullptr, b, n, out, d, &ps[0].v);
 }
 
 int pf_fas_profile_pairs_terms(pf_ctx* c, const pf_query_profile* a, const int32_t* b, int64_t n, const pf_field_select* s,
@@ -1469,20 +481,16 @@ int pf_fas_profile_pairs_terms(pf_ctx* c, const pf_query_profile* a, const int32
     if (!c) return PF_EINVAL;
     if (n < 0 || !a || (n && (!b || !head || !terms))) return c->fail(PF_EINVAL, "profile pairs terms: null argument");
     pf::FieldSel d;
-    if (make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "profile pairs terms: unknown bits in fixed / flags");
+    if (pf::make_select(c, s, d) != PF_OK) return c->fail(PF_EINVAL, "profile pairs terms: unknown bits in fixed / flags");
     (void)hipSetDevice(c->device);
     std::vector<pf::ProfileOwned> ps;
-    const int rc = resolve_profiles(c, a, 1, ps);
+    const int rc = pf::resolve_profiles(c, a, 1, ps);
     if (rc != PF_OK) return rc;
     const size_t W = (size_t)(PF_NUM_FIXED + c->hc.T);
-    std::vector<std::vector<int32_t>> slots(1);
-    std::vector<std::vector<int64_t>> dest(1);
-    profile_pair_slots(c, b, n, slots[0], dest[0]);
-    for (int64_t i = 0; i < n; ++i) {  // an unknown uid keeps this: NaN, nothing present, the row all 0.0
-        head[i] = pf_pair_terms_head{NAN, 0u, 0ull};
-        std::fill(terms + (size_t)i * W, terms + (size_t)(i + 1) * W, 0.0);
-    }
-    return run_pair_terms(c, {0}, slots, dest, head, terms, d, &ps[0].v);
+    pf::PairGroups pg;  // one group: the profile
+    pf::group_pairs(c, nullptr, b, 0, n, pg);
+    blank_terms(head, terms, n, W);  // an unknown uid keeps this
+    return pf::run_pair_terms(c, pg.qidx, pg.slots, pg.dest, head, terms, d, &ps[0].v);
 }
 
 int pf_recommend_interest_profile_terms(pf_ctx* c, const pf_query_profile* q, int32_t nq, int32_t topk, int32_t* ou,
@@ -1492,23 +500,21 @@ int pf_recommend_interest_profile_terms(pf_ctx* c, const pf_query_profile* q, in
     if (topk && (!head || !terms)) return c->fail(PF_EINVAL, "query profile: null argument with nq > 0");
     (void)hipSetDevice(c->device);
     std::vector<pf::ProfileOwned> ps;
-    if ((rc = resolve_profiles(c, q, nq, ps)) != PF_OK) return rc;
+    if ((rc = pf::resolve_profiles(c, q, nq, ps)) != PF_OK) return rc;
     for (int i = 0; i < nq; ++i) oc[i] = 0;
     if (topk == 0) return PF_OK;
-    SyncScan S(c);
-    if ((rc = recommend_profiles(c, S, ps, topk, ou, os, oc)) != PF_OK) return rc;
+    pf::SyncScan S(c);
+    if ((rc = pf::recommend_profiles(c, S, ps, topk, ou, os, oc)) != PF_OK) return rc;
     // the (profile, winner) pairs, profile by profile: each has an image of its own
     for (int32_t i = 0; i < nq; ++i) {
         if (oc[i] <= 0) continue;
-        std::vector<std::vector<int32_t>> slots(1);
-        std::vector<std::vector<int64_t>> dest(1);
+        pf::PairGroups pg;
         for (int32_t j = 0; j < oc[i]; ++j) {
             const int32_t ib = c->hc.idx_of(ou[(size_t)i * topk + j]);
             if (ib < 0) return c->fail(PF_EINTERNAL, "scan result without a profile");
-            slots[0].push_back(c->hs.slot_of_idx[ib]);
-            dest[0].push_back((int64_t)i * topk + j);
+            pg.add(0, c->hs.slot_of_idx[ib], (int64_t)i * topk + j);
         }
-        if ((rc = run_pair_terms(c, {0}, slots, dest, head, terms, c->sel, &ps[(size_t)i].v)) != PF_OK) return rc;
+        if ((rc = pf::run_pair_terms(c, pg.qidx, pg.slots, pg.dest, head, terms, c->sel, &ps[(size_t)i].v)) != PF_OK) return rc;
     }
     return PF_OK;
 }
@@ -1520,8 +526,8 @@ int pf_recommend_interest(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk,
     for (int i = 0; i < nq; ++i) oc[i] = 0;
     if (topk == 0 || nq == 0) return PF_OK;
     if (mode == PF_MODE_ALL && topk <= pf::kMaxTopK) {
-        SyncScan S(c);
-        return recommend_uids(c, S, q, nq, topk, ou, os, oc);
+        pf::SyncScan S(c);
+        return pf::recommend_uids(c, S, q, nq, topk, ou, os, oc);
     }
     if (mode == PF_MODE_ALL && c->coll_cap > 0)
         return c->fail(PF_EUNSUPP, "scan collect: topk above 64 runs in the job pipeline, which reads no collector");
@@ -1529,16 +535,7 @@ int pf_recommend_interest(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk,
         return c->fail(PF_EUNSUPP, "scan window: topk above 64 runs in the job pipeline, which reads no window "
                                    "(page with the cursor instead)");
     // FoF-limited (reference) mode, or ALL with topk beyond the in-kernel bound
-    std::vector<pf::Job> jobs(nq);
-    for (int i = 0; i < nq; ++i) {
-        jobs[i].kind = pf::kJobInterest;
-        jobs[i].uid = q[i];
-        jobs[i].topk = topk;
-        jobs[i].limit = limit;
-        jobs[i].all_candidates = mode == PF_MODE_ALL;
-        jobs[i].view = plain_view(c);
-    }
-    return emit_jobs(c, jobs, topk, ou, os, oc);
+    return emit_jobs(c, make_jobs(c, pf::kJobInterest, q, nq, topk, limit, mode == PF_MODE_ALL), topk, ou, os, oc);
 }
 
 // recommender_graph.cpp:105-222
@@ -1546,15 +543,7 @@ int pf_recommend_collab(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, i
                         float* os, int32_t* oc) {
     if (!c || nq < 0 || topk < 0 || (nq && (!q || !oc))) return PF_EINVAL;
     (void)hipSetDevice(c->device);
-    std::vector<pf::Job> jobs(nq);
-    for (int i = 0; i < nq; ++i) {
-        jobs[i].kind = pf::kJobCollab;
-        jobs[i].uid = q[i];
-        jobs[i].topk = topk;
-        jobs[i].limit = limit;
-        jobs[i].view = plain_view(c);
-    }
-    return emit_jobs(c, jobs, topk, ou, os, oc);
+    return emit_jobs(c, make_jobs(c, pf::kJobCollab, q, nq, topk, limit, false), topk, ou, os, oc);
 }
 
 // recommender_clubs.cpp:10-73
@@ -1562,15 +551,7 @@ int pf_recommend_clubs(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, in
                        float* os, int32_t* oc) {
     if (!c || nq < 0 || topk < 0 || (nq && (!q || !oc))) return PF_EINVAL;
     (void)hipSetDevice(c->device);
-    std::vector<pf::Job> jobs(nq);
-    for (int i = 0; i < nq; ++i) {
-        jobs[i].kind = pf::kJobClubs;
-        jobs[i].uid = q[i];
-        jobs[i].topk = topk;
-        jobs[i].limit = limit;
-        jobs[i].view = plain_view(c);
-    }
-    return emit_jobs(c, jobs, topk, ou, os, oc);
+    return emit_jobs(c, make_jobs(c, pf::kJobClubs, q, nq, topk, limit, false), topk, ou, os, oc);
 }
 
 // Asynchronous forms: plan + launch now, outputs written by pf_wait (pokec_fas.h)
@@ -1578,15 +559,7 @@ static int job_async(pf_ctx* c, int kind, const int32_t* q, int32_t nq, int32_t 
                      float* os, int32_t* oc, uint64_t* ticket) {
     if (!c || !ticket || nq < 0 || topk < 0 || (nq && (!q || !oc || (topk && (!ou || !os))))) return PF_EINVAL;
     (void)hipSetDevice(c->device);
-    std::vector<pf::Job> jobs(nq);
-    for (int i = 0; i < nq; ++i) {
-        jobs[i].kind = kind;
-        jobs[i].uid = q[i];
-        jobs[i].topk = topk;
-        jobs[i].limit = limit;
-        jobs[i].view = plain_view(c);
-    }
-    return pf::run_jobs_async(c, std::move(jobs), topk, ou, os, oc, ticket);
+    return pf::run_jobs_async(c, make_jobs(c, kind, q, nq, topk, limit, false), topk, ou, os, oc, ticket);
 }
 
 int pf_recommend_interest_async(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, int32_t limit, int32_t* ou,
@@ -1664,9 +637,7 @@ int pf_set_shard(pf_ctx* c, int32_t shard, int32_t nshards) {
         std::vector<uint64_t> wpre(nwb + 1, 0);
         for (int64_t b = 0; b < nwb; ++b) {
             const int64_t i0 = b * bs, i1 = std::min<int64_t>(hc.n, i0 + bs);
-            const int64_t ent = (hc.tok_off[(size_t)i1 * hc.T] - hc.tok_off[(size_t)i0 * hc.T]) +
-                                (hc.club_off[i1] - hc.club_off[i0]) + (hc.friend_off[i1] - hc.friend_off[i0]);
-            wpre[b + 1] = wpre[b] + (uint64_t)(kBlockFixedWords * (i1 - i0) + ent);
+            wpre[b + 1] = wpre[b] + (uint64_t)(kBlockFixedWords * (i1 - i0) + pf::block_range_entries(hc, i0, i1));
         }
         auto wbound = [&](int s) -> int32_t {
             if (s <= 0) return 0;
@@ -1762,21 +733,10 @@ static_assert(PF_WIN_MIN == pf::kWinMin && PF_WIN_AFTER == pf::kWinAfter && PF_W
               "pf_window.h restates the public window bits");
 static_assert(sizeof(pf_scan_window) == 24, "pf_scan_window is 24 B");
 
-// a caller's window as a call's options take it (null or fields == 0: none), or PF_EINVAL with the reason
-static int make_window(pf_ctx* c, const pf_scan_window* w, pf_scan_window& d) {
-    d = pf_scan_window{};
-    if (!w || w->fields == 0u) return PF_OK;
-    if ((w->fields & ~pf::kWinAllFields) || w->flags != 0u) return c->fail(PF_EINVAL, "scan window: unknown bits in fields / flags");
-    if ((w->fields & PF_WIN_MIN) && std::isnan(w->min_score)) return c->fail(PF_EINVAL, "scan window: min_score is NaN");
-    if ((w->fields & PF_WIN_AFTER) && std::isnan(w->after_score)) return c->fail(PF_EINVAL, "scan window: after_score is NaN");
-    d = *w;
-    return PF_OK;
-}
-
 int pf_set_scan_window(pf_ctx* c, const pf_scan_window* w) {
     if (!c) return PF_EINVAL;
     pf_scan_window d;
-    const int rc = make_window(c, w, d);
+    const int rc = pf::make_window(c, w, d);
     if (rc != PF_OK) return rc;
     c->win_pub = d;
     c->win = pf::window_make(d.fields, d.min_score, d.after_score, d.after_uid);
@@ -1792,29 +752,12 @@ int pf_scan_window_totals(pf_ctx* c, int64_t* out, int32_t cap, int32_t* n) {
     return PF_OK;
 }
 
-// The collector's buffer, grown to hold cap keys (it never shrinks): the new buffer first, so a refusal
-// leaves the one in force alone; then the stream's work on the old one ends, then it is freed.
-static int collect_reserve(pf_ctx* c, int64_t cap) {
-    const size_t bytes = (size_t)cap * sizeof(uint64_t);
-    if (bytes <= c->d_coll.cap) return PF_OK;
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return c->fail(PF_ENOMEM, "scan collect: no device memory for the buffer (8 B per key)");
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->d_coll.p) (void)hipFree(c->d_coll.p);
-    c->d_coll.p = p;
-    c->d_coll.cap = bytes;
-    return PF_OK;
-}
-
 int pf_set_scan_collect(pf_ctx* c, int64_t cap) {
     if (!c) return PF_EINVAL;
     if (cap < 0 || cap > (int64_t)INT32_MAX) return c->fail(PF_EINVAL, "scan collect: cap below 0 or above INT32_MAX");
     if (cap > 0) {  // 0: cleared; the buffers stay for the next collector
         (void)hipSetDevice(c->device);
-        const int rc = collect_reserve(c, cap);
+        const int rc = pf::collect_reserve(c, cap);
         if (rc != PF_OK) return rc;
     }
     c->coll_cap = cap;
@@ -1855,7 +798,7 @@ int pf_scan_keys_async(pf_ctx* c, const int32_t* q, int32_t nq, int32_t topk, ui
         HIPCHK(c, hipMemsetAsync(d_keys, 0xFF, (size_t)nq * topk * sizeof(uint64_t), s));
     // the call's options from the sticky state as it stands now
     const pf::ScanCall call = pf::make_scan_call(c->filt, c->sel, c->win_pub, c->hc.uid.data(), c->hc.uid.size(), 0, nullptr, nullptr);
-    return scan_all(c, call, idx, rows, topk, d_keys, s, true);
+    return pf::scan_all(c, call, idx, rows, topk, d_keys, s, true);
 }
 
 int pf_merge_keys_async(pf_ctx* c, const uint64_t* d_parts, int32_t nparts, int32_t nq, int32_t topk, uint64_t* d_out,
@@ -1882,45 +825,7 @@ int pf_scan_prune_stats(pf_ctx* c, int64_t* out, int32_t reset) {
 int pf_scan_bytes(pf_ctx* c, const int32_t* q, int32_t nq, int64_t* out) {
     if (!c || nq < 0 || (nq && (!q || !out))) return PF_EINVAL;
     (void)hipSetDevice(c->device);
-    // K1: one pass over the shard's tiles and headers, whatever the query
-    int64_t k1 = 0;
-    for (int32_t t = c->tile_begin; t < c->tile_end; ++t) k1 += (int64_t)c->hs.tile_steps[t] * pf::kTileSlots * 16;
-    k1 += (int64_t)(c->tile_end - c->tile_begin) * pf::kTileSlots * 48;
-    if (!c->use_post()) {
-        for (int i = 0; i < nq; ++i) out[i] = c->hc.idx_of(q[i]) < 0 ? 0 : k1;
-        return PF_OK;
-    }
-    // K5 serves the queries whose lists fit one workgroup's LDS; the others go to K1 in a launch
-    // of their own (scan_all's routing): the K5 launch holds only the fitting queries
-    std::vector<std::vector<uint8_t>> imgs((size_t)nq);
-    std::vector<int8_t> kind((size_t)nq, 0);  // 0 unknown uid, 1 K5, 2 K1
-    par_jobs((size_t)nq, [&](size_t i) {
-        const int32_t x = c->hc.idx_of(q[i]);
-        if (x < 0) return;
-        std::vector<int32_t> ex;
-        auto it = c->hc.adj.find(q[i]);
-        if (it != c->hc.adj.end()) ex = it->second;
-        ex.push_back(q[i]);
-        pf::build_query_post(c->hc, c->hp, x, ex, imgs[i]);
-        const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[i].data() + sizeof(pf::QConst));
-        kind[i] = post_image_lds(h) <= kK5LdsCap ? 1 : 2;
-    }, 1);
-    int nfit = 0, max_tok = 0, max_lists = 0;
-    for (int i = 0; i < nq; ++i) {
-        if (kind[i] != 1) continue;
-        ++nfit;
-        const pf::QPostHead* h = reinterpret_cast<const pf::QPostHead*>(imgs[i].data() + sizeof(pf::QConst));
-        max_tok = std::max(max_tok, h->n_tok);
-        max_lists = std::max(max_lists, h->n_tok + h->n_club + h->n_friend);
-    }
-    // workgroups that stage a query's image, as scan_post launches the fitting queries
-    const int nwb = c->wb_end - c->wb_begin;
-    const int wgs = nfit == 1 ? one_query_grid(c, pf::post_var_lds(max_tok, max_lists), false, false, false, true)
-                              : (nwb + batch_blocks_per_wg() - 1) / batch_blocks_per_wg();
-    par_jobs((size_t)nq, [&](size_t i) {
-        out[i] = kind[i] == 0 ? 0 : (kind[i] == 2 ? k1 : post_query_bytes(c, imgs[i], wgs));
-    }, 1);
-    return PF_OK;
+    return pf::scan_bytes(c, q, nq, out);
 }
 
 void pf_decode_keys(const uint64_t* keys, int32_t n, int32_t* ou, float* os, int32_t* count) {
@@ -1950,11 +855,8 @@ int pf_layout(const pf_ctx* c, pf_layout_stats* o) {
     if (c->use_post()) {
         const int64_t bs = c->ps.bsize, n = c->hc.n;
         const int64_t i0 = std::min<int64_t>(n, (int64_t)c->wb_begin * bs), i1 = std::min<int64_t>(n, (int64_t)c->wb_end * bs);
-        const auto& hc = c->hc;
         o->shard_cands = i1 - i0;
-        if (i1 > i0)
-            o->shard_entries = (hc.tok_off[(size_t)i1 * hc.T] - hc.tok_off[(size_t)i0 * hc.T]) +
-                               (hc.club_off[i1] - hc.club_off[i0]) + (hc.friend_off[i1] - hc.friend_off[i0]);
+        if (i1 > i0) o->shard_entries = pf::block_range_entries(c->hc, i0, i1);
     } else {
         for (int32_t t = c->tile_begin; t < c->tile_end; ++t) {
             const int64_t s0 = c->hs.tile_slot0[t];
@@ -2009,7 +911,3 @@ int pf_profile_read(pf_ctx* c, double* total_ms, int64_t* launches) {
 }
 
 }  // extern "C"
-
-// ---------------------------------------------------------------- group query (pf_recommend_group ...)
-#include "pf_group_api.h"
-#include "pf_clubs_api.h"

@@ -1,5 +1,6 @@
-// pf_batch.h — engine-internal batched recommenders (pf_api.cpp) for the C ABI entry points
-// and the batched hold-out drivers (pf_dataset.cpp).  Not part of the public ABI.
+// pf_batch.h — engine-internal batched recommenders (the job pipeline, pf_jobs_plan.cpp) for the
+// C ABI entry points (pf_api.cpp) and the batched hold-out drivers (pf_dataset.cpp), and the host
+// stage clocks.  What the scans' and pairs' host code shares is in pf_host.h.  Not part of the public ABI.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -53,7 +54,7 @@ struct Job {
 // printed to stderr at exit; profiling only).
 enum HostStage {
     kHpPlan = 0, kHpPrep, kHpImages, kHpPack, kHpGpu, kHpUnpack, kHpStage2, kHpCollab, kHpFinish,
-    kHpScanImage, kHpScanLaunch, kHpScanCalls, kHpScanStageWait, kHpStages  // (the scans' stages: pf_api.cpp scan_all)
+    kHpScanImage, kHpScanLaunch, kHpScanCalls, kHpScanStageWait, kHpStages  // (the scans' stages: pf_scan_host.cpp scan_all)
 };
 struct HostProf {
     bool on = false;

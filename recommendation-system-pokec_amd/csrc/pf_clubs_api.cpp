@@ -1,11 +1,16 @@
-// pf_clubs_api.h — the host part of clubs by interest (pokec_fas.h "Clubs by interest"): the three
+// pf_clubs_api.cpp — the host part of clubs by interest (pokec_fas.h "Clubs by interest"): the three
 // calls run the scan underneath with options of their own (the query's window and cap, the context's
 // filter and selection; SyncScan with nothing stored in the context) and hand the ranked keys it
-// left on the device (d_coll_sorted) to the stage (pf_clubsum.h).
-// Part of pf_api.cpp's translation unit (it uses its synchronous scans and the group call's seed
-// resolution); included at its end, after pf_group_api.h.
-#pragma once
+// left on the device (d_coll_sorted) to the stage (pf_clubsum.h).  The synchronous scans, the window
+// check and the group call's seed resolution: pf_host.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
 #include "pf_clubsum.h"
+#include "pf_debug.h"
+#include "pf_host.h"
 
 namespace {
 
@@ -48,10 +53,10 @@ int clubs_run(pf_ctx* c, const pf_clubs_query* q, int32_t topk, const std::vecto
         given = *q->window;
         given.fields &= ~PF_WIN_COUNT;  // the collecting scan counts for itself and stores no totals
     }
-    int rc = make_window(c, &given, w);
+    int rc = pf::make_window(c, &given, w);
     if (rc != PF_OK) return rc;
-    if ((rc = collect_reserve(c, q->cap)) != PF_OK) return rc;
-    SyncScan S(c, w, q->cap);
+    if ((rc = pf::collect_reserve(c, q->cap)) != PF_OK) return rc;
+    pf::SyncScan S(c, w, q->cap);
     if ((rc = scan(S)) != PF_OK) return rc;
     const int64_t total = S.total;
     if (info) info->total = total;
@@ -99,10 +104,10 @@ int pf_recommend_clubs_interest(pf_ctx* c, int32_t uid, const pf_clubs_query* q,
     std::vector<int32_t> own;
     const int32_t idx = c->hc.idx_of(uid);
     if (idx >= 0) own_of_idx(c, idx, own);
-    return clubs_run(c, q, topk, own, [&](SyncScan& S) {
+    return clubs_run(c, q, topk, own, [&](pf::SyncScan& S) {
         int32_t u = 0, n = 0;
         float s = 0.f;
-        return recommend_uids(c, S, &uid, 1, 1, &u, &s, &n);
+        return pf::recommend_uids(c, S, &uid, 1, 1, &u, &s, &n);
     }, oclub, oscore, oc, info);
 }
 
@@ -113,12 +118,12 @@ int pf_recommend_clubs_profile(pf_ctx* c, const pf_query_profile* p, const pf_cl
     if (!p) return c->fail(PF_EINVAL, "clubs by interest: null profile");
     std::vector<int32_t> own;
     if (p->n_clubs > 0 && p->club_ids) own_dense(c, p->club_ids, p->n_clubs, own);
-    return clubs_run(c, q, topk, own, [&](SyncScan& S) {
+    return clubs_run(c, q, topk, own, [&](pf::SyncScan& S) {
         int32_t u = 0, n = 0;
         float s = 0.f;
         std::vector<pf::ProfileOwned> ps;
-        const int prc = resolve_profiles(c, p, 1, ps);
-        return prc != PF_OK ? prc : recommend_profiles(c, S, ps, 1, &u, &s, &n);
+        const int prc = pf::resolve_profiles(c, p, 1, ps);
+        return prc != PF_OK ? prc : pf::recommend_profiles(c, S, ps, 1, &u, &s, &n);
     }, oclub, oscore, oc, info);
 }
 
@@ -127,13 +132,13 @@ int pf_recommend_clubs_group(pf_ctx* c, const pf_group_query* g, const pf_clubs_
     int rc = clubs_args(c, q, topk, oclub, oscore, oc);
     if (rc != PF_OK) return rc;
     if (!g) return c->fail(PF_EINVAL, "clubs by interest: null group");
-    if ((rc = group_args(c, g)) != PF_OK) return rc;
+    if ((rc = pf::group_args(c, g)) != PF_OK) return rc;
     std::vector<int32_t> own;
-    for (int32_t idx : group_seeds(c, *g)) own_of_idx(c, idx, own);
-    return clubs_run(c, q, topk, own, [&](SyncScan& S) {
+    for (int32_t idx : pf::group_seeds(c, *g)) own_of_idx(c, idx, own);
+    return clubs_run(c, q, topk, own, [&](pf::SyncScan& S) {
         int32_t u = 0, n = 0;
         float s = 0.f;
-        return recommend_groups(c, S, g, 1, 1, &u, &s, &n);
+        return pf::recommend_groups(c, S, g, 1, 1, &u, &s, &n);
     }, oclub, oscore, oc, info);
 }
 

@@ -1,5 +1,5 @@
-// pf_ctx.h — the engine context behind the C ABI (pf_api.cpp) and the device job pipeline
-// (pf_jobs.cpp): device buffers, host corpus and stores, workspaces.  Engine-internal.
+// pf_ctx.h — the engine context behind the C ABI (pf_api.cpp), the host side of the scans and
+// pairs (pf_host.h) and the device job pipeline (pf_jobs.cpp): device buffers, host corpus and stores, workspaces.  Engine-internal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -285,12 +285,12 @@ struct pf_ctx {
     // three by default (PF_DEBUG scan_lanes=N: 0 / 1 off, 2 without the aux2 stream); lanes past the
     // third run on streams of their own (lane_st, created at open when scan_lanes asks for them):
     // with the process's default four hardware queues they would share them (an A/B for processes
-    // that raise GPU_MAX_HW_QUEUES; pf_api.cpp scan_lanes)
+    // that raise GPU_MAX_HW_QUEUES; pf_scan_host.cpp scan_lanes)
     static constexpr int kMaxLanes = 16;
     ScanLane lane[kMaxLanes];
     hipStream_t lane_st[kMaxLanes] = {};
     int lane_cur = 0;
-    // Resident postings-scan images (pf_api.cpp build_resident_post): every user's K5 image part
+    // Resident postings-scan images (pf_scan_host.cpp build_resident_post): every user's K5 image part
     // after its QConst (QPostHead | tokens | columns | set lists | exclusions = adj_list row + self),
     // built once at open; a one-query scan launches from it with the QConst of the user's resident
     // K1' image (jb.d_pimg), so the call builds and uploads nothing.  A user whose adj_list row

@@ -1,9 +1,18 @@
-// pf_group_api.h — the host part of the group query (pokec_fas.h "Group query"): seed resolution, the
+// pf_group_api.cpp — the host part of the group query (pokec_fas.h "Group query"): seed resolution, the
 // exclusion union, the pass plan and the launches of fas_group_kernel (pf_group.h), and
-// pf_group_scores through the pair kernel.  Part of pf_api.cpp's translation unit (it uses its image
-// staging and its pair runner); included at its end.
-#pragma once
+// pf_group_scores through the pair kernel (image staging and the pair runner: pf_host.h).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <unordered_set>
+#include <vector>
+
+#include "pf_debug.h"
 #include "pf_group.h"
+#include "pf_host.h"
+
+namespace pf {
 
 namespace {
 
@@ -32,6 +41,8 @@ float group_aggregate(int agg, const float* s, size_t G, size_t stride) {
     return m;
 }
 
+}  // namespace
+
 int group_args(pf_ctx* c, const pf_group_query* g) {
     if (g->n_seeds < 0 || g->n_exclude < 0) return c->fail(PF_EINVAL, "group query: negative count");
     if (g->n_seeds > PF_GROUP_MAX_SEEDS) return c->fail(PF_EINVAL, "group query: more than PF_GROUP_MAX_SEEDS seeds");
@@ -53,6 +64,8 @@ std::vector<int32_t> group_seeds(const pf_ctx* c, const pf_group_query& g) {
     }
     return idx;
 }
+
+namespace {
 
 // What one group launches: the images (the last one carries the exclusion union), their carve
 // offsets and the passes.
@@ -98,33 +111,17 @@ int group_plan(pf_ctx* c, const pf_group_query& g, GroupPlan& P) {
     return PF_OK;
 }
 
-// bytes one pass reads: the shard's record stream and headers (pf_scan_bytes' K1 figure)
-int64_t group_pass_bytes(const pf_ctx* c) {
-    int64_t b = 0;
-    for (int32_t t = c->tile_begin; t < c->tile_end; ++t) b += (int64_t)c->hs.tile_steps[t] * pf::kTileSlots * 16;
-    return b + (int64_t)(c->tile_end - c->tile_begin) * pf::kTileSlots * 48;
-}
-
 // One group's passes on the context's stream, its k keys into d_keys, with x the call's options for
 // this group (its own count word).  One pinned staging buffer [refs | offsets | sync | image pool] goes
 // up in a single copy, as in scan_stream_images.
 int group_scan(pf_ctx* c, const pf::ScanExtras& x, const GroupPlan& P, int agg, int k, uint64_t* d_keys, bool timed) {
     const size_t G = P.idx.size();
     const int tiles = c->tile_end - c->tile_begin;
-    const size_t refs_b = (G * sizeof(pf::QImageRef) + 15) & ~(size_t)15;
-    const size_t offs_b = (G * sizeof(uint32_t) + 15) & ~(size_t)15;
-    const size_t sync_b = sizeof(pf::ScanSync);
-    const size_t total = refs_b + offs_b + sync_b + P.im.pool.size();
-    uint8_t* h = c->stage_acquire(total);
-    if (!h) return c->fail(PF_ENOMEM, "pinned staging allocation failed");
-    std::memcpy(h, P.im.refs.data(), G * sizeof(pf::QImageRef));
-    std::memcpy(h + refs_b, P.off.data(), G * sizeof(uint32_t));
-    std::memset(h + refs_b + offs_b, 0, sync_b);
-    std::memcpy(h + refs_b + offs_b + sync_b, P.im.pool.data(), P.im.pool.size());
-    HIPCHK(c, c->d_pool.ensure(total));
-    HIPCHK(c, hipMemcpyAsync(c->d_pool.p, h, total, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, c->stage_release(c->stream));
-    uint8_t* base = c->d_pool.as<uint8_t>();
+    const StageLayout<4> L = stage_group_layout(G, sizeof(pf::QImageRef), sizeof(pf::ScanSync), P.im.pool.size());
+    const StagePiece pool{P.im.pool.data(), P.im.pool.size()};
+    uint8_t* base = nullptr;
+    int rc = stage_send(c, L, {P.im.refs.data(), P.off.data(), nullptr}, &pool, 1, c->d_pool, c->stream, base);
+    if (rc != PF_OK) return rc;
     if (P.passes.size() > 1) HIPCHK(c, c->d_scores.ensure((size_t)std::max(1, c->ds.n_slots) * sizeof(double)));
     std::vector<int> blocks(P.passes.size());
     for (size_t p = 0; p < P.passes.size(); ++p) {
@@ -133,26 +130,21 @@ int group_scan(pf_ctx* c, const pf::ScanExtras& x, const GroupPlan& P, int agg, 
     }
     HIPCHK(c, c->d_part.ensure((size_t)(blocks.back() + 8) * k * sizeof(uint64_t)));
     hipEvent_t e0, e1;
-    const int rc = scan_events(c, timed, e0, e1);
-    if (rc != PF_OK) return rc;
-    if (timed) HIPCHK(c, hipEventRecord(e0, c->stream));
+    if ((rc = timed_begin(c, timed, e0, e1, c->stream)) != PF_OK) return rc;
     for (size_t p = 0; p < P.passes.size(); ++p)
-        HIPCHK(c, pf::launch_group({.st = c->ds, .pool = base + refs_b + offs_b + sync_b,
+        HIPCHK(c, pf::launch_group({.st = c->ds, .pool = base + L.off[3],
                                     .refs_dev = reinterpret_cast<const pf::QImageRef*>(base),
-                                    .off_dev = reinterpret_cast<const uint32_t*>(base + refs_b), .pass = P.passes[p],
+                                    .off_dev = reinterpret_cast<const uint32_t*>(base + L.off[1]), .pass = P.passes[p],
                                     .hit_bytes = P.hit_bytes, .first = p == 0, .last = p + 1 == P.passes.size(),
                                     .agg = agg, .n_seeds = (int)G, .excl_img = (int)G - 1, .tile_begin = c->tile_begin,
                                     .tile_end = c->tile_end, .k = k, .blocks = blocks[p], .acc = c->d_scores.as<double>(),
                                     .parts = c->d_part.as<uint64_t>(), .out = d_keys,
-                                    .sync = reinterpret_cast<pf::ScanSync*>(base + refs_b + offs_b), .s = c->stream,
+                                    .sync = reinterpret_cast<pf::ScanSync*>(base + L.off[2]), .s = c->stream,
                                     .x = x}));
-    if (timed) {
-        HIPCHK(c, hipEventRecord(e1, c->stream));
-        c->last_ev0 = e0;
-        c->last_ev1 = e1;
-    }
-    return PF_OK;
+    return timed_end(c, timed, e0, e1, c->stream);
 }
+
+}  // namespace
 
 // pf_recommend_group's scans: group i's keys through row 0 of d_out, its count in word i (0 for G = 0);
 // last_scan_ms is the last scanned group's
@@ -170,7 +162,7 @@ int recommend_groups(pf_ctx* c, SyncScan& S, const pf_group_query* g, int32_t ng
     return S.finish();
 }
 
-}  // namespace
+}  // namespace pf
 
 extern "C" {
 
@@ -179,26 +171,26 @@ int pf_recommend_group(pf_ctx* c, const pf_group_query* g, int32_t ng, int32_t t
     if (ng < 0 || topk < 0) return c->fail(PF_EINVAL, "group query: negative ng / topk");
     if (ng && (!g || !oc || (topk && (!ou || !os)))) return c->fail(PF_EINVAL, "group query: null argument with ng > 0");
     for (int32_t i = 0; i < ng; ++i) {
-        const int rc = group_args(c, &g[i]);
+        const int rc = pf::group_args(c, &g[i]);
         if (rc != PF_OK) return rc;
     }
     if (topk > pf::kMaxTopK) return c->fail(PF_EUNSUPP, "group query: topk above the scan kernels' bound (64)");
     (void)hipSetDevice(c->device);
     for (int32_t i = 0; i < ng; ++i) oc[i] = 0;
     if (topk == 0) return PF_OK;
-    SyncScan S(c);
-    return recommend_groups(c, S, g, ng, topk, ou, os, oc);
+    pf::SyncScan S(c);
+    return pf::recommend_groups(c, S, g, ng, topk, ou, os, oc);
 }
 
 int pf_group_scores(pf_ctx* c, const pf_group_query* g, const int32_t* b, int64_t n, const pf_field_select* s, float* out) {
     if (!c) return PF_EINVAL;
     if (!g || n < 0 || (n && (!b || !out))) return c->fail(PF_EINVAL, "group scores: null argument");
-    int rc = group_args(c, g);
+    int rc = pf::group_args(c, g);
     if (rc != PF_OK) return rc;
     pf::FieldSel sel;
-    if (make_select(c, s, sel) != PF_OK) return c->fail(PF_EINVAL, "group scores: unknown bits in fixed / flags");
+    if (pf::make_select(c, s, sel) != PF_OK) return c->fail(PF_EINVAL, "group scores: unknown bits in fixed / flags");
     (void)hipSetDevice(c->device);
-    const std::vector<int32_t> idx = group_seeds(c, *g);
+    const std::vector<int32_t> idx = pf::group_seeds(c, *g);
     const size_t G = idx.size();
     for (int64_t i = 0; i < n; ++i) out[i] = NAN;
     if (G == 0 || n == 0) return PF_OK;
@@ -206,22 +198,18 @@ int pf_group_scores(pf_ctx* c, const pf_group_query* g, const int32_t* b, int64_
     const int64_t chunk = std::max<int64_t>(1, ((int64_t)4 << 20) / (int64_t)G);
     for (int64_t b0 = 0; b0 < n; b0 += chunk) {
         const int64_t b1 = std::min(n, b0 + chunk);
-        std::vector<int32_t> slots;
-        std::vector<int64_t> where;
-        for (int64_t i = b0; i < b1; ++i) {
-            const int32_t x = c->hc.idx_of(b[i]);
-            if (x < 0) continue;
-            slots.push_back(c->hs.slot_of_idx[x]);
-            where.push_back(i);
-        }
-        if (slots.empty()) continue;
+        pf::PairGroups pg;  // one group: the candidates every seed shares
+        pf::group_pairs(c, nullptr, b, b0, b1, pg);
+        if (pg.slots.empty()) continue;
+        const std::vector<int32_t>& slots = pg.slots[0];
+        const std::vector<int64_t>& where = pg.dest[0];
         const std::vector<std::vector<int32_t>> gs(G, slots);
         std::vector<std::vector<float>> res;
-        if ((rc = run_pairs(c, idx, gs, res, nullptr, nullptr, sel)) != PF_OK) return rc;
+        if ((rc = pf::run_pairs(c, idx, gs, res, nullptr, nullptr, sel)) != PF_OK) return rc;
         std::vector<float> col(G);
         for (size_t j = 0; j < slots.size(); ++j) {
             for (size_t q = 0; q < G; ++q) col[q] = res[q][j];
-            out[where[j]] = group_aggregate(g->agg, col.data(), G, 1);
+            out[where[j]] = pf::group_aggregate(g->agg, col.data(), G, 1);
         }
     }
     return PF_OK;
@@ -230,30 +218,30 @@ int pf_group_scores(pf_ctx* c, const pf_group_query* g, const int32_t* b, int64_
 int pf_group_plan_of(pf_ctx* c, const pf_group_query* g, pf_group_plan* out) {
     if (!c) return PF_EINVAL;
     if (!g || !out) return c->fail(PF_EINVAL, "group plan: null argument");
-    int rc = group_args(c, g);
+    int rc = pf::group_args(c, g);
     if (rc != PF_OK) return rc;
-    GroupPlan P;
-    if ((rc = group_plan(c, *g, P)) != PF_OK) return rc;
+    pf::GroupPlan P;
+    if ((rc = pf::group_plan(c, *g, P)) != PF_OK) return rc;
     out->n_seeds = (int32_t)P.idx.size();
     out->n_passes = (int32_t)P.passes.size();
     out->n_global = P.n_global;
     out->pad = 0;
-    out->stream_bytes = (int64_t)P.passes.size() * group_pass_bytes(c);
+    out->stream_bytes = (int64_t)P.passes.size() * pf::k1_pass_bytes(c);
     return PF_OK;
 }
 
 int pf_group_image_lds(pf_ctx* c, const pf_group_query* g, int32_t* out, int32_t cap) {
     if (!c) return PF_EINVAL;
     if (!g || !out) return c->fail(PF_EINVAL, "group image lds: null argument");
-    int rc = group_args(c, g);
+    int rc = pf::group_args(c, g);
     if (rc != PF_OK) return rc;
-    GroupPlan P;
-    if ((rc = group_plan(c, *g, P)) != PF_OK) return rc;
+    pf::GroupPlan P;
+    if ((rc = pf::group_plan(c, *g, P)) != PF_OK) return rc;
     const size_t G = P.idx.size();
     if ((size_t)cap < G + 2) return c->fail(PF_EINVAL, "group image lds: out too small");
     for (size_t i = 0; i < G; ++i) out[i] = (int32_t)P.img_lds[i];
     out[G] = (int32_t)(P.hit_bytes * (uint32_t)pf::kScanThreads + pf::kGroupTailLds);
-    out[G + 1] = (int32_t)group_budget();
+    out[G + 1] = (int32_t)pf::group_budget();
     return PF_OK;
 }
 

@@ -9,7 +9,7 @@
 
 namespace pf {
 
-// One query image K6 builds (layout of pf_api.cpp plan_images): byte offsets into the image
+// One query image K6 builds (layout of pf_scan_host.cpp image_ref): byte offsets into the image
 // pool; lg = table log2 (load <= 0.4), lge = exclusion table log2, dlg = log2 of the set
 // de-duplication table in scratch (u32 words from scr_off; the item list follows it; img_dlg).
 struct ImgJob {

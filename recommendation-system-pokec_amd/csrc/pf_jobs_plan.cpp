@@ -27,7 +27,7 @@ constexpr int kDevTopK = kMaxTopK;           // K8 keeps up to 64 keys per job
 constexpr int64_t kChunkElems = 192ll << 20; // element workspace per chunk (x 12 B)
 constexpr int64_t kChunkHt = 128ll << 20;    // gather hash tables per chunk (int32 words)
 constexpr size_t kPipeJobs = 1024;           // calls of this many jobs or more run as pipelined chunks
-constexpr uint32_t kStageLimitJobs = 48 * 1024;  // as pf_api.cpp kStageLimit (LDS-staged tables)
+constexpr uint32_t kStageLimitJobs = 48 * 1024;  // as pf_scan_host.cpp kStageLimit (LDS-staged tables)
 
 int32_t node_of(const pf_ctx* c, int32_t uid) {
     const auto& dn = c->jb.dense_node;  // uids of a dense range: one load (built at open)

@@ -52,7 +52,7 @@ int scan_blocks_per_cu(bool packed, bool gtab, uint32_t lds);
 // offsets img_off[] into pool); var_lds = post_var_lds(max n_tok, max lists of an image)
 uint32_t post_var_lds(int n_tok, int n_lists);
 uint32_t post_lds(uint32_t var_lds);
-// mode flags (pf_api.cpp post_mode).  Claimed launches and batches alike: kPostPrune = drop candidates
+// mode flags (pf_scan_host.cpp post_mode).  Claimed launches and batches alike: kPostPrune = drop candidates
 // below the query's shared score threshold (pf_prune.h; a batch query's is its own sync[q]),
 // kPostPruneBlockOnly = at block starts only, kPostPruneStats = count them.  kPostFiltKeepBlocks (filtered launches, A/B): a block in which no
 // candidate passes the filter runs to its end instead of leaving after its first barrier.

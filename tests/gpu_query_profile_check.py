@@ -7,6 +7,8 @@ picks the check:
   absent                            Y and Z, whom E does not hold, against the oracle opened on
                                     C+ = E + {Y, Z}; the breakdown; one batch = its single calls; shards
   state                             nothing sticks to the context; the error codes
+  heavy                             one call of ordinary profiles and one too large for the postings scan
+                                    (a clone of the hub corpus's uid 4242) equals the by-uid call
 Cases and corpora: tests/query_profile_cases.py.  Exits non-zero on any mismatch."""
 import ctypes
 import sys
@@ -303,10 +305,32 @@ def check_state():
         eng.close()
 
 
+def check_heavy():
+    """The hub corpus of test_gpu_parity.py: 20,000 users, uid 4242 naming 22,000 friend ids (about 20k
+    set lists, beyond one workgroup's 160 KB).  One recommend_profile call of clones of
+    [4242, 3, 15000, 4242, 777] under the auto kernel sends the heavy ones to K1 and the others to K5;
+    ids and float32 bits are the by-uid call's (pinned to the oracle by test_heavy_query_routes_to_stream_scan)."""
+    base = tl.synth.Corpus(n_users=20000, seed=77, edge_cases=1)
+    c = tl.with_rows(tl.corpus_from_desc(base.desc_ptr()), user=4242, friends=np.arange(1, 22001, dtype=np.uint32))
+    eng = tl.engine(c)
+    try:
+        q = [4242, 3, 15000, 4242, 777]
+        if eng.layout().scan_kernel != pf.PF_SCAN_POSTINGS:
+            return fail("the auto kernel is not the postings scan")
+        want = eng.recommend_interest_all(q, 10)
+        got = eng.recommend_profile([qc.clone_profile(pf, c, u) for u in q], 10)
+        for u, g, w in zip(q, got, want):
+            if len(w[0]) != 10 or not same_list(g, w):
+                return fail("heavy batch", u, list(g[0]), list(w[0]))
+        return 0
+    finally:
+        eng.close()
+
+
 def main():
     mode = sys.argv[1]
     rc = {"clone_profiles": lambda: check_clone(False), "clone_explicit": lambda: check_clone(True),
-          "absent": check_absent, "state": check_state}[mode]()
+          "absent": check_absent, "state": check_state, "heavy": check_heavy}[mode]()
     if rc:
         return 1
     print("ok")

@@ -9,8 +9,8 @@ intersection), the items of a wave share a queue of kQueue = 384 entries, lanes 
 second round, a wave whose second round overflows too falls back to the per-lane epilogue, and a lane
 whose hit list reached kHitCap is re-walked by the whole wave.  The public call fixes which 64 pairs
 share a wave: pf_fas_pairs groups the pairs by query in order of first appearance, keeps each group's
-pairs in the caller's order and cuts a group into blocks of kPairThreads = 512 (csrc/pf_api.cpp
-fas_pairs, pair_chunks), so pair j of a group is lane j % 512 of block j // 512, wave (j % 512) // 64.
+pairs in the caller's order and cuts a group into blocks of kPairThreads = 512 (csrc/pf_pair_groups.h
+PairGroups, csrc/pf_pairs_host.cpp pair_chunks), so pair j of a group is lane j % 512 of block j // 512, wave (j % 512) // 64.
 
 Users (uid = UID0 + position; no adjacency, so an all-candidates call ranks everyone but the query):
   Q    one token in each of the T = 22 columns, 70 more in column COL_LONG, three clubs, four friends
@@ -42,7 +42,7 @@ WAVE = 64                          # csrc/pf_types.h:11 kWave
 QUEUE = HIT_SLOTS * WAVE // 4      # csrc/pf_kernels.hip:517 kQueue = kHitSlots * 64 / 4
 PAIR_THREADS = 512                 # csrc/pf_kernels.h kPairThreads: pairs of a block
 MAX_DENSE_ITEMS = HIT_CAP - 1 + 2  # a list of kHitCap hits already reads as overflowed (pf_kernels.hip:717-718)
-STAGE_LIMIT = 48 * 1024            # csrc/pf_api.cpp:57 kStageLimit, csrc/pf_jobs_plan.cpp:30 kStageLimitJobs
+STAGE_LIMIT = 48 * 1024            # csrc/pf_scan_host.cpp kStageLimit, csrc/pf_jobs_plan.cpp:30 kStageLimitJobs
 assert T >= HIT_CAP + 2 and QUEUE == 384 and MAX_DENSE_ITEMS == 21
 
 UID0 = 100
@@ -300,7 +300,7 @@ def classify(items, overflow=None, inactive=None):
 
 
 def waves_of(pairs):
-    """The waves pf_fas_pairs makes of pairs = [(query key, b key)] (csrc/pf_api.cpp fas_pairs: groups
+    """The waves pf_fas_pairs makes of pairs = [(query key, b key)] (csrc/pf_pair_groups.h PairGroups: groups
     by query in order of first appearance, each group's pairs in the caller's order; pair_chunks: a
     group cut into blocks of kPairThreads; the kernel: lane i of a block scores its pair i): a list
     of (query key, [b key per active lane]) with 1 .. 64 lanes each, in block order."""

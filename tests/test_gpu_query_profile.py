@@ -45,6 +45,13 @@ def test_nothing_sticks_and_errors():
     run("state")
 
 
+def test_heavy_profile_in_a_batch_routes_to_stream_scan():
+    """A by-value profile too large for K5 (a clone of the hub corpus's uid 4242, 22,000 friend ids) in
+    one call with ordinary profiles: the heavy ones go to K1, the others stay on K5, and every list
+    has the ids and score bits of the by-uid call of the same users."""
+    run("heavy")
+
+
 def test_cpp_facade_by_profile(tmp_path):
     """include/pokec/recommender.h: recommend_by_profile of a copy of a map profile gives
     recommend_interest_all's list; profile_similarity_adhoc / _terms_adhoc the bits of

@@ -1,5 +1,5 @@
 """A scan call's options travel by value (csrc/pf_scan_call.h) and the synchronous calls share one
-helper (pf_api.cpp SyncScan): counted calls of more than one 256-query chunk, by uid and by value, under
+helper (pf_scan_host.cpp SyncScan): counted calls of more than one 256-query chunk, by uid and by value, under
 K1 and K5, and one engine serving calls of every kind in turn, each with other options than the one
 before (tests/gpu_scan_call_check.py, a fresh process each).  On the edge corpus E, against the
 oracle's ranking cut in numpy: ids, float32 bits, totals and the stored results equal."""

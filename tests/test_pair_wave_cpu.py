@@ -57,8 +57,8 @@ def test_queries(C):
     gc, gf, gt = pw.record(C, pw.uid_of("QG"))
     qc_, qf, _ = pw.record(C, pw.uid_of("Q"))
     assert (gc, gf) == (qc_, qf) and all(set(qt[t]) <= set(gt[t]) for t in range(pw.T)), "QG holds all of Q"
-    # QG's table is probed in global memory: keys + values above the staging limit (csrc/pf_api.cpp:57, :82-84,
-    # :104-106; csrc/pf_jobs_plan.cpp:760-761), the table sized as csrc/pf_store.cpp:455-459 lg_for (load <= 0.4)
+    # QG's table is probed in global memory: keys + values above the staging limit (csrc/pf_scan_host.cpp kStageLimit,
+    # image_ref's lds_bytes; csrc/pf_jobs_plan.cpp:760-761), the table sized as csrc/pf_store.cpp:455-459 lg_for (load <= 0.4)
     n = len(gc) + len(gf) + sum(len(m) for m in gt)
     lg = 4
     while (1 << lg) * 2 < n * 5:
