@@ -503,6 +503,72 @@ public:
         });
     }
 
+    // Diverse top-k (pokec_fas.h "Diverse top-k"): a ranking re-ranked by maximal marginal relevance.  Each
+    // pick maximises lambda * score - (1 - lambda) * (its highest FAS with anything picked before); ties go to
+    // the earlier entry.  diversify re-ranks a list the caller holds (unknown ids are dropped, of a repeated
+    // id the first entry counts, at most PF_DIVERSE_MAX_POOL entries).  The recommend_diverse_* calls take
+    // the first `pool` candidates of `window` in the all-candidates ranking as the pool; a window that holds
+    // more than cap candidates throws std::length_error like clubs by interest; any other failure returns
+    // an empty list and last_error says why.  info (optional) receives the call's pf_diverse_info.  The
+    // pairs keep their relevance: (id, score) in pick order.
+    Ranked diversify(const Ranked& list, int topk, float lambda) const {
+        Ranked out;
+        if (!profiles || topk <= 0 || list.empty()) return out;
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return out;
+        std::lock_guard<std::mutex> g(e->mu);
+        std::vector<int32_t> u, ids((size_t)std::min<size_t>((size_t)topk, list.size()));
+        std::vector<float> s, sc(ids.size());
+        for (const auto& p : list) {
+            u.push_back(p.first);
+            s.push_back(p.second);
+        }
+        int32_t n = 0;
+        if (pf_diverse_rerank(e->ctx, u.data(), s.data(), (int64_t)u.size(), lambda, (int32_t)ids.size(), nullptr, ids.data(), sc.data(),
+                              nullptr, nullptr, &n) != PF_OK)
+            return fail_(e->ctx, out);
+        for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
+        return out;
+    }
+    Ranked recommend_diverse_by_interest(int user, int topk, float lambda = 0.7f, int pool = 200, const ScoreWindow& window = ScoreWindow(),
+                                         int64_t cap = 1 << 20, pf_diverse_info* info = nullptr) const {
+        return diverse_(topk, lambda, pool, window, cap, info, [&](detail::Engine& e, const pf_diverse_query* q, int k, int32_t* ou,
+                                                                  float* os, int32_t* n, pf_diverse_info* di) {
+            if (adj_list) {  // the row the scan excludes, as the caller's adj_list holds it now
+                const int rc = sync_row_(e, user);
+                if (rc != PF_OK) return rc;
+            }
+            return pf_recommend_diverse_interest(e.ctx, user, q, k, ou, os, nullptr, nullptr, n, di);
+        });
+    }
+    Ranked recommend_diverse_by_profile(const Profile& A, int topk, float lambda = 0.7f, int pool = 200,
+                                        const ScoreWindow& window = ScoreWindow(), int64_t cap = 1 << 20,
+                                        pf_diverse_info* info = nullptr, const std::vector<int>& exclude = {}) const {
+        return diverse_(topk, lambda, pool, window, cap, info, [&](detail::Engine& e, const pf_diverse_query* q, int k, int32_t* ou,
+                                                                  float* os, int32_t* n, pf_diverse_info* di) {
+            QueryHold h;
+            const pf_query_profile qp = query_of_(e.ctx, A, exclude, h);
+            return pf_recommend_diverse_profile(e.ctx, &qp, q, k, ou, os, nullptr, nullptr, n, di);
+        });
+    }
+    Ranked recommend_diverse_for_group(const std::vector<int>& seeds, int topk, float lambda = 0.7f, int pool = 200,
+                                       const ScoreWindow& window = ScoreWindow(), int64_t cap = 1 << 20, pf_diverse_info* info = nullptr,
+                                       GroupAgg agg = GroupAgg::Mean, bool exclude_adj = false, const std::vector<int>& exclude = {}) const {
+        if (seeds.empty()) return Ranked();
+        return diverse_(topk, lambda, pool, window, cap, info, [&](detail::Engine& e, const pf_diverse_query* q, int k, int32_t* ou,
+                                                                  float* os, int32_t* n, pf_diverse_info* di) {
+            if (exclude_adj && adj_list)
+                for (int s : seeds) {
+                    const int rc = sync_row_(e, s);
+                    if (rc != PF_OK) return rc;
+                }
+            const std::vector<int32_t> sd(seeds.begin(), seeds.end()), ex(exclude.begin(), exclude.end());
+            const pf_group_query g{sd.data(), (int32_t)sd.size(), (int32_t)agg, exclude_adj ? PF_GROUP_EXCLUDE_ADJ : 0u,
+                                   ex.empty() ? nullptr : ex.data(), (int32_t)ex.size()};
+            return pf_recommend_diverse_group(e.ctx, &g, q, k, ou, os, nullptr, nullptr, n, di);
+        });
+    }
+
     // The group's aggregate score of B, a profile of the map (NaN when B or every seed is not): how
     // well B fits the group.  No exclusion applies: a seed is scored like anyone else.
     float group_similarity(const std::vector<int>& seeds, const Profile& B, GroupAgg agg = GroupAgg::Mean) const {
@@ -624,6 +690,33 @@ private:
         if (info) *info = ci;
         if (ci.total > cap)
             throw std::length_error("clubs by interest: the window holds " + std::to_string(ci.total) + " candidates, above the cap of " +
+                                    std::to_string(cap));
+        return out;
+    }
+
+    // the three diverse top-k calls: call(engine, query, topk, out_uid, out_score, out_count, info) -> rc
+    template <class Call>
+    Ranked diverse_(int topk, float lambda, int pool, const ScoreWindow& window, int64_t cap, pf_diverse_info* info, Call call) const {
+        Ranked out;
+        if (info) *info = pf_diverse_info{0, 0, 0, 0};
+        if (!profiles || topk <= 0) return out;
+        std::shared_ptr<detail::Engine> e = engine_();
+        if (!e) return out;
+        pf_diverse_info di{0, 0, 0, 0};
+        {
+            std::lock_guard<std::mutex> g(e->mu);
+            const pf_scan_window w = window.c_form();
+            const pf_diverse_query q{cap, pool, lambda, w.fields ? &w : nullptr};
+            topk = std::min(topk, PF_DIVERSE_MAX_POOL);  // a result never holds more than the pool
+            std::vector<int32_t> ids((size_t)topk);
+            std::vector<float> sc((size_t)topk);
+            int32_t n = 0;
+            if (call(*e, &q, topk, ids.data(), sc.data(), &n, &di) != PF_OK) return fail_(e->ctx, out);
+            for (int i = 0; i < n; ++i) out.emplace_back(ids[i], sc[i]);
+        }
+        if (info) *info = di;
+        if (di.total > cap)
+            throw std::length_error("diverse top-k: the window holds " + std::to_string(di.total) + " candidates, above the cap of " +
                                     std::to_string(cap));
         return out;
     }

@@ -592,6 +592,73 @@ int pf_recommend_clubs_group(pf_ctx* ctx, const pf_group_query* group, const pf_
                              int32_t* out_club, float* out_score, int32_t* out_count, pf_clubs_info* info);
 
 /*
+ * Diverse top-k: a ranked list re-ranked by maximal marginal relevance, so that a first page is not
+ * ten copies of one person.  There is no reference function; this is the definition.
+ *   Pool         M users p_0 .. p_{M-1} in a fixed order, each with a float relevance r_i.  Position
+ *                is part of the contract: it breaks ties.
+ *   Similarity   sim(s, i) is the float pf_fas_pairs_select gives for a = p_s, b = p_i under the
+ *                selection named below: the picked user is on the A side (FAS is symmetric in exact
+ *                arithmetic, not in floats).
+ *   Penalty      pen_i is a float, 0.0f before the first pick; after each pick s,
+ *                pen_i = sim(s, i) > pen_i ? sim(s, i) : pen_i.
+ *   Value        v_i is a double from three separately rounded IEEE operations, never fused:
+ *                a = (double)lambda * (double)r_i (exact); p = (1.0 - (double)lambda) * (double)pen_i
+ *                (the subtraction rounds once, the product once); v_i = a - p (rounds once).
+ *   A pick       Among the unpicked i the largest v_i; ties go to the smallest position.  Repeated
+ *                min(topk, M) times.
+ *   Outputs      Per pick, in pick order: out_uid, out_score = r (untouched), out_pen = the float
+ *                penalty at the moment of the pick (0 for the first), out_value = the double v.
+ *                out_pen and out_value may be NULL.
+ *   lambda       A float in [0, 1].  1: the pool's first topk.  0: position 0, then the users least
+ *                similar to anything picked so far.
+ *   Limits       M <= PF_DIVERSE_MAX_POOL.  Any topk >= 0; topk = 0 scans nothing and reports zeros.
+ * pf_diverse_rerank diversifies a list the caller holds (a FoF result, a collaborative result, a
+ * collected window): the pool is the caller's order; unknown uids are dropped; of a repeated uid the
+ * first occurrence counts; `select` (NULL = none) is the selection of the similarities, and the
+ * context's selection plays no part.  PF_EINVAL: a NULL context or out_count, n < 0, a NULL list with
+ * n > 0, NULL out_uid / out_score with topk > 0, topk < 0, lambda outside [0, 1] or NaN, a NaN or
+ * infinite relevance (an infinity times a zero weight has no value to rank), unknown selection bits.  PF_EUNSUPP: more than PF_DIVERSE_MAX_POOL known, distinct entries.
+ * The three scan calls take the pool from the collecting scan of the query, run as the clubs calls
+ * above run it ("Neighbours", "State"): the candidates inside `window`, passing the context's filter,
+ * ranked (score desc, uid asc) under the context's field selection (a group's score is its
+ * aggregate); the pool is the first min(pool, total) of that ranking, r their scores, and the
+ * similarities are scored under the same selection.  The context's window, collector, stored totals
+ * and pf_scan_collected result come back as they were found.
+ *   info         total = the candidates in the window (exact, whatever cap is); pool = M; pairs = the
+ *                pairs scored for the similarities, M * M (the whole matrix, the diagonal included,
+ *                in one launch; the rows never picked are the price of that); picked = out_count.
+ *                NULL is allowed.
+ *   Overflow     total > cap is no error: out_count = 0, info.total is exact, pool = picked = 0.
+ *   Empty        An unknown uid, a group with G = 0 and an empty window give out_count = 0.
+ *   Refusals     PF_EINVAL: a NULL context, query or out_count; NULL out_uid / out_score with
+ *                topk > 0; topk < 0; cap <= 0 or above INT32_MAX; pool < 1; lambda outside [0, 1] or
+ *                NaN; a window the window setter would refuse; what the call underneath refuses.
+ *                PF_EUNSUPP: pool > PF_DIVERSE_MAX_POOL; a context sharded into more than one shard.
+ *                PF_ENOMEM: a device buffer cannot be had.
+ */
+#define PF_DIVERSE_MAX_POOL 1024
+typedef struct pf_diverse_query {
+    int64_t  cap;        /* most candidates the window may hold; > 0, <= INT32_MAX       */
+    int32_t  pool;       /* M: the first M of the ranking are the pool; 1 .. 1024        */
+    float    lambda;     /* in [0, 1]                                                    */
+    const pf_scan_window* window;   /* NULL = every rankable candidate                   */
+} pf_diverse_query;
+typedef struct pf_diverse_info { int64_t total, pool, pairs, picked; } pf_diverse_info;
+
+int pf_diverse_rerank(pf_ctx* ctx, const int32_t* uid, const float* score, int64_t n, float lambda, int32_t topk,
+                      const pf_field_select* select, int32_t* out_uid, float* out_score, float* out_pen,
+                      double* out_value, int32_t* out_count);
+int pf_recommend_diverse_interest(pf_ctx* ctx, int32_t uid, const pf_diverse_query* q, int32_t topk, int32_t* out_uid,
+                                  float* out_score, float* out_pen, double* out_value, int32_t* out_count,
+                                  pf_diverse_info* info);
+int pf_recommend_diverse_profile(pf_ctx* ctx, const pf_query_profile* profile, const pf_diverse_query* q, int32_t topk,
+                                 int32_t* out_uid, float* out_score, float* out_pen, double* out_value,
+                                 int32_t* out_count, pf_diverse_info* info);
+int pf_recommend_diverse_group(pf_ctx* ctx, const pf_group_query* group, const pf_diverse_query* q, int32_t topk,
+                               int32_t* out_uid, float* out_score, float* out_pen, double* out_value,
+                               int32_t* out_count, pf_diverse_info* info);
+
+/*
  * Device-resident all-candidates scan for the multi-GPU bench: scores the
  * queries against this context's shard and writes, per query, `topk` packed
  * 64-bit keys to DEVICE memory d_keys[nq*topk] on `stream` (a hipStream_t).

@@ -37,6 +37,13 @@ and one route of the engine's own:
                                         the api_cli JSON line for "CLUBS ...": club recommendations for a stored user
                                         from its most similar users, whether or not it has an adj_list row.
 
+    POST /api/match and /api/group      "diverse": {"lambda": 0.7, "pool": 200} makes the reply's list the diverse top-k
+                                        (pokec_fas.h "Diverse top-k"): the window's first `pool` users re-ranked by
+                                        maximal marginal relevance, each item with its "pen"; the reply ends with
+                                        "total" and "pool".  Not together with "all", "top_clubs" or "neighbours".
+    GET /api/diverse/{uid}?topk=20&lam=0.7&pool=&min_score=
+                                        the api_cli JSON line for "DIVERSE ...": the same for a stored user.
+
 What differs, because the reference's file cannot run as written:
   * it has unresolved merge-conflict markers (app.py:38-42, 147-159); the start-up wait here
     is the HEAD side's 120 s;
@@ -95,7 +102,33 @@ def window_words(body):
         if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 2**31 - 1:
             raise ValueError("all must be a cap between 1 and 2147483647")
         words.append("all=%d" % v)
-    return words + club_words(body)
+    return words + club_words(body) + diverse_words(body)
+
+
+def _lambda(v):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:  # NaN fails the comparison
+        raise ValueError("lambda must be a number between 0 and 1")
+    return repr(float(v))
+
+
+def diverse_words(body):
+    """The diverse top-k words of a /api/match or /api/group body: "diverse": {"lambda": x, "pool": m}
+    (pool optional, 1 .. 1024); not together with "all", "top_clubs" or "neighbours": the reply holds one list."""
+    d = body.get("diverse")
+    if d is None:
+        return []
+    if not isinstance(d, dict) or set(d) - {"lambda", "pool"} or "lambda" not in d:
+        raise ValueError("diverse must be {\"lambda\": x, \"pool\": m}")
+    for other in ("all", "top_clubs", "neighbours"):
+        if body.get(other) is not None:
+            raise ValueError("diverse cannot be combined with " + other)
+    words = ["diverse=" + _lambda(d["lambda"])]
+    m = d.get("pool")
+    if m is not None:
+        if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 1024:
+            raise ValueError("pool must be between 1 and 1024")
+        words.append("pool=%d" % m)
+    return words
 
 
 def club_words(body):
@@ -135,13 +168,28 @@ def clubs_line(uid, topk=20, min_score=None, neighbours=None, cap=None):
     return " ".join(words)
 
 
+def diverse_line(uid, topk=20, lam=0.7, pool=None, min_score=None):
+    """The api_cli "DIVERSE ..." line of GET /api/diverse/{uid}; ValueError on a value out of range."""
+    for name, v, lo, hi in (("uid", uid, 0, 2**31 - 1), ("topk", topk, 0, 1 << 20), ("pool", pool, 1, 1024)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi):
+            raise ValueError("%s must be between %d and %d" % (name, lo, hi))
+    words = ["DIVERSE", str(topk), str(uid), _lambda(lam)]
+    if pool is not None:
+        words.append("pool=%d" % pool)
+    if min_score is not None:
+        if isinstance(min_score, bool) or not isinstance(min_score, (int, float)) or min_score != min_score:
+            raise ValueError("min_score must be a number")
+        words.append("min=" + repr(float(min_score)))
+    return " ".join(words)
+
+
 def match_line(body):
     """The api_cli "MATCH ..." line of a POST /api/match body (csrc/match_line.h); ValueError on a
     field of the wrong shape."""
     if not isinstance(body, dict):
         raise ValueError("the body must be a JSON object")
     unknown = set(body) - {"topk", "public", "gender", "completion", "age", "region", "clubs", "friends", "exclude", "tokens",
-                           "min_score", "after", "count", "all", "top_clubs", "neighbours"}
+                           "min_score", "after", "count", "all", "top_clubs", "neighbours", "diverse"}
     if unknown:
         raise ValueError("unknown field: " + sorted(unknown)[0])
 
@@ -178,7 +226,7 @@ def group_line(body):
     if not isinstance(body, dict):
         raise ValueError("the body must be a JSON object")
     unknown = set(body) - {"seeds", "topk", "agg", "exclude", "exclude_adj", "min_score", "after", "count", "all",
-                           "top_clubs", "neighbours"}
+                           "top_clubs", "neighbours", "diverse"}
     if unknown:
         raise ValueError("unknown field: " + sorted(unknown)[0])
 
@@ -377,6 +425,14 @@ def create_app(root, cli_cmd=None, load_users=None, ready_timeout=120.0, request
     def api_clubs(uid: int, topk: int = 20, min_score: float = None, neighbours: int = None, cap: int = None):
         try:
             line = clubs_line(uid, topk, min_score, neighbours, cap)
+        except (ValueError, TypeError) as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        return JSONResponse(cli_json(line))
+
+    @app.get("/api/diverse/{uid}")
+    def api_diverse(uid: int, topk: int = 20, lam: float = 0.7, pool: int = None, min_score: float = None):
+        try:
+            line = diverse_line(uid, topk, lam, pool, min_score)
         except (ValueError, TypeError) as e:
             raise HTTPException(status_code=422, detail=str(e))
         return JSONResponse(cli_json(line))

@@ -17,6 +17,12 @@
 // (pf_recommend_clubs_profile / _group).  CLUBS <topk> <uid> [min=<float>] [m=<M>] [cap=<n>] is the same
 // for a stored user (pf_recommend_clubs_interest): {"recommendations":{"clubs":[..]},"total":N,"used":U}
 // and "overflow":true when the window holds more than cap (default 1048576) candidates.
+// MATCH and GROUP also take diverse=<lambda> [pool=<M>] (match_line.h): the reply's list is then the
+// diverse top-k of the line's window (pf_recommend_diverse_profile / _group), each item with its "pen",
+// and the reply ends with "total":N,"pool":M; not together with all=, topclubs= or m=.  DIVERSE <topk> <uid> <lambda> [pool=<M>] [min=<float>]
+// [cap=<n>] is the same for a stored user (pf_recommend_diverse_interest):
+// {"recommendations":{"interest":[{"id":..,"score":..,"pen":..},..]},"total":N,"pool":M} and
+// "overflow":true when the window holds more than cap (default 1048576) candidates.
 //
 //   pokec_api_cli [load_users] [--root DIR] [--device N] [--no-cap] [--cache PATH]
 //
@@ -85,6 +91,41 @@ void write_list(std::ostringstream& os, const char* name, const List& l, const p
         os << "}";
     }
     os << "]";
+}
+
+// a diverse list: write_list's items with the penalty each was picked at
+void write_diverse_list(std::ostringstream& os, const char* name, const List& l, const std::vector<float>& pen) {
+    os << "\"" << name << "\":[";
+    for (int i = 0; i < l.n; ++i)
+        os << (i ? "," : "") << "{\"id\":" << l.id[i] << ",\"score\":" << std::fixed << std::setprecision(6) << l.score[i] << ",\"pen\":"
+           << pen[(size_t)i] << "}";
+    os << "]";
+}
+
+// The diverse list of a MATCH / GROUP / DIVERSE line: call(q, topk, ids, scores, pen, n, info) is the
+// engine call; the reply, or the engine-failure line.
+template <class Call>
+std::string diverse_reply(pf_ctx* ctx, const char* name, int topk, float lambda, int32_t pool, const pf_scan_window& win, int64_t cap,
+                          Call call) {
+    pf_scan_window w = win;
+    w.fields &= ~PF_WIN_COUNT;  // the reply carries the total anyway
+    pf_diverse_query q{};
+    q.cap = cap;
+    q.pool = pool > 0 ? pool : pokec::kDiversePoolDefault;
+    q.lambda = lambda;
+    q.window = w.fields ? &w : nullptr;
+    List r(topk > 0 ? topk : 1);
+    std::vector<float> pen((size_t)(topk > 0 ? topk : 1));
+    pf_diverse_info di{};
+    if (call(&q, (int32_t)topk, r.id.data(), r.score.data(), pen.data(), &r.n, &di) != PF_OK) {
+        std::cerr << "[api_cli] engine: " << pf_last_error(ctx) << "\n";
+        return "{\"error\":\"engine failure\",\"detail\":\"" + json_escape(pf_last_error(ctx)) + "\"}";
+    }
+    std::ostringstream os;
+    os << "{\"recommendations\":{";
+    write_diverse_list(os, name, r, pen);
+    os << "},\"total\":" << di.total << ",\"pool\":" << di.pool << (di.total > q.cap ? ",\"overflow\":true" : "") << "}";
+    return os.str();
 }
 
 // The score window of one MATCH / GROUP line (match_line.h: min=, after=, count): set for the span of
@@ -273,6 +314,14 @@ int main(int argc, char** argv) {
                 continue;
             }
             const pf_query_profile q = m.profile();
+            if (m.diverse >= 0.f) {
+                std::cout << diverse_reply(ctx, "interest", m.topk, m.diverse, m.diverse_pool, m.window, (int64_t)1 << 20,
+                                           [&](const pf_diverse_query* dq, int32_t k, int32_t* ou, float* os_, float* op, int32_t* n, pf_diverse_info* di) {
+                                               return pf_recommend_diverse_profile(ctx, &q, dq, k, ou, os_, op, nullptr, n, di);
+                                           })
+                          << std::endl;
+                continue;
+            }
             List r(m.topk > 0 ? m.topk : 1);
             const WindowScope ws(ctx, m.window);
             const CollectScope cs(ctx, m.collect);
@@ -314,7 +363,8 @@ int main(int argc, char** argv) {
             std::vector<int32_t> seeds, excl;
             pf_scan_window win{};
             int64_t collect = 0;
-            int32_t club_topk = 0, club_m = -1;
+            int32_t club_topk = 0, club_m = -1, dpool = 0;
+            float dlam = -1.f;
             uint32_t flags = 0;
             bool ok = !iss.fail() && topk >= 0 && (agg == "mean" || agg == "min" || agg == "max");
             auto number = [](const std::string& t, int32_t& v) {
@@ -330,7 +380,10 @@ int main(int argc, char** argv) {
                 const int ww = pokec::parse_window_word(w, win);
                 const int cw = ww == 0 ? pokec::parse_collect_word(w, collect) : 0;
                 const int kw = ww == 0 && cw == 0 ? pokec::parse_clubs_word(w, club_topk, club_m) : 0;
-                if (ww != 0) {
+                const int dw = ww == 0 && cw == 0 && kw == 0 ? pokec::parse_diverse_word(w, dlam, dpool) : 0;
+                if (dw != 0) {
+                    ok = dw > 0;
+                } else if (ww != 0) {
                     ok = ww > 0;
                 } else if (cw != 0) {
                     ok = cw > 0;
@@ -350,14 +403,23 @@ int main(int argc, char** argv) {
                     seeds.push_back(v);
                 }
             }
-            if (!ok || seeds.empty() || (club_m >= 0 && club_topk == 0)) {
+            if (!ok || seeds.empty() || (club_m >= 0 && club_topk == 0) || !pokec::diverse_words_ok(dlam, dpool, collect, club_topk, club_m)) {
                 std::cout << "{\"error\":\"bad request\",\"detail\":\"GROUP <topk> <mean|min|max> <uid>... [noadj] [exclude=<uid,...>] [min=<float>] [after=<hex>:<uid>] [count] [all=<cap>]"
-                          << (club_topk > 0 || club_m >= 0 ? " [topclubs=<topk>] [m=<M>]" : "") << "\"}"
+                          << (club_topk > 0 || club_m >= 0 ? " [topclubs=<topk>] [m=<M>]" : "")
+                          << (dlam >= 0.f || dpool > 0 ? " [diverse=<lambda>] [pool=<M>]" : "") << "\"}"
                           << std::endl;
                 continue;
             }
             const pf_group_query q{seeds.data(), (int32_t)seeds.size(), agg == "mean" ? PF_GROUP_MEAN : (agg == "min" ? PF_GROUP_MIN : PF_GROUP_MAX),
                                    flags, excl.empty() ? nullptr : excl.data(), (int32_t)excl.size()};
+            if (dlam >= 0.f) {
+                std::cout << diverse_reply(ctx, "group", topk, dlam, dpool, win, (int64_t)1 << 20,
+                                           [&](const pf_diverse_query* dq, int32_t k, int32_t* ou, float* os_, float* op, int32_t* n, pf_diverse_info* di) {
+                                               return pf_recommend_diverse_group(ctx, &q, dq, k, ou, os_, op, nullptr, n, di);
+                                           })
+                          << std::endl;
+                continue;
+            }
             List r(topk > 0 ? topk : 1);
             const WindowScope ws(ctx, win);
             const CollectScope cs(ctx, collect);
@@ -424,6 +486,34 @@ int main(int argc, char** argv) {
             write_list(os, "clubs", cl, ds);
             os << "},\"total\":" << ci.total << ",\"used\":" << ci.used << (ci.total > cq.cap ? ",\"overflow\":true" : "") << "}";
             std::cout << os.str() << std::endl;
+            continue;
+        }
+        if (cmd == "DIVERSE") {
+            // DIVERSE <topk> <uid> <lambda> [pool=<M>] [min=<float>] [cap=<n>]
+            std::istringstream iss(line);
+            std::string w, lam;
+            long long topk = -1, cu = -1, capv = (long long)1 << 20;
+            iss >> w >> topk >> cu >> lam;
+            pf_scan_window win{};
+            float dlam = -1.f;
+            int32_t dpool = 0;
+            bool ok = !iss.fail() && topk >= 0 && topk <= (1 << 20) && cu >= 0 && cu <= 2147483647LL &&
+                      pokec::parse_diverse_word("diverse=" + lam, dlam, dpool) > 0;
+            while (ok && iss >> w) {
+                if (w.rfind("min=", 0) == 0) ok = pokec::parse_window_word(w, win) > 0;
+                else if (w.rfind("pool=", 0) == 0) ok = pokec::parse_diverse_word(w, dlam, dpool) > 0;
+                else if (w.rfind("cap=", 0) == 0) ok = w.size() > 4 && w[4] != '+' && w[4] != '-' && pokec::match_detail::to_int(w.substr(4), 1, 2147483647LL, capv);
+                else ok = false;
+            }
+            if (!ok) {
+                std::cout << "{\"error\":\"bad request\",\"detail\":\"DIVERSE <topk> <uid> <lambda> [pool=<M>] [min=<float>] [cap=<n>]\"}" << std::endl;
+                continue;
+            }
+            std::cout << diverse_reply(ctx, "interest", (int)topk, dlam, dpool, win, (int64_t)capv,
+                                       [&](const pf_diverse_query* dq, int32_t k, int32_t* ou, float* os_, float* op, int32_t* n, pf_diverse_info* di) {
+                                           return pf_recommend_diverse_interest(ctx, (int32_t)cu, dq, k, ou, os_, op, nullptr, n, di);
+                                       })
+                      << std::endl;
             continue;
         }
         if (cmd == "EXPLAIN" && xa >= 0 && xb >= 0) {

@@ -17,6 +17,12 @@
 // topclubs adds a "clubs" list to the reply: the clubs of the window's first M neighbours (m=0 or no m:
 // the whole window), scored by the neighbours' scores, with names.  (MATCH's clubs=<id,..> is the
 // profile's own club list, so the new word cannot be spelt clubs=.)  m without topclubs is malformed.
+// The words of diverse top-k (pokec_fas.h "Diverse top-k"), on both commands and on DIVERSE:
+//         [diverse=<lambda>] [pool=<M>]      0 <= lambda <= 1, 1 <= M <= 1024 (default 200)
+// diverse makes the reply's list the diverse one: the window's first M candidates re-ranked by maximal
+// marginal relevance, topk of them, each item with its "pen", and the reply ends with "total" and "pool"
+// (so count adds nothing, and no "next" follows: a diverse list has no next page).  pool without diverse
+// is malformed, and so is diverse together with all=, topclubs= or m=: the reply holds one list.
 //
 // A field that is not given is missing; an empty region part ("region=3,,27") is missing; c<t> is
 // text column t of the engine's list, as token ids (the text -> id ETL is not part of the engine).
@@ -43,6 +49,8 @@ struct MatchLine {
     int64_t collect = 0;      // all=<cap>; 0: the line has no such word
     int32_t club_topk = 0;    // topclubs=<topk>; 0: the line has no such word
     int32_t club_m = -1;      // m=<M>; -1: the line has no such word
+    float diverse = -1.f;     // diverse=<lambda>; below 0: the line has no such word
+    int32_t diverse_pool = 0; // pool=<M>; 0: the line has no such word
     std::vector<std::vector<std::pair<int32_t, int32_t>>> cols;  // [n_cols] (tid, tf) in the line's order
     // the C struct over this object's arrays (valid while the object lives and is not changed)
     std::vector<int64_t> off;
@@ -142,6 +150,30 @@ inline int parse_clubs_word(const std::string& w, int32_t& topk, int32_t& m) {
     (is_top ? topk : m) = (int32_t)v;
     return 1;
 }
+// One word of a MATCH / GROUP / DIVERSE line as a word of diverse top-k: 1 = taken, 0 = another word,
+// -1 = malformed (lambda not a number in [0, 1], pool not a number in 1 .. PF_DIVERSE_MAX_POOL)
+inline int parse_diverse_word(const std::string& w, float& lambda, int32_t& pool) {
+    if (w.rfind("diverse=", 0) == 0) {
+        const std::string val = w.substr(8);
+        char* end = nullptr;
+        const float f = std::strtof(val.c_str(), &end);
+        if (val.empty() || *end != '\0' || !(f >= 0.f && f <= 1.f)) return -1;
+        lambda = f;
+        return 1;
+    }
+    if (w.rfind("pool=", 0) != 0) return 0;
+    const std::string val = w.substr(5);
+    long long v = 0;
+    if (val.empty() || val[0] == '+' || val[0] == '-' || !match_detail::to_int(val, 1, PF_DIVERSE_MAX_POOL, v)) return -1;
+    pool = (int32_t)v;
+    return 1;
+}
+// whether the diverse words of a line go together: pool needs diverse, diverse excludes all= and the
+// clubs words
+inline bool diverse_words_ok(float lambda, int32_t pool, int64_t collect, int32_t club_topk, int32_t club_m) {
+    return lambda >= 0.f ? collect == 0 && club_topk == 0 && club_m < 0 : pool == 0;
+}
+constexpr int32_t kDiversePoolDefault = 200;
 // the cursor token of a result: its score's float bits and its uid
 inline std::string window_cursor(float score, int32_t uid) {
     uint32_t bits = 0;
@@ -173,6 +205,9 @@ inline bool parse_match_line(const std::string& rest, int n_cols, MatchLine& m, 
         const int kw = parse_clubs_word(w, m.club_topk, m.club_m);
         if (kw < 0) { why = "bad value: " + w; return false; }
         if (kw > 0) continue;
+        const int dw = parse_diverse_word(w, m.diverse, m.diverse_pool);
+        if (dw < 0) { why = "bad value: " + w; return false; }
+        if (dw > 0) continue;
         const size_t eq = w.find('=');
         if (eq == std::string::npos || eq == 0) { why = "not key=value: " + w; return false; }
         const std::string key = w.substr(0, eq), val = w.substr(eq + 1);
@@ -224,6 +259,10 @@ inline bool parse_match_line(const std::string& rest, int n_cols, MatchLine& m, 
         if (!ok) { why = "bad value: " + w; return false; }
     }
     if (m.club_m >= 0 && m.club_topk == 0) { why = "m= without topclubs="; return false; }
+    if (!diverse_words_ok(m.diverse, m.diverse_pool, m.collect, m.club_topk, m.club_m)) {
+        why = "pool= without diverse=, or diverse= with all= / topclubs= / m=";
+        return false;
+    }
     return true;
 }
 

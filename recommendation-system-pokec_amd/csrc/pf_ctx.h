@@ -23,6 +23,7 @@
 
 #include "pf_batch.h"
 #include "pf_clubsum.h"
+#include "pf_diverse.h"
 #include "pf_dbuf.h"
 #include "pf_jobs.h"
 #include "pf_store.h"
@@ -230,6 +231,8 @@ struct pf_ctx {
     bool coll_set = false;
     // clubs by interest (pf_clubsum.h): the stage's workspaces, grown on demand
     pf::ClubSumWs clubs_ws;
+    // diverse top-k (pf_diverse.h): the pair-score matrix, the by-list pool and the stage's picks
+    pf::DiverseWs diverse_ws;
     int32_t n_shards = 1;                // pf_set_shard's count (the clubs-by-interest calls refuse more than one)
     // pinned staging ring for the per-call query upload (a slot is reused only after
     // the copy that read it has completed)

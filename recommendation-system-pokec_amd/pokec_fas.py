@@ -45,7 +45,9 @@ EXPORTS = ["pf_abi_version", "pf_open", "pf_close", "pf_last_error", "pf_num_use
            "pf_recommend_interest_profile_terms",
            "pf_recommend_group", "pf_group_scores", "pf_group_plan_of", "pf_group_image_lds",
            "pf_set_scan_window", "pf_scan_window_totals", "pf_set_scan_collect", "pf_scan_collected",
-           "pf_recommend_clubs_interest", "pf_recommend_clubs_profile", "pf_recommend_clubs_group"]
+           "pf_recommend_clubs_interest", "pf_recommend_clubs_profile", "pf_recommend_clubs_group",
+           "pf_diverse_rerank", "pf_recommend_diverse_interest", "pf_recommend_diverse_profile",
+           "pf_recommend_diverse_group"]
 # include/pokec_io.h: loaders and hold-out drivers
 IO_EXPORTS = ["pf_dataset_load", "pf_dataset_load_cached", "pf_dataset_free", "pf_dataset_desc", "pf_dataset_info_get", "pf_dataset_column",
               "pf_dataset_profile_order", "pf_dataset_adj_order", "pf_dataset_profile_json", "pf_dataset_club_name",
@@ -368,6 +370,19 @@ class ClubsInfo(ctypes.Structure):
         return {"total": self.total, "used": self.used, "contributions": self.contributions, "clubs": self.clubs}
 
 
+PF_DIVERSE_MAX_POOL = 1024
+
+
+class DiverseQuery(ctypes.Structure):
+    """pf_diverse_query: the pool of a diverse top-k call (cap, M, lambda, window)."""
+    _fields_ = [("cap", ctypes.c_int64), ("pool", ctypes.c_int32), ("lam", ctypes.c_float), ("window", ctypes.c_void_p)]
+
+
+class DiverseInfo(ctypes.Structure):
+    """pf_diverse_info: candidates in the window, the pool's size, pairs scored, users picked."""
+    _fields_ = [("total", ctypes.c_int64), ("pool", ctypes.c_int64), ("pairs", ctypes.c_int64), ("picked", ctypes.c_int64)]
+
+
 class GroupPlan(ctypes.Structure):
     """pf_group_plan: what a group scan launches (kept seeds, passes, global-memory images, bytes)."""
     _fields_ = [("n_seeds", ctypes.c_int32), ("n_passes", ctypes.c_int32), ("n_global", ctypes.c_int32),
@@ -456,6 +471,10 @@ def lib():
         L.pf_recommend_clubs_interest.argtypes = [V, ctypes.c_int32, V, ctypes.c_int32, V, V, V, V]
         L.pf_recommend_clubs_profile.argtypes = [V, V, V, ctypes.c_int32, V, V, V, V]
         L.pf_recommend_clubs_group.argtypes = [V, V, V, ctypes.c_int32, V, V, V, V]
+        L.pf_diverse_rerank.argtypes = [V, V, V, I64, ctypes.c_float, I32, V, V, V, V, V, V]
+        L.pf_recommend_diverse_interest.argtypes = [V, I32, V, I32, V, V, V, V, V, V]
+        L.pf_recommend_diverse_profile.argtypes = [V, V, V, I32, V, V, V, V, V, V]
+        L.pf_recommend_diverse_group.argtypes = [V, V, V, I32, V, V, V, V, V, V]
         L.pf_scan_collected.argtypes = [V, V, V, I64, ctypes.POINTER(I64), ctypes.POINTER(I64)]
         L.pf_merge_keys_async.argtypes = [V, V, I32, I32, I32, V, V]
         L.pf_decode_keys.argtypes = [V, I32, V, V, V]
@@ -826,6 +845,67 @@ class FasEngine:
         g = GroupQuery.make(seeds, agg, exclude, exclude_adj)
         return self._clubs_interest(self._L.pf_recommend_clubs_group, "pf_recommend_clubs_group", ctypes.byref(g), k,
                                     neighbours, cap, window, keep_own, filter, select)
+
+    # -- diverse top-k (pf_diverse_query): a ranking re-ranked by maximal marginal relevance
+    def diverse_rerank(self, uids, scores, k, lam, select=None):
+        """Re-rank a list the caller holds: (ids, scores, pen, value), k picks in pick order.  Each
+        pick maximises lam * score - (1 - lam) * (its highest FAS with anything picked before);
+        ties go to the earlier entry.  Unknown uids are dropped, of a repeated uid the first entry
+        counts, at most PF_DIVERSE_MAX_POOL entries remain.  select (a FieldSelect): the selection
+        of the similarities; the scan selection in force plays no part."""
+        u = _i32(uids)
+        s = np.ascontiguousarray(np.atleast_1d(np.asarray(scores)), dtype=np.float32)
+        if len(u) != len(s):
+            raise ValueError("diverse_rerank: uids and scores differ in length")
+        k = max(int(k), 0)
+        ou, os_, op = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float32), np.zeros(max(k, 1), np.float32)
+        ov = np.zeros(max(k, 1), np.float64)
+        n = np.zeros(1, np.int32)
+        self._check(self._L.pf_diverse_rerank(self.h, u.ctypes.data, s.ctypes.data, len(u), float(lam), k,
+                                              None if select is None else ctypes.addressof(select), ou.ctypes.data,
+                                              os_.ctypes.data, op.ctypes.data, ov.ctypes.data, n.ctypes.data),
+                    "pf_diverse_rerank")
+        return ou[:n[0]].copy(), os_[:n[0]].copy(), op[:n[0]].copy(), ov[:n[0]].copy()
+
+    def _diverse(self, fn, name, arg, k, lam, pool, cap, window, filter, select):
+        q = DiverseQuery()
+        q.cap, q.pool, q.lam = int(cap), int(pool), float(lam)
+        q.window = None if window is None else ctypes.addressof(window)
+        k = max(int(k), 0)
+        ou, os_, op = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float32), np.zeros(max(k, 1), np.float32)
+        ov = np.zeros(max(k, 1), np.float64)
+        n = np.zeros(1, np.int32)
+        info = DiverseInfo()
+        with self._scoped(filter, select):
+            self._check(fn(self.h, arg, ctypes.byref(q), k, ou.ctypes.data, os_.ctypes.data, op.ctypes.data, ov.ctypes.data,
+                           n.ctypes.data, ctypes.byref(info)), name)
+        return ou[:n[0]].copy(), os_[:n[0]].copy(), {"total": info.total, "pool": info.pool, "pairs": info.pairs,
+                                                     "pen": op[:n[0]].copy(), "value": ov[:n[0]].copy()}
+
+    def recommend_diverse_interest(self, uid, k, lam=0.7, pool=200, cap=1 << 20, window=None, filter=None, select=None):
+        """Diverse top-k for a stored user: (ids, scores, info).  The pool is the first `pool`
+        (<= PF_DIVERSE_MAX_POOL) candidates of `window` (a ScanWindow; None = everyone rankable) in the
+        all-candidates ranking; k of them are picked as in diverse_rerank, the similarities scored
+        under the selection of the ranking.  info: total (the window's candidates), pool, pairs, and
+        per pick pen (float32) and value (float64).  cap: the most candidates the window may hold
+        (more: an empty list, info["total"] says how many).  filter / select as in
+        recommend_interest_all.  Nothing in force on the engine changes."""
+        return self._diverse(self._L.pf_recommend_diverse_interest, "pf_recommend_diverse_interest", int(uid), k, lam, pool,
+                             cap, window, filter, select)
+
+    def recommend_diverse_profile(self, profile, k, lam=0.7, pool=200, cap=1 << 20, window=None, filter=None, select=None):
+        """recommend_diverse_interest for a QueryProfile (a person who is not a user of the corpus)."""
+        ps, arr = self._profile_array(profile)
+        return self._diverse(self._L.pf_recommend_diverse_profile, "pf_recommend_diverse_profile", ctypes.byref(arr), k, lam,
+                             pool, cap, window, filter, select)
+
+    def recommend_diverse_group(self, seeds, k, agg="mean", exclude=(), exclude_adj=False, lam=0.7, pool=200, cap=1 << 20,
+                                window=None, filter=None, select=None):
+        """recommend_diverse_interest for a group of seed users (as recommend_group); the relevance is
+        the group's aggregate."""
+        g = GroupQuery.make(seeds, agg, exclude, exclude_adj)
+        return self._diverse(self._L.pf_recommend_diverse_group, "pf_recommend_diverse_group", ctypes.byref(g), k, lam, pool,
+                             cap, window, filter, select)
 
     def group_scores(self, seeds, b_uid, agg="mean", select=None):
         """The group's aggregate score of each listed user (NaN for an unknown uid), with no filter and
